@@ -37,11 +37,28 @@ Bytes per step (counting what the step must move):
                 window shadowed by a later one in the step costs its keys only)
   Get           q*(4+2V) (key read + parameter read + value write)
 
-Prints ONE JSON line on rank 0 with roofline (per-kernel rates from HIP events
-on the launch stream, the dominant kernel's as `frac`, and the cold form's) and
+A plain run (`bench.py --gpus N --steps K --warmup W`) builds the window sets
+and the shard, warms up, times the K steps, writes the last step's pulls if
+--dump-outputs is given, and prints ONE JSON line on rank 0: the headline
+`value` with `ms_per_step`, the workload's `config` and the per-GPU spread.
+
+--dump-outputs DIR writes what the last timed step handed back, as float32
+.npy files: `pull_values.npy`, the step's pulled windows concatenated in pull
+order (a fixed, seeded sample of DUMP_MAX_ELEMS of them where they are more),
+and `param_sample.npy`, a Get of DUMP_PARAM_KEYS seeded keys of the shard
+after that step (what the steps' Adds left behind).  At N > 1 every rank
+writes its own (`..._rank<r>.npy`).  Inputs are seeded, so two runs with the
+same arguments write the same arrays.
+
+--full adds everything else to the same line: the self-check of the
+benchmarked state against a torch model before timing, roofline (per-kernel
+rates from HIP events on the launch stream, the dominant kernel's as `frac`,
+and the cold form's), zipf_sparse (cfg 3), extra (side measurements) and
 cpu_baseline (the oracle restatement of the reference storages timed on this
 host by rank 0: one thread with one storage at N = 1, beside 8 server threads
-with 8 storages; at N > 1 the 8-thread sample is the value).
+with 8 storages; at N > 1 the 8-thread sample is the value).  The --no-*
+options drop parts of a --full run; --cold-only and --vector-only are --full
+runs of one part alone.
 """
 from __future__ import annotations
 
@@ -81,6 +98,12 @@ def parse(argv=None):
                         "and more draws bring the ranks' totals over the timed steps to what an endless stream "
                         "of draws gives them (the largest rank share over the mean at N = 8: 1.078 with 16 sets, "
                         "1.027 with 64)"),
+    p.add_argument("--full", action="store_true",
+                   help="beside the headline: the self-check, the per-kernel roofline pass, the cold form, cfg 3 "
+                        "(Zipf), the side measurements and the CPU baseline (the --no-* options drop parts of it)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed step's pulls (and a Get of seeded keys of the shard after it) as "
+                        "float32 .npy files into DIR")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-extra", action="store_true", help="skip the side measurements (e2e, f64, accumulate)")
     p.add_argument("--no-zipf", action="store_true", help="skip the cfg-3 sparse (Zipf) measurement")
@@ -95,7 +118,9 @@ def parse(argv=None):
     p.add_argument("--vector-only", action="store_true",
                    help="time only the VectorStorage restatement at --vector-sizes (no GPU; e.g. the one "
                         "measured 1e6-key run of config 1) and print its JSON")
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    args.full = args.full or args.cold_only or args.vector_only  # one part of the full run alone
+    return args
 
 
 def default_sets(sets, world):
@@ -417,6 +442,46 @@ def run_form(form, steps, warmup, world, dev):
     total = sum_over_ranks(float(a + g), world, dev)
     return {"GB/s": total / elapsed / 1e9, "ms_per_step": elapsed / steps * 1e3, "elapsed": elapsed,
             "own_GB/s": (a + g) / own / 1e9, "bytes": total}
+
+
+# ------------------------------------------------------------ --dump-outputs
+
+DUMP_MAX_ELEMS = 8 << 20    # pulled values kept (32 MB of float32; a fixed sample of a larger pull)
+DUMP_PARAM_KEYS = 1 << 20   # keys of the shard read back after the last step (4 MB)
+DUMP_SEED = 4242
+
+
+def dump_positions(total, limit=DUMP_MAX_ELEMS, seed=DUMP_SEED):
+    """Which of a step's `total` pulled values (concatenated in pull order) are
+    written: all of them (None) up to `limit`, else `limit` positions drawn
+    once with a fixed seed, ascending — the same for every run and build."""
+    if total <= limit:
+        return None
+    return np.sort(np.random.default_rng(seed).integers(0, total, size=limit, dtype=np.int64))
+
+
+def dump_param_keys(lo, hi, n=DUMP_PARAM_KEYS, seed=DUMP_SEED + 1):
+    """The seeded keys of [lo, hi) read back after the last step, ascending."""
+    return lo + np.sort(np.random.default_rng(seed).integers(0, hi - lo, size=min(n, hi - lo), dtype=np.int64))
+
+
+def dump_outputs(path, form, last, lo, hi, rank, world, dev):
+    """Write what step `last` of `form` handed its caller: the pulled windows'
+    values, and a Get of dump_param_keys after it (module docstring)."""
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    tag = "" if world == 1 else f"_rank{rank}"
+    outs = form.outs[last % form.R]
+    flat = torch.cat(outs) if outs else torch.empty(0, dtype=torch.float32, device=dev)
+    pos = dump_positions(flat.numel())
+    if pos is not None:
+        flat = flat[torch.from_numpy(pos).to(dev)]
+    keys = torch.from_numpy(dump_param_keys(lo, hi)).to(torch.int32).to(dev)  # uint32 bit patterns
+    params = form.shard.get(keys)
+    torch.cuda.synchronize()
+    for name, t in (("pull_values", flat), ("param_sample", params)):
+        np.save(os.path.join(path, f"{name}{tag}.npy"), t.cpu().numpy().astype(np.float32, copy=False))
 
 
 # ------------------------------------------------------------ CPU baseline
@@ -1003,6 +1068,30 @@ def cold_form(dev, J, B, R, steps, warmup, space, n_pulls):
             "traffic_source": src}
 
 
+def roofline(ktimes, ms_per_step_evented, cold, cfg_key):
+    """The --full line's roofline record from the evented pass's per-kernel
+    times (the dominant kernel: the one with the most time in that pass)."""
+    dom = max(ktimes.items(), key=lambda kv: kv[1]["avg_ms"] * kv[1]["launches"])
+    achieved = dom[1]["GB/s"]
+    traffic, traffic_src = load_pmc(dom[0], cfg_key)
+    roof = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "kernel": dom[0],
+            "algorithmic_bytes_per_launch": dom[1]["algorithmic_bytes"],
+            "bytes_per_unit": "Add n*4 + 2*u*V (keys, last values, parameter writes), Get q*(4+2V); V=4, "
+                              "u = distinct pushed keys",
+            "timing": "HIP events on the launch stream around each launch of the two streaming "
+                      "kernels, over a second pass of the same K steps run right after the "
+                      "event-free timed region",
+            "ms_per_step_evented": ms_per_step_evented,
+            "kernels": kernel_fracs(ktimes)}
+    if cold is not None:
+        roof["cold"] = cold
+    if traffic_src:
+        roof["traffic_source"] = traffic_src
+        roof["traffic_over_algorithmic"] = traffic / dom[1]["algorithmic_bytes"]
+    return roof
+
+
 _T0 = time.perf_counter()
 
 
@@ -1075,13 +1164,18 @@ def main(argv=None):
     shard = ps.Shard(lo, hi, np.float32, device=local)
     shard.set_stream(stream.cuda_stream)  # torch events and the kernels share one stream
     form = Form(shard, sets, dev)
-    # correctness guard on the benchmarked state: one rotation from a cleared
-    # shard, every pull against a model of the shard
-    progress("headline: self-check")
-    form.self_check(lo, hi, dev)
+    if args.full:
+        # correctness guard on the benchmarked state: one rotation from a cleared
+        # shard, every pull against a model of the shard
+        progress("headline: self-check")
+        form.self_check(lo, hi, dev)
     progress("headline: timed steps")
     head = run_form(form, args.steps, max(args.warmup, R), world, dev)
-    ktimes, evented_s = evented(form, args.steps, world, dev)
+    if args.dump_outputs:
+        progress("headline: writing the last step's outputs")
+        dump_outputs(args.dump_outputs, form, args.steps - 1, lo, hi, rank, world, dev)
+    if args.full:
+        ktimes, evented_s = evented(form, args.steps, world, dev)
     touched = min(form.touched(i) for i in range(R))
     a_b, g_b = form.bytes(args.steps)
     own_bytes = a_b + g_b
@@ -1093,36 +1187,20 @@ def main(argv=None):
                "max_keys_pushed_per_step": max_over_ranks(n_push, world, dev)}
 
     zipf_res = None
-    if not args.no_zipf:
+    if args.full and not args.no_zipf:
         progress("cfg 3 (Zipf)")
         zipf_res, zb = zipf_sparse(prank, world, dev, lo, hi, B, args.steps)
     cold = None
-    if pworld == 1 and not args.no_cold:
+    if args.full and pworld == 1 and not args.no_cold:
         shard.set_stream(None)  # the cold shard takes the stream meanwhile
         progress("cold form")
         cold = cold_form(dev, J, B, R, args.steps, args.warmup, int(args.cold_keys), n_pulls)
         shard.set_stream(stream.cuda_stream)
 
-    # dominant kernel: the one with the most time in the evented pass
-    dom = max(ktimes.items(), key=lambda kv: kv[1]["avg_ms"] * kv[1]["launches"])
-    achieved = dom[1]["GB/s"]
-    cfg_key = {"n_gpus": world, "batches": J, "batch_keys": B, "sets": R, "form": "pull-free-slots"}
-    traffic, traffic_src = load_pmc(dom[0], cfg_key)
-    roof = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-            "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "kernel": dom[0],
-            "algorithmic_bytes_per_launch": dom[1]["algorithmic_bytes"],
-            "bytes_per_unit": "Add n*4 + 2*u*V (keys, last values, parameter writes), Get q*(4+2V); V=4, "
-                              "u = distinct pushed keys",
-            "timing": "HIP events on the launch stream around each launch of the two streaming "
-                      "kernels, over a second pass of the same K steps run right after the "
-                      "event-free timed region",
-            "ms_per_step_evented": evented_s / args.steps * 1e3,
-            "kernels": kernel_fracs(ktimes)}
-    if cold is not None:
-        roof["cold"] = cold
-    if traffic_src:
-        roof["traffic_source"] = traffic_src
-        roof["traffic_over_algorithmic"] = traffic / dom[1]["algorithmic_bytes"]
+    roof = None
+    if args.full:
+        roof = roofline(ktimes, evented_s / args.steps * 1e3, cold,
+                        {"n_gpus": world, "batches": J, "batch_keys": B, "sets": R, "form": "pull-free-slots"})
 
     result = {
         "metric": METRIC,
@@ -1158,17 +1236,18 @@ def main(argv=None):
             "param_bytes_touched_per_step_per_gpu": touched,
             "parallelism": f"range-sharded x{pworld} (no collective)",
         },
-        "roofline": roof,
         # cfg 4 reports per-GPU next to aggregate: each rank's own
         # bytes over its own time, min / max over ranks
         "per_gpu": per_gpu,
     }
+    if roof is not None:
+        result["roofline"] = roof
     if (prank, pworld) != (rank, world):
         result["config"]["emulated_rank"] = f"{prank}/{pworld} (probe: one rank's share alone on one GPU)"
     if zipf_res is not None:
         result["zipf_sparse"] = zipf_res
     extra = {}
-    if not args.no_extra:
+    if args.full and not args.no_extra:
         warm = Form(shard, sets, dev, pull="same")
         w = run_form(warm, args.steps, 2, world, dev)
         extra["cache_warm_step"] = {
@@ -1189,7 +1268,7 @@ def main(argv=None):
             del wf, wsets
     shard.set_stream(None)
     shard.close()
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         progress("cpu baseline")
         if pworld == 1:
             sizes = [int(x) for x in args.vector_sizes.split(",") if x]
@@ -1203,7 +1282,7 @@ def main(argv=None):
             result["cpu_baseline"] = cpu_baseline(list(sets[0]["bases"]), B, 16, [], servers=8)
     if zipf_res is not None:
         del zb
-    if pworld == 1 and not args.no_extra:
+    if args.full and pworld == 1 and not args.no_extra:
         progress("side measurements")
         extra["dense_f64_step"] = variant_f64(rank, world, J, B, dev, R, args.steps, lo, hi)
         extra["dense_accumulate_step"] = variant_accumulate(rank, world, J, B, dev, sets, args.steps, lo, hi)

@@ -84,6 +84,19 @@ def build_oracle():
         sys.path.pop(0)
 
 
+REFERENCE = os.environ.get("PSKV_REFERENCE_TREE", "/root/reference")
+
+
+def build_in_tree():
+    """tests/cpp/in_tree_frames.cpp against the reference's own headers, into
+    oracle/_ref/ (oracle/Makefile's in-tree target; tests/test_in_tree.py reads
+    the result), where a checkout of the reference is at hand; None where not."""
+    if not os.path.isdir(os.path.join(REFERENCE, "base", "third_party")):
+        return None
+    _run(["make", "-C", ORACLE_DIR, "in-tree", "REFERENCE=" + REFERENCE])
+    return os.path.join(ORACLE_DIR, "_ref", "in_tree_frames")
+
+
 RA_SRC = os.path.join(ROOT, "tools", "micro", "random_access.hip")
 RA_OUT = os.path.join(ROOT, "tools", "micro", "librandom_access.so")
 
@@ -100,7 +113,7 @@ def build_all(force=False):
     orc = build_oracle()
     progs = build_cpp_tests(force)
     ra = build_random_access(force)
-    return {"lib": lib, "cpp": progs, "oracle": orc, "random_access": ra}
+    return {"lib": lib, "cpp": progs, "oracle": orc, "random_access": ra, "in_tree": build_in_tree()}
 
 
 if __name__ == "__main__":

@@ -1,8 +1,9 @@
 // in_tree_frames.cpp — compiles include/ps/host_frames.hpp in its
 // PSKV_IN_REFERENCE_TREE form against the reference's own boundary types
 // (base/third_party/sarray.h, base/message.hpp), as INTEGRATION.md §2 tells a
-// maintainer to include it.  Built and linked by tests/test_in_tree.py (CPU;
-// never run there: pskv_host_alloc needs a GPU).
+// maintainer to include it.  Built and linked by oracle/Makefile's in-tree
+// target, checked by tests/test_in_tree.py (CPU; never run there:
+// pskv_host_alloc needs a GPU).
 #define PSKV_IN_REFERENCE_TREE 1
 
 #include "base/message.hpp"

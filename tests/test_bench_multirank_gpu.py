@@ -1,6 +1,6 @@
 """bench.py's N > 1 path end to end, as the driver launches it
 (`python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr
-127.0.0.1 ... bench.py --gpus N`), rehearsed on one GPU: two and four rank
+127.0.0.1 ... bench.py --gpus N`, here with --full), rehearsed on one GPU: two and four rank
 processes,
 gloo for the barrier and the reductions, both ranks' shards on cuda:0
 (PSKV_BENCH_BACKEND=gloo, PSKV_BENCH_SHARE_GPU=1 — rehearsal knobs the driver
@@ -37,7 +37,8 @@ def test_bench_ranks_one_gpu(cuda, world):
     env = dict(os.environ, PSKV_BENCH_BACKEND="gloo", PSKV_BENCH_SHARE_GPU="1", PSKV_SYNC_TIMEOUT_MS="60000")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world),
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-           os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "3", "--warmup", "1", "--sets", "4"]
+           os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "3", "--warmup", "1", "--sets", "4",
+           "--full"]
     r = subprocess.run(["timeout", "-k", "10", "400"] + cmd, capture_output=True, text=True, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-5000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -723,15 +723,23 @@ def test_overflow_growth_concurrent_shards(cuda, oracle_mod):
             kb, ke = 1_000_000 + 20_000 * i, 1_010_000 + 20_000 * i
             rng = np.random.default_rng(700 + i)
             seen = []
+            # device inputs stay alive until the shard's stream has passed the call
+            # (include/pskv.h): a kernel waiting for the grow service has not read
+            # them yet, and freed at once their memory goes to another thread's
+            # tensors, which that thread's shard fills on its own stream meanwhile
+            alive = []
             for b in range(bursts):
                 k = _burst(rng, b, kb, ke, 3000, sort=i % 2 == 1)
                 v = (rng.standard_normal(k.size) * 100).astype(np.float32)
                 pushes[i].append((k, v))
                 seen.append(k)
                 q = np.unique(np.concatenate(seen))
-                sh.add(tdev(k, cuda), tdev(v, cuda), sorted_hint=i % 2 == 1)
-                reads[i].append((q, sh.get(tdev(q, cuda)).cpu().numpy()))
+                dk, dv, dq = tdev(k, cuda), tdev(v, cuda), tdev(q, cuda)
+                alive += [dk, dv, dq]
+                sh.add(dk, dv, sorted_hint=i % 2 == 1)
+                reads[i].append((q, sh.get(dq).cpu().numpy()))
             sh.sync()
+            del alive
             reads[i].append((q, sh.get(q)))
         except Exception as e:  # re-raised on the main thread
             errors.append((i, e))

@@ -193,3 +193,33 @@ def test_bench_default_window_sets():
     assert bench.parse(["--sets", "4"]).sets == 4
     assert bench.default_sets(None, 1) == 16 and bench.default_sets(None, 8) == 64
     assert bench.default_sets(4, 8) == 4 and bench.default_sets(1, 1) == 2
+
+
+def test_bench_plain_and_full_options():
+    """A plain run is the headline alone: --full (off by default) turns the
+    other measurements on, and the single-part runs are --full runs."""
+    import bench
+
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    assert bench.parse(["--full"]).full is True
+    assert bench.parse(["--cold-only"]).full and bench.parse(["--vector-only"]).full
+    assert bench.parse(["--dump-outputs", "d"]).dump_outputs == "d"
+
+
+def test_bench_dump_sample_is_fixed():
+    """--dump-outputs keeps every pulled value up to its limit and a seeded,
+    ascending sample above it (the same positions in every run); with the
+    parameter read-back the files stay under 64 MB."""
+    import bench
+
+    assert bench.dump_positions(0) is None and bench.dump_positions(bench.DUMP_MAX_ELEMS) is None
+    p = bench.dump_positions(1000, limit=100)
+    assert p.shape == (100,) and p.dtype == np.int64 and int(p.min()) >= 0 and int(p.max()) < 1000
+    assert np.all(np.diff(p) >= 0) and np.array_equal(p, bench.dump_positions(1000, limit=100))
+    assert len(np.unique(p)) > 50  # spread over the output, not one spot
+    k = bench.dump_param_keys(1000, 5000, n=64)
+    assert k.shape == (64,) and int(k.min()) >= 1000 and int(k.max()) < 5000 and np.all(np.diff(k) >= 0)
+    assert np.array_equal(k, bench.dump_param_keys(1000, 5000, n=64))
+    assert bench.dump_param_keys(10, 14).shape == (4,)
+    assert (bench.DUMP_MAX_ELEMS + bench.DUMP_PARAM_KEYS) * 4 <= 64 * 10 ** 6

@@ -10,7 +10,7 @@
 set -o pipefail
 R=${GRAFT_REPO_ROOT:-$PWD}
 OUT=$R/gpurun_out/${1:-ab}
-ARGS=${2:-"--no-extra --no-cpu-baseline --no-zipf"}
+ARGS=${2:-"--full --no-extra --no-cpu-baseline --no-zipf"}
 mkdir -p "$OUT"
 LIB=$R/parameter_server_amd/libpskv.so
 SAVE=$(mktemp) && cp "$LIB" "$SAVE" || exit 1   # the tree's own build, put back at the end

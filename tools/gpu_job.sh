@@ -64,8 +64,9 @@
 #   smoke        __graft_entry__.smoke() (what the driver runs before the bench)
 #   shardsize    tools/shard_size_probe.py: K2g / K1 per key on 1e8 / 5e8 / 1e9-key shards (same windows)
 #   e2e          tools/e2e_probe.py (host-buffer Add / Get against raw PCIe copy rates)
-#   bench        bench.py --steps 20 (the driver's command line)
-#   benchdef     bench.py with no arguments (its defaults), timed by the job
+#   bench        bench.py --steps 20 (the driver's command line: the headline alone)
+#   benchfull    the same with --full (roofline, cold form, cfg 3, side measurements, CPU baseline)
+#   benchdef     bench.py --full at its defaults, timed by the job
 #   zipf         tools/zipf_probe.py kernel times on cfg 3
 #   zipf_bin     the same for K5a at 1024- and 512-thread workgroups
 #   profile      tools/gpu_profile.sh: rocprofv3 kernel trace + stats, FETCH / WRITE PMC passes (headline)
@@ -99,35 +100,35 @@ for step in "$@"; do
         -k "$TESTS_K" > "$OUT/tests_k.log" 2>&1 ;;
     align) timeout -k 10 200 python3 "$R/tools/align_probe.py" 0,1,2,3 20 > "$OUT/align.log" 2>&1 ;;
     foldcold) mkdir -p "$OUT/foldcold" && for i in 1 2 3; do for f in 1 0; do
-          PSKV_FOLD_REPLAY=$f timeout -k 10 200 python3 "$R/bench.py" --steps 50 --cold-only \
+          PSKV_FOLD_REPLAY=$f timeout -k 10 200 python3 "$R/bench.py" --full --steps 50 --cold-only \
             > "$OUT/foldcold/c_f${f}_$i.json" 2> "$OUT/foldcold/c_f${f}_$i.err" || exit 1
         done; done ;;
     foldab) mkdir -p "$OUT/foldab" && for i in 1 2 3; do for f in 1 0; do
-          PSKV_FOLD_REPLAY=$f timeout -k 10 200 python3 "$R/bench.py" --steps 100 --no-zipf --no-cpu-baseline \
+          PSKV_FOLD_REPLAY=$f timeout -k 10 200 python3 "$R/bench.py" --full --steps 100 --no-zipf --no-cpu-baseline \
             --no-extra --no-cold > "$OUT/foldab/h_f${f}_$i.json" 2> "$OUT/foldab/h_f${f}_$i.err" || exit 1
-          PSKV_FOLD_REPLAY=$f PSKV_BENCH_EMULATE=0/8 timeout -k 10 200 python3 "$R/bench.py" --steps 100 --no-zipf \
+          PSKV_FOLD_REPLAY=$f PSKV_BENCH_EMULATE=0/8 timeout -k 10 200 python3 "$R/bench.py" --full --steps 100 --no-zipf \
             --no-cpu-baseline --no-extra > "$OUT/foldab/r8_f${f}_$i.json" 2> "$OUT/foldab/r8_f${f}_$i.err" || exit 1
         done; done ;;
-    emu) PSKV_BENCH_EMULATE=0/8 timeout -k 10 200 python3 "$R/bench.py" --steps 20 --no-zipf --no-cpu-baseline --no-extra \
+    emu) PSKV_BENCH_EMULATE=0/8 timeout -k 10 200 python3 "$R/bench.py" --full --steps 20 --no-zipf --no-cpu-baseline --no-extra \
            > "$OUT/emu08.json" 2> "$OUT/emu08.err" &&
-         PSKV_BENCH_EMULATE=0/2 timeout -k 10 200 python3 "$R/bench.py" --steps 20 --no-zipf --no-cpu-baseline --no-extra \
+         PSKV_BENCH_EMULATE=0/2 timeout -k 10 200 python3 "$R/bench.py" --full --steps 20 --no-zipf --no-cpu-baseline --no-extra \
            > "$OUT/emu02.json" 2> "$OUT/emu02.err" ;;
     emu8all) for r in 0 1 2 3 4 5 6 7; do
-          PSKV_BENCH_EMULATE=$r/8 timeout -k 10 200 python3 "$R/bench.py" --steps ${EMU_STEPS:-50} --no-zipf --no-cpu-baseline \
+          PSKV_BENCH_EMULATE=$r/8 timeout -k 10 200 python3 "$R/bench.py" --full --steps ${EMU_STEPS:-50} --no-zipf --no-cpu-baseline \
             --no-extra > "$OUT/emu8_$r.json" 2> "$OUT/emu8_$r.err" || exit 1
         done ;;
     emu_curve) for n in 2 4; do for r in $(seq 0 $((n - 1))); do
-          PSKV_BENCH_EMULATE=$r/$n timeout -k 10 200 python3 "$R/bench.py" --steps ${EMU_STEPS:-50} --no-zipf --no-cpu-baseline \
+          PSKV_BENCH_EMULATE=$r/$n timeout -k 10 200 python3 "$R/bench.py" --full --steps ${EMU_STEPS:-50} --no-zipf --no-cpu-baseline \
             --no-extra > "$OUT/emu${n}_$r.json" 2> "$OUT/emu${n}_$r.err" || exit 1
         done; done ;;
     emutrace) PSKV_BENCH_EMULATE=0/8 timeout -k 10 200 rocprofv3 --kernel-trace --stats -d "$OUT/emutrace" -o run \
-          -- python3 "$R/bench.py" --steps 50 --no-zipf --no-cpu-baseline --no-extra > "$OUT/emutrace.log" 2>&1 ;;
-    emu_unroll) PSKV_BENCH_EMULATE=0/8 PSKV_UNROLL=4 timeout -k 10 200 python3 "$R/bench.py" --steps 20 --no-zipf \
+          -- python3 "$R/bench.py" --full --steps 50 --no-zipf --no-cpu-baseline --no-extra > "$OUT/emutrace.log" 2>&1 ;;
+    emu_unroll) PSKV_BENCH_EMULATE=0/8 PSKV_UNROLL=4 timeout -k 10 200 python3 "$R/bench.py" --full --steps 20 --no-zipf \
            --no-cpu-baseline --no-extra > "$OUT/emu08_u4.json" 2> "$OUT/emu08_u4.err" &&
-         PSKV_BENCH_EMULATE=0/8 timeout -k 10 200 python3 "$R/bench.py" --steps 20 --no-zipf --no-cpu-baseline \
+         PSKV_BENCH_EMULATE=0/8 timeout -k 10 200 python3 "$R/bench.py" --full --steps 20 --no-zipf --no-cpu-baseline \
            --no-extra > "$OUT/emu08_u8.json" 2> "$OUT/emu08_u8.err" ;;
     emu_u48) for rep in 1 2; do for r in 0 1; do for u in 8 4; do
-          PSKV_BENCH_EMULATE=$r/8 PSKV_UNROLL=$u timeout -k 10 200 python3 "$R/bench.py" --steps 50 --no-zipf \
+          PSKV_BENCH_EMULATE=$r/8 PSKV_UNROLL=$u timeout -k 10 200 python3 "$R/bench.py" --full --steps 50 --no-zipf \
             --no-cpu-baseline --no-extra > "$OUT/emu8_${r}_u${u}_$rep.json" 2> "$OUT/emu8_${r}_u${u}_$rep.err" || exit 1
         done; done; done ;;
     smalllat) timeout -k 10 300 "$R/tools/micro/small_latency" > "$OUT/small_latency.log" 2>&1 ;;
@@ -164,53 +165,53 @@ for step in "$@"; do
     abh) AB_PROG=e2e timeout -k 10 900 bash "$R/tools/ab_lib.sh" "$(basename "$OUT")/abh" > "$OUT/abh.log" 2>&1 ;;
     abb) timeout -k 10 900 bash "$R/tools/ab_lib.sh" "$(basename "$OUT")/abb" > "$OUT/abb.log" 2>&1 ;;
     abe) PSKV_BENCH_EMULATE=0/8 timeout -k 10 900 bash "$R/tools/ab_lib.sh" "$(basename "$OUT")/abe" \
-          "--no-extra --no-cpu-baseline --no-zipf --steps 50" > "$OUT/abe.log" 2>&1 ;;
+          "--full --no-extra --no-cpu-baseline --no-zipf --steps 50" > "$OUT/abe.log" 2>&1 ;;
     abocc) AB_VARIANTS="base occ3 occ4b" timeout -k 10 900 bash "$R/tools/ab_lib.sh" "$(basename "$OUT")/abocc" \
           > "$OUT/abocc.log" 2>&1 ;;
     abocce) PSKV_BENCH_EMULATE=0/8 AB_VARIANTS="base occ3 occ4b" timeout -k 10 900 bash "$R/tools/ab_lib.sh" \
-          "$(basename "$OUT")/abocce" "--no-extra --no-cpu-baseline --no-zipf --no-cold --steps 50" > "$OUT/abocce.log" 2>&1 ;;
+          "$(basename "$OUT")/abocce" "--full --no-extra --no-cpu-baseline --no-zipf --no-cold --steps 50" > "$OUT/abocce.log" 2>&1 ;;
     abk1) AB_VARIANTS="base k1occ6 k1occ4" timeout -k 10 900 bash "$R/tools/ab_lib.sh" "$(basename "$OUT")/abk1" \
           > "$OUT/abk1.log" 2>&1 &&
         PSKV_BENCH_EMULATE=0/8 AB_VARIANTS="base k1occ6 k1occ4" timeout -k 10 900 bash "$R/tools/ab_lib.sh" \
-          "$(basename "$OUT")/abk1e" "--no-extra --no-cpu-baseline --no-zipf --no-cold --steps 50" > "$OUT/abk1e.log" 2>&1 ;;
+          "$(basename "$OUT")/abk1e" "--full --no-extra --no-cpu-baseline --no-zipf --no-cold --steps 50" > "$OUT/abk1e.log" 2>&1 ;;
     abke) AB_VARIANTS="base kearly" timeout -k 10 900 bash "$R/tools/ab_lib.sh" "$(basename "$OUT")/abke" \
           > "$OUT/abke.log" 2>&1 &&
         PSKV_BENCH_EMULATE=0/8 AB_VARIANTS="base kearly" timeout -k 10 900 bash "$R/tools/ab_lib.sh" \
-          "$(basename "$OUT")/abkee" "--no-extra --no-cpu-baseline --no-zipf --no-cold --steps 50" > "$OUT/abkee.log" 2>&1 &&
-        for r in 1 2; do PSKV_EARLY=1 timeout -k 10 300 python3 "$R/bench.py" --steps 50 --no-zipf --no-extra \
+          "$(basename "$OUT")/abkee" "--full --no-extra --no-cpu-baseline --no-zipf --no-cold --steps 50" > "$OUT/abkee.log" 2>&1 &&
+        for r in 1 2; do PSKV_EARLY=1 timeout -k 10 300 python3 "$R/bench.py" --full --steps 50 --no-zipf --no-extra \
           --no-cpu-baseline > "$OUT/early1_$r.json" 2> "$OUT/early1_$r.err" || exit 1; done ;;
     graph) timeout -k 10 300 python3 "$R/tools/graph_probe.py" 10 > "$OUT/graph_n1.log" 2>&1 &&
         PSKV_BENCH_EMULATE=0/8 timeout -k 10 300 python3 "$R/tools/graph_probe.py" 10 > "$OUT/graph_r0of8.log" 2>&1 ;;
-    emuzipf) PSKV_BENCH_EMULATE=0/4 timeout -k 10 120 python3 "$R/bench.py" --steps 5 --warmup 2 --sets 4 --no-extra \
+    emuzipf) PSKV_BENCH_EMULATE=0/4 timeout -k 10 120 python3 "$R/bench.py" --full --steps 5 --warmup 2 --sets 4 --no-extra \
           --no-cpu-baseline > "$OUT/emuzipf4.json" 2> "$OUT/emuzipf4.err" &&
-        PSKV_BENCH_EMULATE=0/8 timeout -k 10 120 python3 "$R/bench.py" --steps 5 --warmup 2 --sets 4 --no-extra \
+        PSKV_BENCH_EMULATE=0/8 timeout -k 10 120 python3 "$R/bench.py" --full --steps 5 --warmup 2 --sets 4 --no-extra \
           --no-cpu-baseline > "$OUT/emuzipf8.json" 2> "$OUT/emuzipf8.err" ;;
     ranks8diag) PSKV_BENCH_BACKEND=gloo PSKV_BENCH_SHARE_GPU=1 timeout -k 10 170 python3 -m torch.distributed.run \
-          --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29611 "$R/bench.py" --gpus 8 --steps 5 \
+          --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29611 "$R/bench.py" --full --gpus 8 --steps 5 \
           --warmup 2 --sets 4 --no-zipf --no-extra > "$OUT/ranks8_nozipf.json" 2> "$OUT/ranks8_nozipf.err" &&
         PSKV_BENCH_BACKEND=gloo PSKV_BENCH_SHARE_GPU=1 timeout -k 10 170 python3 -m torch.distributed.run \
-          --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29612 "$R/bench.py" --gpus 8 --steps 5 \
+          --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29612 "$R/bench.py" --full --gpus 8 --steps 5 \
           --warmup 2 --sets 4 --no-extra > "$OUT/ranks8_zipf.json" 2> "$OUT/ranks8_zipf.err" ;;
     ranks8z) for r in 1 2 3 4 5 6 7; do
-          PSKV_BENCH_EMULATE=$r/8 PSKV_SYNC_TIMEOUT_MS=30000 timeout -k 10 90 python3 "$R/bench.py" --steps 3 \
+          PSKV_BENCH_EMULATE=$r/8 PSKV_SYNC_TIMEOUT_MS=30000 timeout -k 10 90 python3 "$R/bench.py" --full --steps 3 \
             --warmup 1 --sets 2 --no-extra --no-cpu-baseline --no-cold > "$OUT/emuz8_$r.json" 2> "$OUT/emuz8_$r.err" || exit 1
         done &&
         for q in ${RANKS8_QUEUES:-1 4}; do
           GPU_MAX_HW_QUEUES=$q PSKV_SYNC_TIMEOUT_MS=40000 PSKV_BENCH_WATCHDOG=30 PSKV_BENCH_BACKEND=gloo \
             PSKV_BENCH_SHARE_GPU=1 timeout -k 10 150 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 8 \
-            --master-addr 127.0.0.1 --master-port $((29620 + q)) "$R/bench.py" --gpus 8 --steps 3 --warmup 1 --sets 2 \
+            --master-addr 127.0.0.1 --master-port $((29620 + q)) "$R/bench.py" --full --gpus 8 --steps 3 --warmup 1 --sets 2 \
             --no-extra > "$OUT/ranks8_q$q.json" 2> "$OUT/ranks8_q$q.err" || exit 1
         done ;;
     ranks8q) for q in ${RANKS8_QUEUES:-4}; do
           GPU_MAX_HW_QUEUES=$q PSKV_SYNC_TIMEOUT_MS=40000 PSKV_BENCH_WATCHDOG=30 PSKV_BENCH_BACKEND=gloo \
             PSKV_BENCH_SHARE_GPU=1 timeout -k 10 ${RANKS8_LIMIT:-150} python3 -m torch.distributed.run --nnodes=1 \
             --nproc-per-node ${RANKS8_N:-8} --master-addr 127.0.0.1 --master-port $((29640 + q)) "$R/bench.py" \
-            --gpus ${RANKS8_N:-8} --steps 3 --warmup 1 --sets 2 --no-extra \
+            --full --gpus ${RANKS8_N:-8} --steps 3 --warmup 1 --sets 2 --no-extra \
             > "$OUT/ranks${RANKS8_N:-8}_q$q.json" 2> "$OUT/ranks${RANKS8_N:-8}_q$q.err" || exit 1
         done ;;
     ranks48) for n in 4 8; do
           PSKV_BENCH_BACKEND=gloo PSKV_BENCH_SHARE_GPU=1 timeout -k 10 500 python3 -m torch.distributed.run --nnodes=1 \
-            --nproc-per-node $n --master-addr 127.0.0.1 --master-port $((29600 + n)) "$R/bench.py" --gpus $n --steps 5 \
+            --nproc-per-node $n --master-addr 127.0.0.1 --master-port $((29600 + n)) "$R/bench.py" --full --gpus $n --steps 5 \
             --warmup 2 --sets 4 > "$OUT/ranks$n.json" 2> "$OUT/ranks$n.err" || exit 1
         done ;;
     wsweep) for sp in 1e8 1.25e8 5e8; do PROBE_SPACE=$sp PROBE_ROUNDS=10 timeout -k 10 300 python3 -u "$R/tools/zipf_probe.py" "" \
@@ -238,11 +239,11 @@ for step in "$@"; do
           PSKV_EARLY=$e timeout -k 10 200 python3 "$R/tools/size_probe.py" 2,4,8,16,64 > "$OUT/size_early${e}_$r.log" 2>&1 || exit 1
         done; done ;;
     emu_early) for r in 0 1; do for e in 0 2; do
-          PSKV_EARLY=$e PSKV_BENCH_EMULATE=$r/8 timeout -k 10 200 python3 "$R/bench.py" --steps 50 --no-zipf \
+          PSKV_EARLY=$e PSKV_BENCH_EMULATE=$r/8 timeout -k 10 200 python3 "$R/bench.py" --full --steps 50 --no-zipf \
             --no-cpu-baseline --no-extra > "$OUT/emu8_${r}_early$e.json" 2> "$OUT/emu8_${r}_early$e.err" || exit 1
         done; done ;;
     bench_early) for r in 1 2; do for e in 2 1; do
-          PSKV_EARLY=$e timeout -k 10 200 python3 "$R/bench.py" --steps 50 --no-zipf --no-cpu-baseline --no-extra \
+          PSKV_EARLY=$e timeout -k 10 200 python3 "$R/bench.py" --full --steps 50 --no-zipf --no-cpu-baseline --no-extra \
             > "$OUT/bench_early${e}_$r.json" 2> "$OUT/bench_early${e}_$r.err" || exit 1
         done; done ;;
     align_own) for r in 1 2; do for e in 0 3; do
@@ -258,20 +259,20 @@ for step in "$@"; do
           env $o timeout -k 10 300 python3 "$R/bench.py" --cold-only --steps 50 > "$OUT/cold$tag.json" 2> "$OUT/cold$tag.err" || exit 1
         done ;;
     ntp_ab) for r in 1 2; do for e in 0 1; do
-          PSKV_NTP=$e timeout -k 10 300 python3 "$R/bench.py" --steps 50 --no-zipf --no-extra \
+          PSKV_NTP=$e timeout -k 10 300 python3 "$R/bench.py" --full --steps 50 --no-zipf --no-extra \
             --no-cpu-baseline > "$OUT/ntp${e}_$r.json" 2> "$OUT/ntp${e}_$r.err" || exit 1
         done; done ;;
     emu_ntp) for r in 0 1 2 3 4 5 6 7; do for e in 0 1; do
-          PSKV_NTP=$e PSKV_BENCH_EMULATE=$r/8 timeout -k 10 200 python3 "$R/bench.py" --steps 50 --no-zipf \
+          PSKV_NTP=$e PSKV_BENCH_EMULATE=$r/8 timeout -k 10 200 python3 "$R/bench.py" --full --steps 50 --no-zipf \
             --no-cpu-baseline --no-extra > "$OUT/emu8_${r}_ntp$e.json" 2> "$OUT/emu8_${r}_ntp$e.err" || exit 1
         done; done ;;
     early_cold) for r in 1 2; do for e in 2 0; do
-          PSKV_EARLY=$e timeout -k 10 300 python3 "$R/bench.py" --steps 50 --no-zipf --no-extra --no-cpu-baseline \
+          PSKV_EARLY=$e timeout -k 10 300 python3 "$R/bench.py" --full --steps 50 --no-zipf --no-extra --no-cpu-baseline \
             > "$OUT/early${e}_$r.json" 2> "$OUT/early${e}_$r.err" || exit 1
         done; done ;;
     k2g_tune) for o in "" "PSKV_TILE_GRID=4096" "PSKV_UNROLL=4" "PSKV_TILE_GRID=8192"; do
           tag=$(echo "x$o" | tr ' =' '__')
-          env $o timeout -k 10 300 python3 "$R/bench.py" --steps 50 --no-zipf --no-extra --no-cpu-baseline \
+          env $o timeout -k 10 300 python3 "$R/bench.py" --full --steps 50 --no-zipf --no-extra --no-cpu-baseline \
             > "$OUT/tune$tag.json" 2> "$OUT/tune$tag.err" || exit 1
         done ;;
     smoke) timeout -k 10 300 python3 -c "import sys; sys.path.insert(0, '$R'); import __graft_entry__ as g; g.smoke()" \
@@ -279,9 +280,11 @@ for step in "$@"; do
     shardsize) timeout -k 10 400 python3 "$R/tools/shard_size_probe.py" > "$OUT/shard_size.log" 2>&1 &&
         FLUSH=1 timeout -k 10 400 python3 "$R/tools/shard_size_probe.py" > "$OUT/shard_size_flush.log" 2>&1 ;;
     e2e) timeout -k 10 200 python3 "$R/tools/e2e_probe.py" > "$OUT/e2e.log" 2>&1 ;;
-    benchdef) t0=$(date +%s); timeout -k 10 900 python3 "$R/bench.py" > "$OUT/benchdef.json" 2> "$OUT/benchdef.err" &&
-        echo "bench.py defaults: $(( $(date +%s) - t0 )) s" >> "$OUT/benchdef.err" ;;
+    benchdef) t0=$(date +%s); timeout -k 10 900 python3 "$R/bench.py" --full > "$OUT/benchdef.json" 2> "$OUT/benchdef.err" &&
+        echo "bench.py --full defaults: $(( $(date +%s) - t0 )) s" >> "$OUT/benchdef.err" ;;
     bench) timeout -k 10 400 python3 "$R/bench.py" --steps 20 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err" ;;
+    benchfull) timeout -k 10 600 python3 "$R/bench.py" --full --steps 20 --warmup 5 > "$OUT/benchfull.json" \
+        2> "$OUT/benchfull.err" ;;
     profile) bash "$R/tools/gpu_profile.sh" "$(basename "$OUT")/prof" > "$OUT/profile.log" 2>&1 ;;
     profile_cold) MODE=cold bash "$R/tools/gpu_profile.sh" "$(basename "$OUT")/prof_cold" > "$OUT/profile_cold.log" 2>&1 ;;
     zipf) timeout -k 10 300 python3 "$R/tools/zipf_probe.py" "" > "$OUT/zipf.log" 2>&1 ;;
