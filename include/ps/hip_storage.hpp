@@ -21,6 +21,10 @@
 // the message's SArrays and the pool holds them until the work has run), and
 // Get replies are frames the kernel writes directly.  Payloads outside frames
 // take the ordinary host paths.
+// Row-valued storage (width > 1, pskv_shard_create_rows): every key holds
+// `width` values; SubAdd takes keys.size() * width values (row-major), SubGet
+// replies with as many.  Such a storage holds only the keys of its range
+// (pskv.h), so construct it with the range the server owns.
 #pragma once
 
 #include <cstdint>
@@ -66,9 +70,10 @@ class HipStorage : public AbstractStorage {
  public:
   // No arguments = the reference's construction: whole key space, assign.
   explicit HipStorage(int device = 0, uint32_t key_begin = 0, uint64_t key_end = 1ull << 32,
-                      int mode = PSKV_ASSIGN, uint64_t overflow_slots = 0) {
-    pskv_check(pskv_shard_create_ex(device, key_begin, key_end, PskvDtype<Val>::value, mode,
-                                    overflow_slots, &shard_),
+                      int mode = PSKV_ASSIGN, uint64_t overflow_slots = 0, uint32_t width = 1)
+      : width_(width) {
+    pskv_check(pskv_shard_create_rows(device, key_begin, key_end, PskvDtype<Val>::value, mode, width,
+                                      overflow_slots, &shard_),
                "pskv_shard_create");
   }
   ~HipStorage() override { pskv_shard_destroy(shard_); }
@@ -78,9 +83,9 @@ class HipStorage : public AbstractStorage {
   void SubAdd(const third_party::SArray<Key>& typed_keys,
               const third_party::SArray<char>& vals) override {
     auto typed_vals = third_party::SArray<Val>(vals);
-    if (typed_keys.size() != typed_vals.size()) {
-      std::fprintf(stderr, "Check failed: typed_keys.size() == typed_vals.size() (%zu vs %zu)\n",
-                   (size_t)typed_keys.size(), (size_t)typed_vals.size());
+    if (typed_keys.size() * width_ != typed_vals.size()) {
+      std::fprintf(stderr, "Check failed: typed_keys.size() * width == typed_vals.size() (%zu * %u vs %zu)\n",
+                   (size_t)typed_keys.size(), (unsigned)width_, (size_t)typed_vals.size());
       std::abort();
     }
     pskv_check(pskv_add(shard_, typed_keys.data(), typed_vals.data(), typed_keys.size(),
@@ -102,8 +107,8 @@ class HipStorage : public AbstractStorage {
       }
       keep_k.emplace_back(m.data[0]);
       keep_v.emplace_back(m.data[1]);
-      if (keep_k.back().size() != keep_v.back().size()) {
-        std::fprintf(stderr, "Check failed: typed_keys.size() == typed_vals.size()\n");
+      if (keep_k.back().size() * width_ != keep_v.back().size()) {
+        std::fprintf(stderr, "Check failed: typed_keys.size() * width == typed_vals.size()\n");
         std::abort();
       }
       batches.push_back(pskv_batch{keep_k.back().data(), keep_v.back().data(), keep_k.back().size()});
@@ -116,7 +121,7 @@ class HipStorage : public AbstractStorage {
   third_party::SArray<char> SubGet(const third_party::SArray<Key>& typed_keys) override {
     // the reply is a page-locked frame: written in place by the kernel when the
     // request keys are a frame too, and sent zero-copy by the Sender
-    auto reply_vals = FrameArray<Val>(typed_keys.size());
+    auto reply_vals = FrameArray<Val>(typed_keys.size() * width_);
     pskv_check(pskv_get(shard_, typed_keys.data(), typed_keys.size(), reply_vals.data(),
                         PSKV_HOST | PSKV_HOST_FRAME),
                "pskv_get");
@@ -129,9 +134,11 @@ class HipStorage : public AbstractStorage {
   void FinishIter() override { pskv_check(pskv_sync(shard_), "pskv_sync"); }
 
   pskv_shard* shard() const { return shard_; }
+  uint32_t width() const { return width_; }
 
  private:
   pskv_shard* shard_ = nullptr;
+  uint32_t width_ = 1;
 };
 
 }  // namespace csci5570

@@ -43,13 +43,14 @@ using KeyRange = std::pair<uint64_t, uint64_t>;  // [begin, end), end <= 2^32
 template <typename Val>
 std::unique_ptr<AbstractStorage> MakeStorage(StorageType type, const KeyRange& r, size_t i,
                                              int mode = PSKV_ASSIGN,
-                                             const CpuStorageMaker& cpu = nullptr) {
+                                             const CpuStorageMaker& cpu = nullptr, uint32_t width = 1) {
   if (type == StorageType::Hip) {
     const int ndev = pskv_device_count();
     PS_CHECK(ndev > 0);
     return std::unique_ptr<AbstractStorage>(
-        new HipStorage<Val>((int)(i % (size_t)ndev), (uint32_t)r.first, r.second, mode));
+        new HipStorage<Val>((int)(i % (size_t)ndev), (uint32_t)r.first, r.second, mode, 0, width));
   }
+  PS_CHECK(width == 1);  // the CPU storages hold one value per key
 #ifdef PSKV_IN_REFERENCE_TREE
   if (type == StorageType::Map) return std::unique_ptr<AbstractStorage>(new MapStorage<Val>());
   return std::unique_ptr<AbstractStorage>(new VectorStorage<Val>());
@@ -74,18 +75,19 @@ inline std::unique_ptr<AbstractModel> MakeModel(ModelType type, uint32_t model_i
 
 // Engine::CreateTable for a group of server threads: threads[i] gets a storage
 // owning ranges[i] and a consistency model.  Returns the storages (still owned
-// by the models) in server order, for inspection.
+// by the models) in server order, for inspection.  width > 1: row-valued
+// storages (StorageType::Hip only), `width` values per key.
 template <typename Val>
 std::vector<AbstractStorage*> CreateTable(std::vector<std::unique_ptr<ServerThread>>& threads,
                                           const std::vector<KeyRange>& ranges, uint32_t model_id,
                                           ModelType model_type, StorageType storage_type,
                                           int staleness, ReplyQueue* replies,
                                           int mode = PSKV_ASSIGN,
-                                          const CpuStorageMaker& cpu = nullptr) {
+                                          const CpuStorageMaker& cpu = nullptr, uint32_t width = 1) {
   PS_CHECK(threads.size() == ranges.size());
   std::vector<AbstractStorage*> out;
   for (size_t i = 0; i < threads.size(); ++i) {
-    auto st = MakeStorage<Val>(storage_type, ranges[i], i, mode, cpu);
+    auto st = MakeStorage<Val>(storage_type, ranges[i], i, mode, cpu, width);
     out.push_back(st.get());
     threads[i]->RegisterModel(model_id, MakeModel(model_type, model_id, std::move(st), staleness, replies));
   }
@@ -99,12 +101,12 @@ std::vector<AbstractStorage*> CreateTable(std::vector<std::unique_ptr<ServerThre
                                           ModelType model_type, StorageType storage_type,
                                           int staleness, ReplyQueue* replies,
                                           int mode = PSKV_ASSIGN,
-                                          const CpuStorageMaker& cpu = nullptr) {
+                                          const CpuStorageMaker& cpu = nullptr, uint32_t width = 1) {
   PS_CHECK(threads.size() == map.GetNumServers());
   std::vector<KeyRange> ranges;
   for (size_t i = 0; i < threads.size(); ++i) ranges.push_back(map.GetRange(i));
   return CreateTable<Val>(threads, ranges, model_id, model_type, storage_type, staleness, replies, mode,
-                          cpu);
+                          cpu, width);
 }
 
 // Consistent hashing (the reference default, driver/engine.hpp:143-150): any
@@ -116,11 +118,11 @@ std::vector<AbstractStorage*> CreateTable(std::vector<std::unique_ptr<ServerThre
                                           uint32_t model_id, ModelType model_type,
                                           StorageType storage_type, int staleness, ReplyQueue* replies,
                                           int mode = PSKV_ASSIGN,
-                                          const CpuStorageMaker& cpu = nullptr) {
+                                          const CpuStorageMaker& cpu = nullptr, uint32_t width = 1) {
   PS_CHECK(threads.size() == map.GetNumServers());
   std::vector<KeyRange> ranges(threads.size(), KeyRange(0, key_end));
   return CreateTable<Val>(threads, ranges, model_id, model_type, storage_type, staleness, replies, mode,
-                          cpu);
+                          cpu, width);
 }
 
 }  // namespace csci5570

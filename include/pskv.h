@@ -43,6 +43,24 @@
  * PSKV_ESTATE -- only if a growth request is not answered within
  * SYNC_TIMEOUT_MS or its allocation fails (device memory exhausted).
  *
+ * Row-valued shards (pskv_shard_create_rows, width W > 1): every key holds a
+ * row of W values -- an embedding vector, a latent factor of the reference's
+ * matrix-factorisation app (app/mf.cpp:392-397 flattens such a row into W
+ * scalar keys for want of a row type).  Every call keeps its signature; n and
+ * pskv_batch.n count KEYS; vals and out hold n * W values, row i at element
+ * i * W (row-major), and so does the dense array.  PSKV_ASSIGN: the last
+ * occurrence of a key wins and the WHOLE row comes from it (a stored row is
+ * never a mix of two pushes); PSKV_ACCUMULATE: element-wise sums.  Column j of
+ * a row shard behaves exactly like a scalar shard fed (keys, vals[:, j]).
+ * PSKV_SORTED_HINT and the tuning options are accepted and change nothing;
+ * PSKV_HOST_FRAME buffers are treated as plain host memory.
+ * ONE LIMIT: a row shard stores no key outside [key_begin, key_end) (the
+ * overflow table holds one value per slot).  It refuses such keys loudly: a
+ * host Add that contains one returns PSKV_EINVAL naming the first and applies
+ * nothing; a device Add applies its in-range rows, drops the others, and the
+ * next pskv_sync returns PSKV_ESTATE ("row shard ... out-of-range"; pskv_clear
+ * resets it); a Get of such a key returns a row of zeros.
+ *
  * Threading: one shard handle is used by one host thread at a time (the
  * reference calls a storage only from its ServerThread, server_thread.cpp:20-50);
  * distinct handles may be used concurrently.  Every call selects the shard's
@@ -120,7 +138,7 @@ typedef struct pskv_info {
   int value_bytes;
   uint32_t key_begin;
   uint64_t key_end;          /* exclusive, may be 2^32 */
-  uint64_t dense_bytes;      /* HBM held by the dense parameter array */
+  uint64_t dense_bytes;      /* HBM held by the dense parameter array (keys * width * value_bytes) */
   uint64_t overflow_capacity;/* slots of the overflow hash table */
   uint64_t overflow_count;   /* keys stored in the overflow table (as of the last sync) */
   uint64_t n_add_calls;
@@ -142,7 +160,10 @@ enum pskv_kernel {
   PSKV_K_INLINE_ADD = 8,    /* K8: small host Add carried in the kernel arguments */
   PSKV_K_INLINE_GET = 9,    /* K8: small host Get, reply written to page-locked memory */
   PSKV_K_REPLAY = 10,       /* K4r: conditional replay behind a verifying sorted-path group */
-  PSKV_K_COUNT = 11
+  PSKV_K_ROW_GATHER = 11,   /* row shard Get */
+  PSKV_K_ROW_COMMIT = 12,   /* row shard assign Add: K4a stamps on the keys + whole-row winner copy */
+  PSKV_K_ROW_ACCUMULATE = 13, /* row shard accumulate Add: one atomic add per element */
+  PSKV_K_COUNT = 14
 };
 
 /* Create a shard owning keys [key_begin, key_end) on `device`.  The dense
@@ -154,6 +175,15 @@ int pskv_shard_create(int device, uint32_t key_begin, uint64_t key_end, int dtyp
  * up to a power of two; 0 = default). */
 int pskv_shard_create_ex(int device, uint32_t key_begin, uint64_t key_end, int dtype, int mode,
                          uint64_t overflow_slots, pskv_shard** out);
+#define PSKV_MAX_WIDTH 4096
+/* As pskv_shard_create_ex, with `width` values per key (a row).  width == 1 is
+ * exactly pskv_shard_create_ex.  width 0, width > PSKV_MAX_WIDTH or a dense
+ * array of more than 2^46 bytes is PSKV_EINVAL. */
+int pskv_shard_create_rows(int device, uint32_t key_begin, uint64_t key_end, int dtype, int mode,
+                           uint32_t width, uint64_t overflow_slots, pskv_shard** out);
+/* Values per key of this shard (1 for every shard made by the older
+ * constructors); 0 for a null shard. */
+uint32_t pskv_shard_width(pskv_shard* s);
 int pskv_shard_destroy(pskv_shard* s);
 
 /* Push: apply n (key, value) pairs.  Asynchronous on the shard's stream for

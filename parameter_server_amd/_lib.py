@@ -37,7 +37,11 @@ PSKV_K_ACC_DENSE = 7
 PSKV_K_INLINE_ADD = 8
 PSKV_K_INLINE_GET = 9
 PSKV_K_REPLAY = 10
-PSKV_K_COUNT = 11
+PSKV_K_ROW_GATHER = 11
+PSKV_K_ROW_COMMIT = 12
+PSKV_K_ROW_ACCUMULATE = 13
+PSKV_K_COUNT = 14
+PSKV_MAX_WIDTH = 4096
 KERNEL_NAMES = {
     PSKV_K_GATHER: "k_gather",
     PSKV_K_ASSIGN_SORTED: "k_assign_sorted",
@@ -50,6 +54,9 @@ KERNEL_NAMES = {
     PSKV_K_INLINE_ADD: "k_inline_add",
     PSKV_K_INLINE_GET: "k_inline_get",
     PSKV_K_REPLAY: "k_replay",
+    PSKV_K_ROW_GATHER: "k_row_gather",
+    PSKV_K_ROW_COMMIT: "k_row_commit",
+    PSKV_K_ROW_ACCUMULATE: "k_row_accumulate",
 }
 
 # Every symbol include/pskv.h declares (checked by tests/test_abi.py).
@@ -60,6 +67,7 @@ EXPORTED = [
     "pskv_kernel_time", "pskv_reset_timing", "pskv_range_slice", "pskv_jump_hash", "pskv_last_error",
     "pskv_abi_version", "pskv_device_count", "pskv_host_alloc", "pskv_host_free",
     "pskv_host_pool_stats", "pskv_host_pool_trim", "pskv_set_option", "pskv_get_option",
+    "pskv_shard_create_rows", "pskv_shard_width",
 ]
 
 
@@ -94,6 +102,8 @@ def _load():
     sig = {
         "pskv_shard_create": ([i32, u32, u64, i32, i32, ctypes.POINTER(vp)], i32),
         "pskv_shard_create_ex": ([i32, u32, u64, i32, i32, u64, ctypes.POINTER(vp)], i32),
+        "pskv_shard_create_rows": ([i32, u32, u64, i32, i32, u32, u64, ctypes.POINTER(vp)], i32),
+        "pskv_shard_width": ([vp], u32),
         "pskv_shard_destroy": ([vp], i32),
         "pskv_add": ([vp, vp, vp, u64, i32], i32),
         "pskv_get": ([vp, vp, u64, vp, i32], i32),

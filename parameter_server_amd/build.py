@@ -16,12 +16,13 @@ INCLUDE = os.path.join(ROOT, "include")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 
-LIB_SOURCES = ["pskv_kernels.hip", "pskv_shard.cpp", "pskv_frames.cpp"]
+LIB_SOURCES = ["pskv_kernels.hip", "pskv_rows.hip", "pskv_shard.cpp", "pskv_frames.cpp"]
 LIB_OUT = os.path.join(PKG, "libpskv.so")
 CPP_TESTS = {  # program -> (source in tests/cpp, links the oracle checker)
     "hip_storage_test": ("hip_storage_test.cpp", False),
     "ssp_replay": ("ssp_replay.cpp", True),
     "kv_client_table_test": ("kv_client_table_test.cpp", False),
+    "hip_storage_rows_test": ("hip_storage_rows_test.cpp", False),
 }
 ORACLE_DIR = os.path.join(ROOT, "oracle")
 BIN_DIR = os.path.join(PKG, "bin")

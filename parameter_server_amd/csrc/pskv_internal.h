@@ -41,6 +41,7 @@ constexpr uint32_t kEmpty32 = 0xFFFFFFFFu;
 
 // Error bits in ovf.stat[1].
 constexpr uint32_t kErrOverflowFull = 1u;
+constexpr uint32_t kErrRowOutOfRange = 2u;  // a row shard's device Add met a key outside its range (dropped)
 
 struct DevBatch {
   const uint32_t* keys;
@@ -238,5 +239,32 @@ hipError_t launch_dense_check(const GroupArgs& ga, uint32_t nchunks, const Dense
 // K7: accumulate dense windows (skips when flag == epoch); chunk as K6.
 hipError_t launch_acc_dense(int dtype, const GroupArgs& ga, uint32_t grid, const DenseView& d,
                             const uint32_t* flag, uint32_t epoch, hipStream_t st);
+
+
+// Row-valued shards (pskv_rows.hip): W values per key, row-major.  A row is
+// `units` units of `unit_bytes` (16, or the element size); a group of `lanes`
+// = min(64, next_pow2(units)) = 1 << lshift lanes owns one row at a time.
+struct RowShape {
+  uint32_t units;
+  uint32_t unit_bytes;
+  uint32_t lanes;
+  uint32_t lshift;
+};
+// unit16: the row size is a multiple of 16 bytes and every row pointer of the
+// launch is 16-byte aligned (the copy kernels); false: one element per unit.
+RowShape row_shape(uint32_t width, int vb, bool unit16);
+// `ga` chunked by kGeneralChunk keys; batch pointers step width * vb bytes per key.
+// Get: zeros for a key outside the range.
+hipError_t launch_row_gather(int vb, bool nt, const GroupArgs& ga, uint32_t nwg, const DenseView& d,
+                             const RowShape& rs, hipStream_t st);
+// Behind launch_general_mark (stamp mode) over the same `ga` and epoch: the
+// element whose tag equals its key's stamp copies its row.  Out-of-range keys
+// set kErrRowOutOfRange in o.c->stat[1].
+hipError_t launch_row_commit(int vb, const GroupArgs& ga, uint32_t nwg, const DenseView& d,
+                             const unsigned long long* owner, const Ovf& o, uint32_t epoch,
+                             const RowShape& rs, hipStream_t st);
+// One no-return atomic add per element (rs built with unit16 = false).
+hipError_t launch_row_accumulate(int dtype, const GroupArgs& ga, uint32_t nwg, const DenseView& d,
+                                 const Ovf& o, const RowShape& rs, hipStream_t st);
 
 }  // namespace pskv

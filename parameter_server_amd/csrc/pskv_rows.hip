@@ -1,0 +1,277 @@
+// pskv_rows.hip — CDNA4 (gfx950) kernels of row-valued shards: a fixed-width
+// vector of W values per key (DESIGN.md "Row-valued shards").
+//
+//   k_row_gather      Get: out[i] = row(keys[i]), zeros for a key outside the range
+//   k_row_commit      assign Add: the stamped winner of each key copies its whole row
+//   k_row_accumulate  accumulate Add: one no-return atomic add per element
+//
+// Lane mapping (all three).  A row is U units long (RowShape); a group of
+// L = min(64, next_pow2(U)) consecutive lanes owns one row at a time, lane l
+// of the group taking units l, l + L, ...  A wave therefore covers 64 / L
+// rows per instruction, each as one contiguous segment, and every lane of a
+// group reads the same key (one broadcast load).  The copy kernels take
+// 16-byte units when the row size and the pointers allow, else one element;
+// the accumulate always takes one element per lane, so that an atomic
+// wave-instruction covers contiguous bytes of each row (a lane holding four
+// consecutive elements would spread each instruction over 64 rows' worth of
+// 16-byte strides).  kRowsInFlight rows per group are loaded before the first
+// is stored.
+//
+// Work split: as K4 (pskv_kernels.hip): virtual workgroups of kGeneralChunk
+// keys of one batch (GroupArgs / build_group), grid-stride.  Within a chunk,
+// group g of the workgroup's G = kBlock / L groups takes the chunk's elements
+// g, g + G, ...; `li` below is the element's index inside the chunk, the same
+// number K4a folds into its stamps.
+#include "pskv_internal.h"
+
+namespace pskv {
+namespace {
+
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int kRowsInFlight = 4;
+static_assert(kGeneralChunk % (kRowsInFlight * kBlock) == 0, "every group's row index stays inside the chunk");
+
+// (the same search as pskv_kernels.hip's: the last batch whose first virtual
+// workgroup is at or before `wg`)
+__device__ __forceinline__ int row_batch_of(const GroupArgs& ga, uint32_t wg) {
+  int lo = 0, hi = ga.nb;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (ga.wg_prefix[mid] <= wg)
+      lo = mid;
+    else
+      hi = mid;
+  }
+  return lo;
+}
+
+// Group-wide index of batch j's first element: must equal K4a's elem_prefix,
+// or no element's tag would match its stamp.
+__device__ __forceinline__ uint64_t row_elem_prefix(const GroupArgs& ga, int j) {
+  uint64_t e = 0;
+  for (int i = 0; i < j; ++i) e += ga.b[i].n;
+  return e;
+}
+
+template <typename UT>
+__device__ __forceinline__ UT zero_unit() {
+  return UT(0);
+}
+template <>
+__device__ __forceinline__ u32x4 zero_unit<u32x4>() {
+  return u32x4{0u, 0u, 0u, 0u};
+}
+
+template <bool NT, typename UT>
+__device__ __forceinline__ void store_unit(UT* p, UT v) {
+  if (NT)
+    __builtin_nontemporal_store(v, p);
+  else
+    *p = v;
+}
+
+// The rows one lane group handles in one step: kRowsInFlight elements of the
+// chunk, G apart.  live: the element exists; in: its key is owned.
+struct RowStep {
+  uint64_t i[kRowsInFlight];    // element index in the batch
+  uint32_t off[kRowsInFlight];  // key - key_begin
+  bool live[kRowsInFlight];
+  bool in[kRowsInFlight];
+};
+
+__device__ __forceinline__ void load_step(RowStep& s, const uint32_t* __restrict__ keys, uint64_t n,
+                                          uint64_t base, uint32_t r0, uint32_t G, const DenseView& d) {
+#pragma unroll
+  for (int r = 0; r < kRowsInFlight; ++r) {
+    s.i[r] = base + r0 + (uint32_t)r * G;
+    s.live[r] = s.i[r] < n;
+    const uint32_t k = s.live[r] ? keys[s.i[r]] : 0u;
+    s.off[r] = k - d.key_begin;
+    s.in[r] = s.live[r] && (uint64_t)s.off[r] < d.range;
+  }
+}
+
+template <typename UT, bool NT>
+__global__ __launch_bounds__(kBlock) void k_row_gather(GroupArgs ga, DenseView d, RowShape rs) {
+  const uint32_t lane = threadIdx.x & (rs.lanes - 1u);
+  const uint32_t grp = threadIdx.x >> rs.lshift;
+  const uint32_t G = (uint32_t)kBlock >> rs.lshift;
+  const uint32_t U = rs.units;
+  const UT* __restrict__ param = reinterpret_cast<const UT*>(d.param);
+  const uint32_t nvwg = ga.wg_prefix[ga.nb];
+  for (uint32_t wg = blockIdx.x; wg < nvwg; wg += gridDim.x) {
+    const int j = row_batch_of(ga, wg);
+    const uint32_t* __restrict__ keys = ga.b[j].keys;
+    UT* __restrict__ out = reinterpret_cast<UT*>(const_cast<void*>(ga.b[j].vals));
+    const uint64_t n = ga.b[j].n;
+    const uint64_t base = (uint64_t)(wg - ga.wg_prefix[j]) * kGeneralChunk;
+    for (uint32_t r0 = grp; r0 < (uint32_t)kGeneralChunk; r0 += kRowsInFlight * G) {
+      if (base + r0 >= n) break;  // (r0 grows: the later rows of the step are past the end too)
+      RowStep s;
+      load_step(s, keys, n, base, r0, G, d);
+      for (uint32_t u = lane; u < U; u += rs.lanes) {
+        UT v[kRowsInFlight];
+#pragma unroll
+        for (int r = 0; r < kRowsInFlight; ++r)
+          v[r] = s.in[r] ? param[(uint64_t)s.off[r] * U + u] : zero_unit<UT>();
+#pragma unroll
+        for (int r = 0; r < kRowsInFlight; ++r)
+          if (s.live[r]) store_unit<NT>(out + s.i[r] * U + u, v[r]);
+      }
+    }
+  }
+}
+
+// `err`: the shard's sticky error word (OvfCtl::stat[1]).  A row whose key
+// lies outside the owned range is dropped, and one lane of its group sets
+// kErrRowOutOfRange there (pskv_sync reports it).
+template <typename UT>
+__global__ __launch_bounds__(kBlock) void k_row_commit(GroupArgs ga, DenseView d,
+                                                       const unsigned long long* __restrict__ owner,
+                                                       uint32_t* err, uint32_t epoch, RowShape rs) {
+  const uint32_t lane = threadIdx.x & (rs.lanes - 1u);
+  const uint32_t grp = threadIdx.x >> rs.lshift;
+  const uint32_t G = (uint32_t)kBlock >> rs.lshift;
+  const uint32_t U = rs.units;
+  UT* __restrict__ param = reinterpret_cast<UT*>(d.param);
+  const uint32_t nvwg = ga.wg_prefix[ga.nb];
+  for (uint32_t wg = blockIdx.x; wg < nvwg; wg += gridDim.x) {
+    const int j = row_batch_of(ga, wg);
+    const uint32_t* __restrict__ keys = ga.b[j].keys;
+    const UT* __restrict__ vals = reinterpret_cast<const UT*>(ga.b[j].vals);
+    const uint64_t n = ga.b[j].n;
+    const uint64_t base = (uint64_t)(wg - ga.wg_prefix[j]) * kGeneralChunk;
+    const uint64_t gbase = row_elem_prefix(ga, j) + base;
+    for (uint32_t r0 = grp; r0 < (uint32_t)kGeneralChunk; r0 += kRowsInFlight * G) {
+      if (base + r0 >= n) break;
+      RowStep s;
+      load_step(s, keys, n, base, r0, G, d);
+      bool win[kRowsInFlight];
+#pragma unroll
+      for (int r = 0; r < kRowsInFlight; ++r) {
+        // the tag K4a stamped for this element: epoch<<32 | (group index of the element)
+        const unsigned long long tag =
+            ((unsigned long long)epoch << 32) | (gbase + r0 + (uint32_t)r * G);
+        win[r] = s.in[r] && owner[s.off[r]] == tag;
+        if (s.live[r] && !s.in[r] && lane == 0) atomicOr(err, kErrRowOutOfRange);
+      }
+      for (uint32_t u = lane; u < U; u += rs.lanes) {
+        UT v[kRowsInFlight];
+#pragma unroll
+        for (int r = 0; r < kRowsInFlight; ++r)
+          v[r] = win[r] ? vals[s.i[r] * U + u] : zero_unit<UT>();
+#pragma unroll
+        for (int r = 0; r < kRowsInFlight; ++r)
+          if (win[r]) param[(uint64_t)s.off[r] * U + u] = v[r];
+      }
+    }
+  }
+}
+
+// One element per lane (rs.units = the width).  The adds are no-return device
+// atomics: any order, so float sums meet the recursive-summation bound.
+template <typename AT>
+__global__ __launch_bounds__(kBlock) void k_row_accumulate(GroupArgs ga, DenseView d, uint32_t* err,
+                                                           RowShape rs) {
+  const uint32_t lane = threadIdx.x & (rs.lanes - 1u);
+  const uint32_t grp = threadIdx.x >> rs.lshift;
+  const uint32_t G = (uint32_t)kBlock >> rs.lshift;
+  const uint32_t U = rs.units;
+  AT* __restrict__ param = reinterpret_cast<AT*>(d.param);
+  const uint32_t nvwg = ga.wg_prefix[ga.nb];
+  for (uint32_t wg = blockIdx.x; wg < nvwg; wg += gridDim.x) {
+    const int j = row_batch_of(ga, wg);
+    const uint32_t* __restrict__ keys = ga.b[j].keys;
+    const AT* __restrict__ vals = reinterpret_cast<const AT*>(ga.b[j].vals);
+    const uint64_t n = ga.b[j].n;
+    const uint64_t base = (uint64_t)(wg - ga.wg_prefix[j]) * kGeneralChunk;
+    for (uint32_t r0 = grp; r0 < (uint32_t)kGeneralChunk; r0 += kRowsInFlight * G) {
+      if (base + r0 >= n) break;
+      RowStep s;
+      load_step(s, keys, n, base, r0, G, d);
+#pragma unroll
+      for (int r = 0; r < kRowsInFlight; ++r)
+        if (s.live[r] && !s.in[r] && lane == 0) atomicOr(err, kErrRowOutOfRange);
+      for (uint32_t u = lane; u < U; u += rs.lanes) {
+        AT v[kRowsInFlight];
+#pragma unroll
+        for (int r = 0; r < kRowsInFlight; ++r) v[r] = s.in[r] ? vals[s.i[r] * U + u] : AT(0);
+#pragma unroll
+        for (int r = 0; r < kRowsInFlight; ++r)
+          if (s.in[r]) (void)atomicAdd(param + (uint64_t)s.off[r] * U + u, v[r]);
+      }
+    }
+  }
+}
+
+uint32_t row_grid(uint32_t nwg) { return nwg < 4096u ? nwg : 4096u; }
+
+}  // namespace
+
+RowShape row_shape(uint32_t width, int vb, bool unit16) {
+  RowShape rs;
+  rs.unit_bytes = unit16 ? 16u : (uint32_t)vb;
+  rs.units = (uint32_t)((uint64_t)width * (uint32_t)vb / rs.unit_bytes);
+  rs.lanes = 1;
+  rs.lshift = 0;
+  while (rs.lanes < 64u && rs.lanes < rs.units) {
+    rs.lanes <<= 1;
+    ++rs.lshift;
+  }
+  return rs;
+}
+
+hipError_t launch_row_gather(int vb, bool nt, const GroupArgs& ga, uint32_t nwg, const DenseView& d,
+                             const RowShape& rs, hipStream_t st) {
+  if (nwg == 0) return hipSuccess;
+  const uint32_t grid = row_grid(nwg);
+  if (rs.unit_bytes == 16) {
+    if (nt)
+      k_row_gather<u32x4, true><<<grid, kBlock, 0, st>>>(ga, d, rs);
+    else
+      k_row_gather<u32x4, false><<<grid, kBlock, 0, st>>>(ga, d, rs);
+  } else if (vb == 4) {
+    if (nt)
+      k_row_gather<uint32_t, true><<<grid, kBlock, 0, st>>>(ga, d, rs);
+    else
+      k_row_gather<uint32_t, false><<<grid, kBlock, 0, st>>>(ga, d, rs);
+  } else {
+    if (nt)
+      k_row_gather<unsigned long long, true><<<grid, kBlock, 0, st>>>(ga, d, rs);
+    else
+      k_row_gather<unsigned long long, false><<<grid, kBlock, 0, st>>>(ga, d, rs);
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_row_commit(int vb, const GroupArgs& ga, uint32_t nwg, const DenseView& d,
+                             const unsigned long long* owner, const Ovf& o, uint32_t epoch,
+                             const RowShape& rs, hipStream_t st) {
+  if (nwg == 0) return hipSuccess;
+  const uint32_t grid = row_grid(nwg);
+  uint32_t* err = &o.c->stat[1];
+  if (rs.unit_bytes == 16)
+    k_row_commit<u32x4><<<grid, kBlock, 0, st>>>(ga, d, owner, err, epoch, rs);
+  else if (vb == 4)
+    k_row_commit<uint32_t><<<grid, kBlock, 0, st>>>(ga, d, owner, err, epoch, rs);
+  else
+    k_row_commit<unsigned long long><<<grid, kBlock, 0, st>>>(ga, d, owner, err, epoch, rs);
+  return hipGetLastError();
+}
+
+hipError_t launch_row_accumulate(int dtype, const GroupArgs& ga, uint32_t nwg, const DenseView& d,
+                                 const Ovf& o, const RowShape& rs, hipStream_t st) {
+  if (nwg == 0) return hipSuccess;
+  const uint32_t grid = row_grid(nwg);
+  uint32_t* err = &o.c->stat[1];
+  if (dtype == 0)
+    k_row_accumulate<int><<<grid, kBlock, 0, st>>>(ga, d, err, rs);
+  else if (dtype == 1)
+    k_row_accumulate<float><<<grid, kBlock, 0, st>>>(ga, d, err, rs);
+  else
+    k_row_accumulate<double><<<grid, kBlock, 0, st>>>(ga, d, err, rs);
+  return hipGetLastError();
+}
+
+}  // namespace pskv

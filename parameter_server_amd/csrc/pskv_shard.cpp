@@ -213,6 +213,7 @@ struct pskv_shard {
   int dtype = PSKV_F32;
   int mode = PSKV_ASSIGN;
   int vb = 4;
+  uint32_t width = 1;  // values per key; > 1: a row shard (the rows_* paths below, pskv_rows.hip)
   uint32_t key_begin = 0;
   uint64_t range = 0;
   void* dense = nullptr;
@@ -432,7 +433,8 @@ const char* const kKernelNames[PSKV_K_COUNT] = {
     "k_gather (K1 Get)",          "k_assign_sorted (K2)",          "k_assign_group (K2g)",
     "k_general_mark (K4a)",       "k_general_commit (K4b)",        "k_rb_bin + k_rb_resolve (K5 Add)",
     "k_dense_check (K6)",         "k_acc_dense (K7)",              "k_inline_add (K8)",
-    "k_inline_get (K8)",          "k_replay (K4r)"};
+    "k_inline_get (K8)",          "k_replay (K4r)",                "k_row_gather (row Get)",
+    "k_general_mark + k_row_commit (row assign Add)",              "k_row_accumulate (row accumulate Add)"};
 
 std::string wait_report(const pskv_shard* s, const char* what, const void* handle, double ms) {
   char buf[384];
@@ -1677,7 +1679,186 @@ int inline_get(pskv_shard* s, const std::vector<pskv_batch>& v, uint64_t total) 
   return PSKV_OK;
 }
 
+// ------------------------------------------------------------- row shards
+// A shard of width W > 1 (pskv_shard_create_rows): W values per key, row-major
+// in the batches and in the dense array.  It takes none of the scalar paths
+// above: add_impl / get_impl / add_get_impl dispatch here at their top.
+//   Get         k_row_gather
+//   assign Add  K4a (k_general_mark, stamp mode, unchanged: it reads keys only)
+//               then k_row_commit: the element whose tag equals its key's stamp
+//               copies its whole row; timed together as PSKV_K_ROW_COMMIT
+//   accumulate  k_row_accumulate
+// Host buffers are staged through the pinned and device staging buffers (keys
+// then rows per batch, 16-byte aligned).  Keys outside the owned range are
+// not stored (pskv.h): a host Add refuses them before anything is queued, the
+// kernels drop them and set kErrRowOutOfRange.
+size_t row_bytes(const pskv_shard* s) { return (size_t)s->width * (size_t)s->vb; }
+
+int rows_pieces(pskv_shard* s, const std::vector<pskv_batch>& in, const char* what, std::vector<pskv_batch>* v) {
+  for (auto& b : in) {
+    if (b.n == 0) continue;
+    if (!b.keys || !b.vals) return fail(PSKV_EINVAL, std::string(what) + ": null keys/vals with n > 0");
+    push_pieces(*v, b, row_bytes(s));
+  }
+  return PSKV_OK;
+}
+
+// Host batches -> device staging through pinned staging: keys (and, for an
+// Add, rows) copied in and queued for DMA; a Get's rows get room behind them.
+// `dv`: the device views.  The pinned copy of batch i's rows lies at
+// hstage + (dv[i].vals - dstage).
+int rows_stage(pskv_shard* s, const std::vector<pskv_batch>& v, bool with_rows, std::vector<pskv_batch>* dv,
+               size_t* in_bytes, size_t* total_bytes) {
+  const size_t rb = row_bytes(s);
+  size_t kbytes = 0, vbytes = 0;
+  for (auto& b : v) {
+    kbytes += round16(b.n * 4);
+    vbytes += round16(b.n * rb);
+  }
+  int rc = ensure_hstage(s, kbytes + vbytes);
+  if (rc) return rc;
+  rc = ensure_dstage(s, kbytes + vbytes);
+  if (rc) return rc;
+  char* h = static_cast<char*>(s->hstage);
+  char* d = static_cast<char*>(s->dstage);
+  std::vector<Piece> pieces;
+  *dv = v;
+  size_t off = 0;
+  for (size_t i = 0; i < v.size(); ++i) {
+    add_pieces(pieces, v[i].keys, h + off, v[i].n * 4, -1);
+    (*dv)[i].keys = reinterpret_cast<const uint32_t*>(d + off);
+    off += round16(v[i].n * 4);
+  }
+  for (size_t i = 0; i < v.size(); ++i) {
+    if (with_rows) add_pieces(pieces, v[i].vals, h + off, v[i].n * rb, -1);
+    (*dv)[i].vals = d + off;
+    off += round16(v[i].n * rb);
+  }
+  *in_bytes = with_rows ? off : kbytes;
+  *total_bytes = off;
+  return pipelined_h2d(s, pieces, h, d);
+}
+
+int rows_add_device(pskv_shard* s, const std::vector<pskv_batch>& v) {
+  bool vec = row_bytes(s) % 16 == 0 && aligned16(s->dense);
+  for (auto& b : v) vec = vec && aligned16(b.vals);
+  for (auto& g : split_groups(v)) {
+    GroupArgs ga;
+    const uint32_t nwg = build_group(v, g.first, g.second, kGeneralChunk, &ga);
+    uint64_t elems = 0;
+    for (size_t i = g.first; i < g.second; ++i) elems += v[i].n;
+    if (s->mode == PSKV_ACCUMULATE) {
+      LaunchTimer t(s, PSKV_K_ROW_ACCUMULATE, elems);
+      PSKV_HIP(launch_row_accumulate(s->dtype, ga, nwg, s->dview(), s->ovf, row_shape(s->width, s->vb, false),
+                                     s->stream));
+      t.done();
+      s->n_general++;
+      continue;
+    }
+    if (!s->owner) {  // 8 B per owned KEY (not per value), on first use
+      const size_t bytes = s->range * sizeof(unsigned long long);
+      if (hipMalloc(&s->owner, bytes) != hipSuccess) {
+        s->owner = nullptr;
+        return fail(PSKV_ENOMEM, "stamp array allocation failed");
+      }
+      PSKV_HIP(hipMemsetAsync(s->owner, 0, bytes, s->stream));
+    }
+    const uint32_t epoch = next_epoch(s);
+    LaunchTimer t(s, PSKV_K_ROW_COMMIT, elems);
+    PSKV_HIP(launch_general_mark(s->dtype, PSKV_ASSIGN, ga, nwg, s->dview(), s->flag + 1, s->owner, nullptr, epoch,
+                                 s->stream));
+    PSKV_HIP(launch_row_commit(s->vb, ga, nwg, s->dview(), s->owner, s->ovf, epoch,
+                               row_shape(s->width, s->vb, vec), s->stream));
+    t.done();
+    s->n_general += 2;
+  }
+  return PSKV_OK;
+}
+
+int rows_add(pskv_shard* s, const std::vector<pskv_batch>& in, int flags) {
+  std::vector<pskv_batch> v;
+  if (int rc = rows_pieces(s, in, "pskv_add", &v)) return rc;
+  s->n_add++;
+  if (v.empty()) return PSKV_OK;
+  int rc = use_device(s);
+  if (rc) return rc;
+  if (flags & PSKV_DEVICE) return rows_add_device(s, v);
+  // the keys are checked before anything is queued: nothing is applied
+  for (const auto& b : v) {
+    Piece p{};
+    check_keys(p, b.keys, b.n, s->key_begin, s->range);
+    if (!p.outside) continue;
+    for (uint64_t i = 0; i < b.n; ++i)
+      if ((uint64_t)(uint32_t)(b.keys[i] - s->key_begin) >= s->range)
+        return fail(PSKV_EINVAL, "pskv_add: row shard: key " + std::to_string(b.keys[i]) +
+                                     " is outside [key_begin, key_end); a row shard stores no out-of-range "
+                                     "keys (nothing was applied)");
+  }
+  std::vector<pskv_batch> dv;
+  size_t in_bytes = 0, total = 0;
+  rc = rows_stage(s, v, /*with_rows=*/true, &dv, &in_bytes, &total);
+  if (!rc) rc = rows_add_device(s, dv);
+  hold_hstage(s);  // until the queued H2D copies have read the staging
+  return rc;
+}
+
+int rows_get(pskv_shard* s, const std::vector<pskv_batch>& in, int flags) {
+  std::vector<pskv_batch> v;
+  if (int rc = rows_pieces(s, in, "pskv_get", &v)) return rc;
+  s->n_get++;
+  if (v.empty()) return PSKV_OK;
+  int rc = use_device(s);
+  if (rc) return rc;
+  const bool device = (flags & PSKV_DEVICE) != 0;
+  std::vector<pskv_batch> dv = v;
+  size_t in_bytes = 0, total = 0;
+  if (!device) {
+    rc = rows_stage(s, v, /*with_rows=*/false, &dv, &in_bytes, &total);
+    if (rc) {
+      hold_hstage(s);
+      return rc;
+    }
+  }
+  bool vec = row_bytes(s) % 16 == 0 && aligned16(s->dense);
+  for (auto& b : dv) vec = vec && aligned16(b.vals);
+  const RowShape rs = row_shape(s->width, s->vb, vec);
+  for (auto& g : split_groups(dv)) {
+    GroupArgs ga;
+    const uint32_t nwg = build_group(dv, g.first, g.second, kGeneralChunk, &ga);
+    uint64_t elems = 0;
+    for (size_t i = g.first; i < g.second; ++i) elems += dv[i].n;
+    LaunchTimer t(s, PSKV_K_ROW_GATHER, elems);
+    const hipError_t e = launch_row_gather(s->vb, s->tune_nt, ga, nwg, s->dview(), rs, s->stream);
+    if (e != hipSuccess) {
+      if (!device) hold_hstage(s);
+      PSKV_HIP(e);
+    }
+    t.done();
+  }
+  if (device) return PSKV_OK;
+  // rows: device staging -> pinned staging -> the caller's buffers
+  char* h = static_cast<char*>(s->hstage);
+  char* d = static_cast<char*>(s->dstage);
+  const hipError_t e =
+      hipMemcpyAsync(h + in_bytes, d + in_bytes, total - in_bytes, hipMemcpyDeviceToHost, s->stream);
+  if (e != hipSuccess) {
+    hold_hstage(s);
+    PSKV_HIP(e);
+  }
+  if (int rc2 = wait_stream(s, s->stream, "shard stream (row Get to host)")) {
+    hold_hstage(s);
+    return rc2;
+  }
+  std::vector<Piece> pieces;
+  for (size_t i = 0; i < v.size(); ++i)
+    add_pieces(pieces, h + (static_cast<const char*>(dv[i].vals) - d), static_cast<char*>(v[i].vals),
+               v[i].n * row_bytes(s), -1);
+  run_pieces(pieces, 0, pieces.size(), [&](Piece& p) { copy_piece(p, s->key_begin, s->range); });
+  return PSKV_OK;
+}
+
 int add_impl(pskv_shard* s, const std::vector<pskv_batch>& in, int flags) {
+  if (s->width > 1) return rows_add(s, in, flags);
   std::vector<pskv_batch> v;
   for (auto& b : in) {
     if (b.n == 0) continue;
@@ -1904,6 +2085,7 @@ int pinned_get(pskv_shard* s, const std::vector<pskv_batch>& v) {
 }
 
 int get_impl(pskv_shard* s, const std::vector<pskv_batch>& in, int flags) {
+  if (s->width > 1) return rows_get(s, in, flags);
   std::vector<pskv_batch> v;
   for (auto& b : in) {
     if (b.n == 0) continue;
@@ -2068,6 +2250,10 @@ int get_impl(pskv_shard* s, const std::vector<pskv_batch>& in, int flags) {
 // kernel was removed; the call stays, as the two paths.
 int add_get_impl(pskv_shard* s, const std::vector<pskv_batch>& adds, const std::vector<pskv_batch>& gets,
                  int flags) {
+  if (s->width > 1) {
+    const int rc = rows_add(s, adds, flags);
+    return rc ? rc : rows_get(s, gets, flags);
+  }
   // Device batches, assign, 4-byte values: the Add's last conditional replay
   // is held and rides on the Get's first K1 launch (K1r) -- one launch fewer
   // per call.  The Get's device path queues nothing before that K1; whatever
@@ -2232,8 +2418,8 @@ int pskv_device_count(void) {
   return n;
 }
 
-int pskv_shard_create_ex(int device, uint32_t key_begin, uint64_t key_end, int dtype, int mode,
-                         uint64_t overflow_slots, pskv_shard** out) {
+int pskv_shard_create_rows(int device, uint32_t key_begin, uint64_t key_end, int dtype, int mode,
+                           uint32_t width, uint64_t overflow_slots, pskv_shard** out) {
   if (!out) return fail(PSKV_EINVAL, "pskv_shard_create: out is null");
   *out = nullptr;
   const int vb = value_bytes(dtype);
@@ -2242,6 +2428,10 @@ int pskv_shard_create_ex(int device, uint32_t key_begin, uint64_t key_end, int d
     return fail(PSKV_EINVAL, "pskv_shard_create: bad mode");
   if (key_end <= (uint64_t)key_begin || key_end > (1ull << 32))
     return fail(PSKV_EINVAL, "pskv_shard_create: need key_begin < key_end <= 2^32");
+  if (width == 0 || width > PSKV_MAX_WIDTH)
+    return fail(PSKV_EINVAL, "pskv_shard_create_rows: width must be 1.." + std::to_string(PSKV_MAX_WIDTH));
+  if ((key_end - key_begin) * (uint64_t)width * (uint64_t)vb > (1ull << 46))
+    return fail(PSKV_EINVAL, "pskv_shard_create_rows: keys * width * value bytes exceeds 2^46 bytes");
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
     return fail(PSKV_EINVAL, "pskv_shard_create: no such HIP device");
@@ -2250,6 +2440,7 @@ int pskv_shard_create_ex(int device, uint32_t key_begin, uint64_t key_end, int d
   s->dtype = dtype;
   s->mode = mode;
   s->vb = vb;
+  s->width = width;
   s->key_begin = key_begin;
   s->range = key_end - key_begin;
   // tuning / path options: creation defaults from the environment (PSKV_<NAME>),
@@ -2273,9 +2464,9 @@ int pskv_shard_create_ex(int device, uint32_t key_begin, uint64_t key_end, int d
       hipEventCreateWithFlags(&s->h2d_done, hipEventDisableTiming | hipEventDisableSystemFence) !=
           hipSuccess)
     return bail(fail(PSKV_EHIP, "hipEventCreate failed"));
-  if (hipMalloc(&s->dense, s->range * (size_t)vb) != hipSuccess)
+  if (hipMalloc(&s->dense, s->range * (size_t)width * (size_t)vb) != hipSuccess)
     return bail(fail(PSKV_ENOMEM, "dense parameter allocation failed"));
-  if (hipMemsetAsync(s->dense, 0, s->range * (size_t)vb, s->stream) != hipSuccess)
+  if (hipMemsetAsync(s->dense, 0, s->range * (size_t)width * (size_t)vb, s->stream) != hipSuccess)
     return bail(fail(PSKV_EHIP, "hipMemsetAsync failed"));
   // flag[0]: the sorted path's verification tag
   // the verification tag (16 bytes), then K1r's replay table (add_get's folded replay)
@@ -2310,6 +2501,13 @@ int pskv_shard_create_ex(int device, uint32_t key_begin, uint64_t key_end, int d
   *out = s;
   return PSKV_OK;
 }
+
+int pskv_shard_create_ex(int device, uint32_t key_begin, uint64_t key_end, int dtype, int mode,
+                         uint64_t overflow_slots, pskv_shard** out) {
+  return pskv_shard_create_rows(device, key_begin, key_end, dtype, mode, 1, overflow_slots, out);
+}
+
+uint32_t pskv_shard_width(pskv_shard* s) { return s ? s->width : 0u; }
 
 int pskv_shard_create(int device, uint32_t key_begin, uint64_t key_end, int dtype, int mode,
                       pskv_shard** out) {
@@ -2440,6 +2638,10 @@ int pskv_sync(pskv_shard* s) {
     return fail(PSKV_ESTATE,
                 "overflow table exhausted: out-of-range keys were dropped (the device-side growth "
                 "request was not answered within SYNC_TIMEOUT_MS, or its allocation failed)");
+  if (err & kErrRowOutOfRange)
+    return fail(PSKV_ESTATE,
+                "row shard: a device Add held out-of-range keys; their rows were dropped (a row shard stores "
+                "no key outside [key_begin, key_end); pskv_clear resets this)");
   if (2 * (uint64_t)cnt > s->ocap) return grow_overflow(s, cnt);
   return PSKV_OK;
 }
@@ -2451,7 +2653,7 @@ int pskv_clear(pskv_shard* s) {
   uint32_t cnt = 0, err = 0;
   rc = read_overflow_stat(s, &cnt, &err);  // (adopts the current table; stops the server)
   if (rc) return rc;
-  PSKV_HIP(hipMemsetAsync(s->dense, 0, s->range * (size_t)s->vb, s->stream));
+  PSKV_HIP(hipMemsetAsync(s->dense, 0, s->range * (size_t)s->width * (size_t)s->vb, s->stream));
   PSKV_HIP(hipMemsetAsync(s->cur.keys, 0xFF, s->ocap * sizeof(unsigned long long), s->stream));
   PSKV_HIP(hipMemsetAsync(s->cur.vals, 0, s->ocap * (size_t)s->vb, s->stream));
   PSKV_HIP(hipMemsetAsync(s->ovf.c->stat, 0, 2 * sizeof(uint32_t), s->stream));
@@ -2484,7 +2686,7 @@ int pskv_shard_info(pskv_shard* s, pskv_info* info) {
   info->value_bytes = s->vb;
   info->key_begin = s->key_begin;
   info->key_end = (uint64_t)s->key_begin + s->range;
-  info->dense_bytes = s->range * (uint64_t)s->vb;
+  info->dense_bytes = s->range * (uint64_t)s->width * (uint64_t)s->vb;
   info->overflow_capacity = s->ocap;
   info->overflow_count = s->ocount_known;
   info->n_add_calls = s->n_add;

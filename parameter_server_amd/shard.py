@@ -42,17 +42,26 @@ class Shard:
     """A key range [key_begin, key_end) of uint32 keys held in HBM.
 
     mode "assign" is the reference semantics (last write wins, missing -> 0);
-    "accumulate" is the gradient-reduction mode (param[k] += v)."""
+    "accumulate" is the gradient-reduction mode (param[k] += v).
+
+    width > 1 makes a row shard: every key holds `width` values (an embedding
+    row).  add takes values shaped (n, width) or flat n * width, get returns
+    (n, width); counts stay in keys.  A row shard stores no key outside its
+    range (include/pskv.h: the one limit)."""
 
     def __init__(self, key_begin: int = 0, key_end: int = 1 << 32, dtype=np.float32,
-                 mode: str = "assign", device: int = 0, overflow_slots: int = 0, options=None):
+                 mode: str = "assign", device: int = 0, overflow_slots: int = 0, options=None,
+                 width: int = 1):
         self.dtype = np.dtype(dtype) if not _is_torch(dtype) else _NP_DTYPE[dtype_code(dtype)]
         self.code = dtype_code(self.dtype)
         self.mode = {"assign": _lib.PSKV_ASSIGN, "accumulate": _lib.PSKV_ACCUMULATE}[mode]
         self.key_begin, self.key_end, self.device = int(key_begin), int(key_end), int(device)
+        self.width = int(width)
+        if not 0 <= self.width < 1 << 32:
+            raise ValueError(f"width {width} out of range")
         h = ctypes.c_void_p()
-        check(lib.pskv_shard_create_ex(self.device, self.key_begin, self.key_end, self.code,
-                                       self.mode, int(overflow_slots), ctypes.byref(h)))
+        check(lib.pskv_shard_create_rows(self.device, self.key_begin, self.key_end, self.code,
+                                         self.mode, self.width, int(overflow_slots), ctypes.byref(h)))
         self._h = h
         for name, value in (options or {}).items():
             self.set_option(name, value)
@@ -85,9 +94,18 @@ class Shard:
 
     def _host_vals(self, vals, n):
         v = np.ascontiguousarray(vals, dtype=self.dtype)
-        if v.size != n:
+        if v.size != n * self.width:
+            if self.width > 1:
+                raise ValueError(f"CHECK_EQ(keys.size() * width, vals.size()) failed: {n} * {self.width} vs {v.size}")
             raise ValueError(f"CHECK_EQ(keys.size(), vals.size()) failed: {n} vs {v.size}")
         return v
+
+    def _check_dev_count(self, keys, vals):
+        if vals.numel() != keys.numel() * self.width:
+            if self.width > 1:
+                raise ValueError(f"CHECK_EQ(keys.size() * width, vals.size()) failed: "
+                                 f"{keys.numel()} * {self.width} vs {vals.numel()}")
+            raise ValueError("CHECK_EQ(keys.size(), vals.size()) failed")
 
     # ------------------------------------------------------------ Add / Get
     def add(self, keys, vals, sorted_hint: bool = False, frame: bool = False):
@@ -97,8 +115,7 @@ class Shard:
         if _is_torch(keys):
             self._check_dev(keys, vals)
             flags = _lib.PSKV_DEVICE | (_lib.PSKV_SORTED_HINT if sorted_hint else 0)
-            if vals.numel() != keys.numel():
-                raise ValueError("CHECK_EQ(keys.size(), vals.size()) failed")
+            self._check_dev_count(keys, vals)
             check(lib.pskv_add(self._h, keys.data_ptr(), vals.data_ptr(), keys.numel(), flags))
             return
         k = self._host_keys(keys)
@@ -113,12 +130,21 @@ class Shard:
             import torch
 
             if out is None:
-                out = torch.empty(keys.numel(), dtype=_torch_dtype(self.dtype), device=keys.device)
+                shape = (keys.numel(), self.width) if self.width > 1 else keys.numel()
+                out = torch.empty(shape, dtype=_torch_dtype(self.dtype), device=keys.device)
             self._check_dev(keys, out)
+            if self.width > 1:
+                self._check_dev_count(keys, out)
             check(lib.pskv_get(self._h, keys.data_ptr(), keys.numel(), out.data_ptr(),
                                _lib.PSKV_DEVICE))
             return out
         k = self._host_keys(keys)
+        if self.width > 1:
+            if out is None:
+                out = np.empty((k.size, self.width), dtype=self.dtype)
+            elif not (isinstance(out, np.ndarray) and out.dtype == self.dtype and out.flags.c_contiguous
+                      and out.size == k.size * self.width):
+                raise ValueError("row shard: out must be a C-contiguous array of keys * width values")
         res = np.empty(k.size, dtype=self.dtype) if out is None else out
         flags = _lib.PSKV_HOST_FRAME if frame else _lib.PSKV_HOST
         check(lib.pskv_get(self._h, k.ctypes.data, k.size, res.ctypes.data, flags))
@@ -173,8 +199,7 @@ class Shard:
                 raise ValueError("mixed host/device batches in one grouped call")
             if t:
                 self._check_dev(k, v)
-                if v.numel() != k.numel():
-                    raise ValueError("CHECK_EQ(keys.size(), vals.size()) failed")
+                self._check_dev_count(k, v)
                 keep += [k, v]
                 arr[i] = _lib.PskvBatch(k.data_ptr(), v.data_ptr(), k.numel())
             else:
@@ -182,6 +207,8 @@ class Shard:
                 if is_get:
                     if not (isinstance(v, np.ndarray) and v.dtype == self.dtype and v.flags.c_contiguous):
                         raise ValueError("get_grouped host outputs must be C-contiguous arrays of the shard dtype")
+                    if self.width > 1 and v.size != kk.size * self.width:
+                        raise ValueError("row shard: get_grouped outputs must hold keys * width values")
                     vv = v
                 else:
                     vv = self._host_vals(v, kk.size)
@@ -225,7 +252,9 @@ class Shard:
     def info(self) -> dict:
         i = _lib.PskvInfo()
         check(lib.pskv_shard_info(self._h, ctypes.byref(i)))
-        return {f: getattr(i, f) for f, _ in _lib.PskvInfo._fields_}
+        d = {f: getattr(i, f) for f, _ in _lib.PskvInfo._fields_}
+        d["width"] = int(lib.pskv_shard_width(self._h))
+        return d
 
     def set_timing(self, on, kernels=None):
         """on: bool; kernels: optional list of kernel ids (_lib.PSKV_K_*) to time."""
@@ -251,6 +280,8 @@ class Shard:
 
         n = self.key_end - self.key_begin
         ptr = self.dense_ptr()
+        if self.width > 1:
+            return _tensor_from_ptr(ptr, n * self.width, _torch_dtype(self.dtype), self.device).view(n, self.width)
         return _tensor_from_ptr(ptr, n, _torch_dtype(self.dtype), self.device)
 
 

@@ -107,23 +107,31 @@ class HipStorage(AbstractStorage):
     """HBM-resident storage: every SubAdd / SubGet runs the HIP kernels.
 
     Defaults reproduce the reference's argument-less construction
-    (driver/engine.hpp:100-109): the whole uint32 key space, assign semantics."""
+    (driver/engine.hpp:100-109): the whole uint32 key space, assign semantics.
+    width > 1: a row-valued storage, `width` values per key (the value frame
+    of an Add holds keys * width values, row-major, and so does a Get reply)."""
 
     def __init__(self, val_dtype=np.float32, key_begin: int = 0, key_end: int = 1 << 32,
-                 device: int = 0, mode: str = "assign", overflow_slots: int = 0):
+                 device: int = 0, mode: str = "assign", overflow_slots: int = 0, width: int = 1):
         self.val_dtype = np.dtype(val_dtype)
+        self.width = int(width)
         self.shard = Shard(key_begin, key_end, self.val_dtype, mode=mode, device=device,
-                           overflow_slots=overflow_slots)
+                           overflow_slots=overflow_slots, width=self.width)
 
     def SubAdd(self, typed_keys, vals) -> None:
         typed_vals = typed(vals, self.val_dtype)
-        CHECK(typed_keys.size == typed_vals.size,
-              f"CHECK_EQ(typed_keys.size(), typed_vals.size()) failed: {typed_keys.size} vs {typed_vals.size}")
+        if self.width > 1:
+            CHECK(typed_keys.size * self.width == typed_vals.size,
+                  f"CHECK_EQ(typed_keys.size() * width, typed_vals.size()) failed: "
+                  f"{typed_keys.size} * {self.width} vs {typed_vals.size}")
+        else:
+            CHECK(typed_keys.size == typed_vals.size,
+                  f"CHECK_EQ(typed_keys.size(), typed_vals.size()) failed: {typed_keys.size} vs {typed_vals.size}")
         self.shard.add(typed_keys, typed_vals)
 
     def SubGet(self, typed_keys) -> np.ndarray:
         vals = self.shard.get(np.ascontiguousarray(typed_keys, dtype=np.uint32))
-        return vals.view(np.uint8)
+        return vals.reshape(-1).view(np.uint8)
 
     def FinishIter(self) -> None:
         self.shard.sync()
