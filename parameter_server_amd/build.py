@@ -44,7 +44,8 @@ def _stale(out, deps):
 
 def build_lib(force=False):
     srcs = [os.path.join(CSRC, s) for s in LIB_SOURCES]
-    deps = srcs + [os.path.join(CSRC, h) for h in ("pskv_internal.h", "pskv_frames.h", "pskv_queues.h")] + [os.path.join(INCLUDE, "pskv.h")]
+    hdrs = [os.path.join(CSRC, h) for h in sorted(os.listdir(CSRC)) if h.endswith(".h")]
+    deps = srcs + hdrs + [os.path.join(INCLUDE, "pskv.h")]
     if force or _stale(LIB_OUT, deps):
         # built beside, then renamed over: a reader (a test, a GPU-box upload)
         # never sees a half-written library

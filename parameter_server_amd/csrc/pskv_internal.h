@@ -1,5 +1,9 @@
 // pskv_internal.h — device-side data layout and kernel launch wrappers shared by
-// pskv_kernels.hip (device code) and pskv_shard.cpp (the C ABI host logic).
+// pskv_kernels.hip, pskv_rows.hip (device code) and pskv_shard.cpp (the C ABI
+// host logic).  The host planner -- pieces, launch groups, staging layout, DMA
+// windows, the key check and K5's bucket rule (RbMap), with the limits they
+// share with the kernels (kMaxBatches, kRbMaxBuckets) -- is pskv_plan.h,
+// included here.
 //
 // HBM layout of one shard (DESIGN.md "Data layout in HBM"):
 //   dense[range]        value array, one slot per owned key, zero-initialised
@@ -13,9 +17,10 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "pskv_plan.h"
+
 namespace pskv {
 
-constexpr int kMaxBatches = 64;     // batches per grouped launch (kernarg budget)
 constexpr int kBlock = 256;         // threads per workgroup (4 waves)
 constexpr int kGatherVec = 4;       // keys per lane per step (16 B loads)
 constexpr int kSortedUnroll = 2;
@@ -23,7 +28,6 @@ inline int stream_chunk(int unroll) { return kBlock * 4 * unroll; }  // keys per
 constexpr int kSortedChunk = kBlock * 4 * kSortedUnroll;          // 2048 keys / workgroup
 constexpr int kGeneralChunk = 2048;  // keys per workgroup in the dedup path
 constexpr int kGeneralSlots = 4096;  // LDS hash slots (load factor <= 1/2)
-constexpr int kRbMaxBuckets = 2064;  // key buckets incl. the out-of-range bucket (>= 2049)
 // K5a workgroup (option RB_BIN_BLOCK): 1024 threads, one per CU.  Two
 // 512-thread workgroups per CU on 4 Ki-key super-chunks bin at the same rate
 // (K5a 55.0 against 56.0 us per 8 M cfg-3 Zipf keys): K5a is bound by the CU's
@@ -190,18 +194,6 @@ constexpr uint32_t kK1rTableWords = 4100;
 hipError_t launch_gather_replay(int vb, bool vec, int unroll, bool nt, const GroupArgs& ga, uint32_t nwg,
                                 const DenseView& d, const Ovf& o, const ReplayGroup& rg,
                                 const uint32_t* cond, uint32_t epoch, uint32_t* tab, hipStream_t st);
-// K5 key buckets: windows of 2^wbits keys of the owned range, window w in
-// bucket w % nbd (1 <= nbd < 2^12, windows < 2^21: wbits >= 11 or a range
-// below 2^32); magic = ceil(2^32 / nbd); span = keys per bucket at most
-// (ceil(windows / nbd) << wbits), the extent of a bucket's local index.
-struct RbMap {
-  uint32_t wbits;
-  uint32_t nbd;
-  uint32_t magic;
-  uint32_t span;
-  int32_t nlog;  // log2(nbd) when nbd is a power of two (then magic is unused), else -1
-};
-
 // K5 radix-bucket general Add (2 launches: K5a bin, K5b resolve).  `ga`
 // chunked by rb_superchunk(vb, bin_block) keys (nsc <= kRbMaxSc super-chunks);
 // nbd dense buckets (RbMap) plus one out-of-range bucket.  bin_block: K5a's

@@ -1,0 +1,307 @@
+// pskv_plan.h — the host planner: the pure arithmetic of a shard's host paths
+// (pskv_shard.cpp).  How a call's batches are cut into pieces, launch groups
+// and DMA windows, where each batch lies in a staging buffer, the vectorised
+// key check of host inputs, and K5's bucket rule.  No HIP and no shard state:
+// everything here is a function of its arguments, so it is tested on the CPU
+// (tests/cpp/host_plan_test.cpp).  Internal linkage throughout: libpskv.so
+// exports nothing from this header (the types the kernels do not share are in
+// an unnamed namespace, so that no instantiation over them is exported either).
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include <algorithm>
+#include <cstring>
+#include <utility>
+#include <vector>
+
+#include "pskv.h"
+
+namespace pskv {
+
+constexpr int kMaxBatches = 64;      // batches per grouped launch (kernarg budget)
+constexpr int kRbMaxBuckets = 2064;  // key buckets incl. the out-of-range bucket (>= 2049)
+constexpr uint64_t kMaxGroupElems = 1ull << 32;  // a launch group holds fewer (32-bit stamp index and counts)
+
+constexpr size_t kPieceBytes = 1 << 20;         // one pool task
+constexpr size_t kCheckPieceBytes = 256 << 10;  // one pool task of a check without copy
+constexpr size_t kWindowBytes = 8 << 20;  // one H2D / D2H DMA while the next window is copied
+
+namespace {
+
+static inline size_t round16(size_t x) { return (x + 15) & ~size_t(15); }
+
+static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+static inline uint64_t next_pow2(uint64_t x) {
+  uint64_t p = 1;
+  while (p < x) p <<= 1;
+  return p;
+}
+
+// ------------------------------------------------------ pieces and groups
+// Append batch b to v as consecutive pieces of at most kMaxPiece elements
+// (empty batches are dropped).  A batch applied piece by piece in order is the
+// same Add (last-wins / sums follow index order) and the same Get, and every
+// launch group then stays below 2^32 elements (the stamp index and the
+// per-launch element counts are 32 bits).  vb: bytes per key of the value
+// side (a row shard: width * value bytes).
+constexpr uint64_t kMaxPiece = 1ull << 31;
+static inline void push_pieces(std::vector<pskv_batch>& v, const pskv_batch& b, size_t vb) {
+  for (uint64_t off = 0; off < b.n; off += kMaxPiece)
+    v.push_back(pskv_batch{b.keys + off, static_cast<char*>(b.vals) + off * vb, std::min(kMaxPiece, b.n - off)});
+}
+
+using Span = std::pair<size_t, size_t>;  // [first, end) of a batch or piece list
+
+// Split a batch list into launch groups: <= max_batches batches and fewer than
+// max_elems elements each.  Every batch holds at most kMaxPiece elements
+// (push_pieces), so every group takes at least one batch.
+static inline std::vector<Span> split_groups(const std::vector<pskv_batch>& v, size_t max_batches = kMaxBatches,
+                                             uint64_t max_elems = kMaxGroupElems) {
+  std::vector<Span> out;
+  size_t b = 0;
+  while (b < v.size()) {
+    size_t e = b;
+    uint64_t el = 0;
+    while (e < v.size() && e - b < max_batches && el + v[e].n < max_elems) {
+      el += v[e].n;
+      ++e;
+    }
+    out.emplace_back(b, e);
+    b = e;
+  }
+  return out;
+}
+
+// Batches into K1 / DMA windows of a page-locked Get: each window takes
+// batches until it holds at least min_key_bytes of keys, and is one launch
+// group (split_groups' limits).  A window always takes its first batch.
+static inline std::vector<Span> batch_windows(const std::vector<pskv_batch>& v, size_t min_key_bytes = kWindowBytes,
+                                              size_t max_batches = kMaxBatches,
+                                              uint64_t max_elems = kMaxGroupElems) {
+  std::vector<Span> wins;
+  for (size_t i = 0; i < v.size();) {
+    size_t j = i, kb = 0;
+    uint64_t el = 0;
+    while (j < v.size() &&
+           (j == i || (kb < min_key_bytes && j - i < max_batches && el + v[j].n < max_elems))) {
+      kb += v[j].n * 4;
+      el += v[j].n;
+      ++j;
+    }
+    wins.emplace_back(i, j);
+    i = j;
+  }
+  return wins;
+}
+
+// ------------------------------------------------------------ staging layout
+// Where each batch's keys and values lie in a staging buffer: every range
+// starts on a 16-byte boundary (16 B vector accesses, DMA alignment).
+enum class StageOrder {
+  kInterleaved,  // keys of batch 0, values of batch 0, keys of batch 1, ...
+  kKeysFirst,    // every batch's keys, then every batch's values
+};
+struct StageSlot {
+  size_t keys, vals;  // byte offsets from the staging's start
+};
+struct StageLayout {
+  std::vector<StageSlot> at;  // per batch
+  size_t key_bytes = 0;       // all key ranges (kKeysFirst: the values start here)
+  size_t total = 0;
+  // The batches as views into a staging buffer at `base`.
+  std::vector<pskv_batch> views(const std::vector<pskv_batch>& v, char* base) const {
+    std::vector<pskv_batch> out(v.size());
+    for (size_t i = 0; i < v.size(); ++i)
+      out[i] = pskv_batch{reinterpret_cast<const uint32_t*>(base + at[i].keys), base + at[i].vals, v[i].n};
+    return out;
+  }
+};
+
+// Staging bytes of the batches (either order); vb: value-side bytes per key.
+static inline size_t staged_bytes(const std::vector<pskv_batch>& v, size_t vb) {
+  size_t bytes = 0;
+  for (const auto& b : v) bytes += round16(b.n * 4) + round16(b.n * vb);
+  return bytes;
+}
+
+static inline StageLayout stage_layout(const std::vector<pskv_batch>& v, size_t vb, StageOrder order) {
+  StageLayout l;
+  l.at.resize(v.size());
+  for (const auto& b : v) l.key_bytes += round16(b.n * 4);
+  size_t ko = 0, vo = order == StageOrder::kKeysFirst ? l.key_bytes : 0;
+  for (size_t i = 0; i < v.size(); ++i) {
+    const size_t kb = round16(v[i].n * 4), vbytes = round16(v[i].n * vb);
+    if (order == StageOrder::kInterleaved) {
+      l.at[i] = StageSlot{ko, ko + kb};
+      ko += kb + vbytes;
+    } else {
+      l.at[i] = StageSlot{ko, vo};
+      ko += kb;
+      vo += vbytes;
+    }
+  }
+  l.total = order == StageOrder::kInterleaved ? ko : vo;
+  return l;
+}
+
+// -------------------------------------------------- host copies and checks
+// One contiguous piece of a host->pinned (or pinned->host) copy.
+struct Piece {
+  const char* src;
+  char* dst;
+  size_t bytes;
+  int key_batch;  // >= 0: keys of that batch (checked while copied), -1: values
+  // results of the key check
+  bool sorted;
+  bool dense;  // every key is its predecessor + 1
+  uint32_t first, last;
+  uint64_t outside;
+};
+
+// The key check, written so the compiler vectorises it (no loop-carried
+// state but the or / sum reductions): 2-4x the rate of the sequential form.
+static inline void check_keys(Piece& p, const uint32_t* k, size_t n, uint32_t key_begin, uint64_t range) {
+  p.sorted = p.dense = true;
+  p.first = p.last = 0;
+  p.outside = 0;
+  if (!n) return;
+  const uint32_t rmax = range ? (uint32_t)(range - 1) : 0u;  // in range: (x - key_begin) <= rmax
+  uint32_t unsorted = 0, gap = 0, out = (uint32_t)(k[0] - key_begin) > rmax;
+  for (size_t i = 1; i < n; ++i) {
+    const uint32_t a = k[i - 1], x = k[i];
+    unsorted |= (uint32_t)(a > x);
+    gap |= (uint32_t)(x != a + 1u);
+    out += (uint32_t)((uint32_t)(x - key_begin) > rmax);
+  }
+  p.sorted = unsorted == 0;
+  p.dense = gap == 0;
+  p.first = k[0];
+  p.last = k[n - 1];
+  p.outside = range ? out : n;  // pieces hold < 2^32 keys
+}
+
+static inline void copy_piece(Piece& p, uint32_t key_begin, uint64_t range) {
+  if (p.key_batch < 0) {
+    std::memcpy(p.dst, p.src, p.bytes);
+    return;
+  }
+  if (p.dst) std::memcpy(p.dst, p.src, p.bytes);  // else a page-locked caller buffer: check only
+  check_keys(p, reinterpret_cast<const uint32_t*>(p.src), p.bytes / 4, key_begin, range);
+}
+
+// Cut [src, src+bytes) into pieces appended to `out`; check-only pieces
+// (dst null) are smaller, so a pool spreads a medium batch's check wider.
+static inline void add_pieces(std::vector<Piece>& out, const void* src, char* dst, size_t bytes, int key_batch) {
+  const char* s = static_cast<const char*>(src);
+  const size_t piece = dst ? kPieceBytes : kCheckPieceBytes;
+  for (size_t off = 0; off < bytes; off += piece) {
+    Piece p{};
+    p.src = s + off;
+    p.dst = dst ? dst + off : nullptr;
+    p.bytes = std::min(piece, bytes - off);
+    p.key_batch = key_batch;
+    p.sorted = true;
+    p.dense = true;
+    out.push_back(p);
+  }
+}
+
+// Combine the per-piece key checks: every piece sorted, and each piece's first
+// key not below the previous piece's last key within the same batch.
+static inline void combine_checks(const std::vector<Piece>& pieces, bool* all_sorted_in_range,
+                                  bool* all_dense_in_range) {
+  bool ok = true, dense = true;
+  uint64_t outside = 0;
+  int prev_batch = -1;
+  uint32_t prev_last = 0;
+  for (const auto& p : pieces) {
+    if (p.key_batch < 0) continue;
+    outside += p.outside;
+    ok &= p.sorted;
+    dense &= p.dense;
+    if (p.key_batch == prev_batch) {
+      ok &= prev_last <= p.first;
+      dense &= p.first == prev_last + 1u;
+    }
+    prev_batch = p.key_batch;
+    prev_last = p.last;
+  }
+  *all_sorted_in_range = ok && outside == 0;
+  if (all_dense_in_range) *all_dense_in_range = dense && outside == 0;
+}
+
+// Pieces into copy windows: each window takes pieces until it holds at least
+// `window` bytes (one DMA while the pool copies the next window).
+static inline std::vector<Span> piece_windows(const std::vector<Piece>& pieces, size_t window = kWindowBytes) {
+  std::vector<Span> wins;
+  for (size_t i = 0; i < pieces.size();) {
+    size_t j = i, win = 0;
+    while (j < pieces.size() && (win < window || j == i)) win += pieces[j++].bytes;
+    wins.emplace_back(i, j);
+    i = j;
+  }
+  return wins;
+}
+
+}  // namespace
+
+// ------------------------------------------------------------ K5 bucket rule
+// K5 key buckets: windows of 2^wbits keys of the owned range, window w in
+// bucket w % nbd (1 <= nbd < 2^12, windows < 2^21: wbits >= 11 or a range
+// below 2^32); magic = ceil(2^32 / nbd); span = keys per bucket at most
+// (ceil(windows / nbd) << wbits), the extent of a bucket's local index.
+struct RbMap {
+  uint32_t wbits;
+  uint32_t nbd;
+  uint32_t magic;
+  uint32_t span;
+  int32_t nlog;  // log2(nbd) when nbd is a power of two (then magic is unused), else -1
+};
+namespace {
+
+struct RbPlan {
+  RbMap bm;
+  int apply_log2;  // log2 of the resolve workgroup's LDS table slots
+};
+
+// The buckets of one K5 launch of `elems` keys into a shard of `range` keys.
+// bucket = key offset >> bshift (more buckets: longer loff rows, shorter
+// runs).  Per mode: assign takes one bucket per 2 Ki pushed keys, at most
+// 2^11 bucket bits; accumulate, whose resolve also reads the parameters, one
+// per 4 Ki, at most 2^10.  The sweep behind the rule (tools/zipf_probe.py,
+// 4/8/16 x 1M Zipf keys) and its timings: DESIGN.md §7 "K5 bucket count",
+// logs in profiles/r01_probes/probe_tb*.log and probe_new_*.log.
+// The resolve workgroup uses a 2^13-slot LDS table while buckets average
+// <= 2 Ki pushed keys, else 2^14.
+// tb, wbits, nbd: options RB_TB, RB_WBITS, RB_NBD (0 = by the rule).
+static inline RbPlan rb_plan(uint64_t range, uint64_t elems, int mode, uint32_t tb_opt, uint32_t wbits_opt,
+                             uint32_t nbd_opt) {
+  uint32_t bits = 0;
+  while (bits < 32 && ((range - 1) >> bits) != 0) ++bits;
+  const uint32_t per = mode == PSKV_ASSIGN ? 11 : 12, tmax = mode == PSKV_ASSIGN ? 11 : 10;
+  uint32_t tb = 6;
+  while (tb < tmax && (elems >> (per + tb)) != 0) ++tb;
+  if (tb_opt) tb = tb_opt;
+  const uint32_t bshift = bits > tb ? bits - tb : 0;
+  uint32_t nbd = (uint32_t)(((range - 1) >> bshift) + 1);
+  if (nbd_opt) nbd = nbd_opt;
+  // The buckets own windows of 2^wbits keys dealt round-robin (window w ->
+  // bucket w % nbd); wbits = bshift is one contiguous window per bucket.
+  RbPlan p;
+  RbMap& bm = p.bm;
+  bm.wbits = std::min<uint32_t>(bshift, wbits_opt ? wbits_opt : 11u);
+  bm.nbd = nbd;
+  bm.nlog = -1;
+  for (int l = 0; l < 12; ++l)
+    if (nbd == (1u << l)) bm.nlog = l;
+  bm.magic = nbd > 1 ? (uint32_t)(((1ull << 32) + nbd - 1) / nbd) : 0u;  // nbd = 1 takes the shift path
+  const uint64_t nwin = ((range - 1) >> bm.wbits) + 1;  // < 2^21: wbits = 11, or wbits = bshift and nwin = nbd
+  bm.span = (uint32_t)std::min<uint64_t>(((nwin + nbd - 1) / nbd) << bm.wbits, 0xFFFFFFFFull);
+  p.apply_log2 = elems / nbd <= 2048 ? 13 : 14;
+  return p;
+}
+
+}  // namespace
+}  // namespace pskv

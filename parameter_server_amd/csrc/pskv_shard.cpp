@@ -18,6 +18,13 @@
 //                   tagged the call.  No hint: K5 (key buckets).
 // Accumulate-mode Add: K6 density proof + K7 for dense windows, else K5.
 // Get: K1 (one launch per group of <= 64 batches), K8 for small messages.
+//
+// This file is the policy: which path a call takes, what it queues and in
+// which order, and what it waits for.  The arithmetic underneath -- pieces,
+// launch groups, staging layout, DMA windows, the key check, K5's bucket rule
+// -- is the host planner, pskv_plan.h (no HIP, tested on the CPU).  The hold
+// on the pinned staging buffer is a scope guard (HstageHold), not a call on
+// each error exit.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -38,6 +45,7 @@
 #include "pskv.h"
 #include "pskv_frames.h"
 #include "pskv_internal.h"
+#include "pskv_plan.h"
 #include "pskv_queues.h"
 
 using namespace pskv;
@@ -69,14 +77,6 @@ int value_bytes(int dtype) {
       return 0;
   }
 }
-
-uint64_t next_pow2(uint64_t x) {
-  uint64_t p = 1;
-  while (p < x) p <<= 1;
-  return p;
-}
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 constexpr uint64_t kDefaultOverflowSlots = 1ull << 16;
 // see tune_dma_min_bytes: measured per call (tools/micro/small_latency.cpp,
@@ -187,9 +187,6 @@ class HostPool {
   bool stop_ = false;
 };
 
-constexpr size_t kPieceBytes = 1 << 20;   // one pool task
-constexpr size_t kCheckPieceBytes = 256 << 10;  // one pool task of a check without copy
-constexpr size_t kWindowBytes = 8 << 20;  // one H2D / D2H DMA while the next window is copied
 constexpr size_t kInlineCopyBytes = 256 << 10;  // smaller windows are copied by the calling thread
 
 // Run fn over pieces [b, e) of `pieces`: on the calling thread when they are
@@ -844,14 +841,28 @@ class GrowService {
   uint64_t served_ = 0;
 };
 
-// A call that gives up on a wait (PSKV_ESTATE) or fails after queueing work
-// that still reads or writes the pinned staging buffer (H2D from it, D2H or K1
-// stores into it): mark the buffer busy until the stream's current end, so the
-// next host call waits (bounded) before its CPU copy touches the buffer or a
-// regrowth frees it.
-void hold_hstage(pskv_shard* s) {
-  if (hipEventRecord(s->hstage_free, s->stream) == hipSuccess) s->hstage_pending = true;
-}
+// The hold on the pinned staging buffer, as a scope guard.  The rule: once
+// anything queued reads or writes the buffer (H2D from it, D2H or K1 stores
+// into it), no exit may leave without marking it busy until the stream's
+// current end, so the next host call waits (bounded) before its CPU copy
+// touches the buffer or a regrowth frees it -- a call that gives
+// up on a wait (PSKV_ESTATE) or fails midway included.  A path arms the guard
+// before it queues the first such operation; every exit from the guard's
+// scope then records hstage_free.  A Get that has waited for all of its copies
+// dismisses it (no event record on a successful Get); a staged Add, which
+// returns before its DMA, leaves it armed.
+struct HstageHold {
+  pskv_shard* s;
+  bool armed = false;
+  explicit HstageHold(pskv_shard* s_) : s(s_) {}
+  HstageHold(const HstageHold&) = delete;
+  HstageHold& operator=(const HstageHold&) = delete;
+  void arm() { armed = true; }
+  void dismiss() { armed = false; }
+  ~HstageHold() {
+    if (armed && hipEventRecord(s->hstage_free, s->stream) == hipSuccess) s->hstage_pending = true;
+  }
+};
 
 int ensure_hstage(pskv_shard* s, size_t bytes) {
   if (s->hstage_pending) {
@@ -887,23 +898,58 @@ int ensure_dstage(pskv_shard* s, size_t bytes) {
   return PSKV_OK;
 }
 
-size_t round16(size_t x) { return (x + 15) & ~size_t(15); }
+// One launch group: the kernarg descriptor of batches [b, e) of a list, cut
+// into chunks of `chunk` elements per workgroup, with its workgroup and
+// element counts.
+struct LaunchGroup {
+  GroupArgs ga;
+  uint32_t nwg;
+  uint64_t elems;
+};
 
-// Build the kernarg group descriptor for batches [b, e) with `chunk` elements
-// per workgroup.  Returns the workgroup count.
-uint32_t build_group(const std::vector<pskv_batch>& v, size_t b, size_t e, uint64_t chunk,
-                     GroupArgs* ga) {
-  std::memset(ga, 0, sizeof(*ga));
-  ga->nb = (int)(e - b);
+// chunk_of(elems): the chunk, for a kernel that chooses it by the launch's size.
+template <typename ChunkOf>
+LaunchGroup make_group_by(const std::vector<pskv_batch>& v, size_t b, size_t e, const ChunkOf& chunk_of) {
+  LaunchGroup g;
+  std::memset(&g.ga, 0, sizeof(g.ga));
+  g.ga.nb = (int)(e - b);
+  g.elems = 0;
+  for (size_t i = b; i < e; ++i) g.elems += v[i].n;
+  const uint64_t chunk = chunk_of(g.elems);
   uint64_t wg = 0;
   for (size_t i = b; i < e; ++i) {
     const int j = (int)(i - b);
-    ga->wg_prefix[j] = (uint32_t)wg;
-    ga->b[j] = DevBatch{v[i].keys, v[i].vals, v[i].n};
+    g.ga.wg_prefix[j] = (uint32_t)wg;
+    g.ga.b[j] = DevBatch{v[i].keys, v[i].vals, v[i].n};
     wg += (v[i].n + chunk - 1) / chunk;
   }
-  ga->wg_prefix[e - b] = (uint32_t)wg;
-  return (uint32_t)wg;
+  g.ga.wg_prefix[e - b] = (uint32_t)wg;
+  g.nwg = (uint32_t)wg;
+  return g;
+}
+
+LaunchGroup make_group(const std::vector<pskv_batch>& v, size_t b, size_t e, uint64_t chunk) {
+  return make_group_by(v, b, e, [chunk](uint64_t) { return chunk; });
+}
+
+// Every keys and values pointer 16-byte aligned: the kernels' `vec` argument.
+bool all_aligned16(const std::vector<pskv_batch>& v) {
+  bool vec = true;
+  for (auto& b : v) vec &= aligned16(b.keys) & aligned16(b.vals);
+  return vec;
+}
+
+// The stamp array is only needed once a stamp-mode Add can run: allocate it on
+// first use (8 B per owned KEY, also in a row shard).
+int ensure_owner(pskv_shard* s) {
+  if (s->owner) return PSKV_OK;
+  const size_t bytes = s->range * sizeof(unsigned long long);
+  if (hipMalloc(&s->owner, bytes) != hipSuccess) {
+    s->owner = nullptr;
+    return fail(PSKV_ENOMEM, "stamp array allocation failed");
+  }
+  PSKV_HIP(hipMemsetAsync(s->owner, 0, bytes, s->stream));
+  return PSKV_OK;
 }
 
 uint32_t next_epoch(pskv_shard* s) {
@@ -915,36 +961,6 @@ uint32_t next_epoch(pskv_shard* s) {
     s->epoch = 0;
   }
   return ++s->epoch;
-}
-
-// Append batch b to v as consecutive pieces of at most kMaxPiece elements
-// (empty batches are dropped).  A batch applied piece by piece in order is the
-// same Add (last-wins / sums follow index order) and the same Get, and every
-// launch group then stays below 2^32 elements (the stamp index and the
-// per-launch element counts are 32 bits).
-constexpr uint64_t kMaxPiece = 1ull << 31;
-void push_pieces(std::vector<pskv_batch>& v, const pskv_batch& b, size_t vb) {
-  for (uint64_t off = 0; off < b.n; off += kMaxPiece)
-    v.push_back(pskv_batch{b.keys + off, static_cast<char*>(b.vals) + off * vb, std::min(kMaxPiece, b.n - off)});
-}
-
-// Split a batch list into launch groups: <= kMaxBatches batches and < 2^32
-// elements each.  Every batch holds at most kMaxPiece elements (push_pieces),
-// so every group takes at least one batch.
-std::vector<std::pair<size_t, size_t>> split_groups(const std::vector<pskv_batch>& v) {
-  std::vector<std::pair<size_t, size_t>> out;
-  size_t b = 0;
-  while (b < v.size()) {
-    size_t e = b;
-    uint64_t el = 0;
-    while (e < v.size() && e - b < (size_t)kMaxBatches && el + v[e].n < (1ull << 32)) {
-      el += v[e].n;
-      ++e;
-    }
-    out.emplace_back(b, e);
-    b = e;
-  }
-  return out;
 }
 
 // Grow a device scratch buffer (stream-ordered: queued kernels may still use
@@ -970,41 +986,11 @@ int ensure_scratch(pskv_shard* s, void** p, size_t* have, size_t need) {
 // per <= kRbMaxSc super-chunks; a longer group is cut into consecutive pieces
 // (a batch may be split), which run in stream order, so call order holds.
 int radix_launch(pskv_shard* s, const std::vector<pskv_batch>& v, size_t b, size_t e) {
-  GroupArgs ga;
-  const uint32_t nsc = build_group(v, b, e, rb_superchunk(s->vb, s->tune_rb_bin_block), &ga);
-  uint64_t elems = 0;
-  for (size_t i = b; i < e; ++i) elems += v[i].n;
-  // bucket = key offset >> bshift (more buckets: longer loff rows, shorter
-  // runs).  Per mode: assign takes one bucket per 2 Ki pushed keys, at most
-  // 2^11 bucket bits; accumulate, whose resolve also reads the parameters, one
-  // per 4 Ki, at most 2^10.  The sweep behind the rule (tools/zipf_probe.py,
-  // 4/8/16 x 1M Zipf keys) and its timings: DESIGN.md §7 "K5 bucket count",
-  // logs in profiles/r01_probes/probe_tb*.log and probe_new_*.log.
-  // The resolve workgroup uses a 2^13-slot LDS table while buckets average
-  // <= 2 Ki pushed keys, else 2^14.
-  uint32_t bits = 0;
-  while (bits < 32 && ((s->range - 1) >> bits) != 0) ++bits;
-  const uint32_t per = s->mode == PSKV_ASSIGN ? 11 : 12, tmax = s->mode == PSKV_ASSIGN ? 11 : 10;
-  uint32_t tb = 6;
-  while (tb < tmax && (elems >> (per + tb)) != 0) ++tb;
-  if (s->tune_rb_tb) tb = s->tune_rb_tb;
-  const uint32_t bshift = bits > tb ? bits - tb : 0;
-  uint32_t nbd = (uint32_t)(((s->range - 1) >> bshift) + 1);
-  if (s->tune_rb_nbd) nbd = s->tune_rb_nbd;
-  const uint32_t nbk = nbd + 1;
-  // The buckets own windows of 2^wbits keys dealt round-robin (window w ->
-  // bucket w % nbd); wbits = bshift is one contiguous window per bucket.
-  RbMap bm;
-  bm.wbits = std::min<uint32_t>(bshift, s->tune_rb_wbits ? s->tune_rb_wbits : 11u);
-  bm.nbd = nbd;
-  bm.nlog = -1;
-  for (int l = 0; l < 12; ++l)
-    if (nbd == (1u << l)) bm.nlog = l;
-  bm.magic = nbd > 1 ? (uint32_t)(((1ull << 32) + nbd - 1) / nbd) : 0u;  // nbd = 1 takes the shift path
-  const uint64_t nwin = ((s->range - 1) >> bm.wbits) + 1;  // < 2^21: wbits = 11, or wbits = bshift and nwin = nbd
-  bm.span = (uint32_t)std::min<uint64_t>(((nwin + nbd - 1) / nbd) << bm.wbits, 0xFFFFFFFFull);
-  int apply_log2 = elems / nbd <= 2048 ? 13 : 14;
-  if (s->tune_rb_apply_log2) apply_log2 = s->tune_rb_apply_log2;
+  const LaunchGroup g = make_group(v, b, e, rb_superchunk(s->vb, s->tune_rb_bin_block));
+  const uint32_t nsc = g.nwg;
+  const RbPlan p = rb_plan(s->range, g.elems, s->mode, s->tune_rb_tb, s->tune_rb_wbits, s->tune_rb_nbd);
+  const int apply_log2 = s->tune_rb_apply_log2 ? s->tune_rb_apply_log2 : p.apply_log2;
+  const uint32_t nbk = p.bm.nbd + 1;
   if (nbk > (uint32_t)kRbMaxBuckets) return fail(PSKV_EINVAL, "radix path: too many buckets");
   if (nsc > kRbMaxSc) return fail(PSKV_EINVAL, "radix path: launch piece too large");
   const size_t eb = rb_entry_bytes(s->vb);
@@ -1014,8 +1000,8 @@ int radix_launch(pskv_shard* s, const std::vector<pskv_batch>& v, size_t b, size
     rc = ensure_scratch(s, &s->rb_ent, &s->rb_ent_bytes,
                         (size_t)nsc * rb_superchunk(s->vb, s->tune_rb_bin_block) * eb + kRbTmpPad);
   if (rc) return rc;
-  LaunchTimer t(s, PSKV_K_RADIX, elems);
-  PSKV_HIP(launch_rb_add(s->dtype, s->mode, ga, nsc, s->dview(), s->ovf, bm, apply_log2,
+  LaunchTimer t(s, PSKV_K_RADIX, g.elems);
+  PSKV_HIP(launch_rb_add(s->dtype, s->mode, g.ga, nsc, s->dview(), s->ovf, p.bm, apply_log2,
                          s->tune_rb_bin_block, s->rb_loff, s->rb_ent, s->stream));
   t.done();
   s->n_general += 2;
@@ -1055,44 +1041,31 @@ int radix_add(pskv_shard* s, const std::vector<pskv_batch>& v, size_t b, size_t 
   return flush();
 }
 
-// The general (any order) Add over one launch group.  `cond` non-null makes
-// it a repair that runs only when the sorted path tagged `epoch` (K4, whose
-// idle launches are cheap); unconditional general Adds take K5.
-int general_add(pskv_shard* s, const std::vector<pskv_batch>& v, size_t b, size_t e,
-                uint32_t epoch, const uint32_t* cond, bool radix = true) {
-  if (!cond && ((radix && s->general_path == 1) || s->general_path == 2)) return radix_add(s, v, b, e);
-  if (s->mode == PSKV_ASSIGN && !s->owner) {
-    // The stamp array is only needed once the general path can run: allocate it
-    // on first use (8 B per owned key).
-    const size_t bytes = s->range * sizeof(unsigned long long);
-    if (hipMalloc(&s->owner, bytes) != hipSuccess) {
-      s->owner = nullptr;
-      return fail(PSKV_ENOMEM, "stamp array allocation failed");
-    }
-    PSKV_HIP(hipMemsetAsync(s->owner, 0, bytes, s->stream));
-  }
-  GroupArgs ga;
-  const uint32_t nwg = build_group(v, b, e, kGeneralChunk, &ga);
-  uint64_t elems = 0;
-  for (size_t i = b; i < e; ++i) elems += v[i].n;
+// The general (any order) Add over one launch group: K5, or K4 (stamps) under
+// GENERAL = 0.
+int general_add(pskv_shard* s, const std::vector<pskv_batch>& v, size_t b, size_t e, uint32_t epoch) {
+  if (s->general_path != 0) return radix_add(s, v, b, e);
+  if (s->mode == PSKV_ASSIGN)
+    if (int rc = ensure_owner(s)) return rc;
+  const LaunchGroup g = make_group(v, b, e, kGeneralChunk);
   {
-    LaunchTimer t(s, PSKV_K_GENERAL_MARK, elems);
-    PSKV_HIP(launch_general_mark(s->dtype, s->mode, ga, nwg, s->dview(), s->flag + 1, s->owner, cond,
+    LaunchTimer t(s, PSKV_K_GENERAL_MARK, g.elems);
+    PSKV_HIP(launch_general_mark(s->dtype, s->mode, g.ga, g.nwg, s->dview(), s->flag + 1, s->owner, nullptr,
                                  epoch, s->stream));
     t.done();
   }
   s->n_general++;
   if (s->mode == PSKV_ASSIGN) {
-    LaunchTimer t(s, PSKV_K_GENERAL_COMMIT, elems);
-    PSKV_HIP(launch_general_commit(s->vb, ga, nwg, s->dview(), s->owner, cond, epoch, s->stream));
+    LaunchTimer t(s, PSKV_K_GENERAL_COMMIT, g.elems);
+    PSKV_HIP(launch_general_commit(s->vb, g.ga, g.nwg, s->dview(), s->owner, nullptr, epoch, s->stream));
     t.done();
     s->n_general++;
   }
   // the group's out-of-range keys, which K4a only tagged (flag[1]): one
   // workgroup applies them in call order, growing the table as it goes
   {
-    LaunchTimer t(s, PSKV_K_REPLAY, elems);
-    PSKV_HIP(launch_replay(s->dtype, s->mode, ga, s->dview(), s->ovf, s->flag + 1, epoch, s->stream,
+    LaunchTimer t(s, PSKV_K_REPLAY, g.elems);
+    PSKV_HIP(launch_replay(s->dtype, s->mode, g.ga, s->dview(), s->ovf, s->flag + 1, epoch, s->stream,
                            /*oor_only=*/true));
     t.done();
     s->n_general++;
@@ -1121,21 +1094,18 @@ int flush_replay(pskv_shard* s) {
 // with 4-byte values is held instead (pend_*): the Get's first K1 launch takes
 // it (K1r), or flush_replay launches it as K4r before anything else is queued.
 int replay(pskv_shard* s, const std::vector<pskv_batch>& v, size_t b, size_t e, uint32_t epoch) {
-  GroupArgs ga;
-  (void)build_group(v, b, e, kGeneralChunk, &ga);
-  uint64_t elems = 0;
-  for (size_t i = b; i < e; ++i) elems += v[i].n;
+  const LaunchGroup g = make_group(v, b, e, kGeneralChunk);
   if (s->defer_replay && s->mode == PSKV_ASSIGN && s->vb == 4) {
     if (int rc = flush_replay(s)) return rc;  // (add_impl flushed it already: the order holds either way)
-    s->pend_rg.nb = ga.nb;
-    for (int i = 0; i < ga.nb; ++i) s->pend_rg.b[i] = ga.b[i];
+    s->pend_rg.nb = g.ga.nb;
+    for (int i = 0; i < g.ga.nb; ++i) s->pend_rg.b[i] = g.ga.b[i];
     s->pend_epoch = epoch;
-    s->pend_elems = elems;
+    s->pend_elems = g.elems;
     s->pend_replay = true;
     return PSKV_OK;
   }
-  LaunchTimer t(s, PSKV_K_REPLAY, elems);
-  PSKV_HIP(launch_replay(s->dtype, s->mode, ga, s->dview(), s->ovf, s->flag, epoch, s->stream));
+  LaunchTimer t(s, PSKV_K_REPLAY, g.elems);
+  PSKV_HIP(launch_replay(s->dtype, s->mode, g.ga, s->dview(), s->ovf, s->flag, epoch, s->stream));
   t.done();
   s->n_general++;
   return PSKV_OK;
@@ -1146,16 +1116,15 @@ int replay(pskv_shard* s, const std::vector<pskv_batch>& v, size_t b, size_t e, 
 // (a host group proven sorted but not all windows) keeps K2g out of early mode.
 int sorted_add(pskv_shard* s, const std::vector<pskv_batch>& v, size_t b, size_t e, bool vec,
                uint32_t epoch, bool repair, bool maybe_windows) {
-  uint64_t elems = 0;
-  for (size_t i = b; i < e; ++i) elems += v[i].n;
   if (e - b == 1) {
-    LaunchTimer t(s, PSKV_K_ASSIGN_SORTED, elems);
+    LaunchTimer t(s, PSKV_K_ASSIGN_SORTED, v[b].n);
     PSKV_HIP(launch_assign_sorted(s->vb, vec, v[b].keys, v[b].vals, v[b].n, s->dview(), s->flag,
                                   epoch, s->stream));
     t.done();
   } else {
-    GroupArgs ga;
-    const uint32_t nchunks = build_group(v, b, e, stream_chunk(s->tune_unroll), &ga);
+    const LaunchGroup g = make_group(v, b, e, stream_chunk(s->tune_unroll));
+    const uint32_t nchunks = g.nwg;
+    const uint64_t elems = g.elems;
     // Tile (tile mode): enough tiles for several workgroups per CU, 4 Ki..64 Ki keys.
     uint32_t shift = 16;
     while (shift > 12 && (elems >> shift) < 2048) --shift;
@@ -1176,7 +1145,7 @@ int sorted_add(pskv_shard* s, const std::vector<pskv_batch>& v, size_t b, size_t
     // mode, where early loads would only be read again (maybe_windows false).
     const bool early = s->tune_early == 1 || (s->tune_early == 2 && maybe_windows && elems * 4 < s->range);
     LaunchTimer t(s, PSKV_K_ASSIGN_TILES, elems);
-    PSKV_HIP(launch_assign_group(s->vb, vec, s->tune_unroll, s->tune_nt, s->tune_ntp, early, ga, s->dview(),
+    PSKV_HIP(launch_assign_group(s->vb, vec, s->tune_unroll, s->tune_nt, s->tune_ntp, early, g.ga, s->dview(),
                                  shift, ntiles, grid, s->flag, epoch, s->stream));
     t.done();
   }
@@ -1191,19 +1160,16 @@ int sorted_add(pskv_shard* s, const std::vector<pskv_batch>& v, size_t b, size_t
 // proven by the CPU check (verify = false).
 int dense_accumulate(pskv_shard* s, const std::vector<pskv_batch>& v, size_t b, size_t e,
                      uint32_t epoch, bool verify) {
-  uint64_t elems = 0;
-  for (size_t i = b; i < e; ++i) elems += v[i].n;
-  GroupArgs ga;
-  const uint32_t nchunks = build_group(v, b, e, stream_chunk(8), &ga);
+  const LaunchGroup g = make_group(v, b, e, stream_chunk(8));
   if (verify) {
-    LaunchTimer t(s, PSKV_K_DENSE_CHECK, elems);
-    PSKV_HIP(launch_dense_check(ga, nchunks, s->dview(), s->flag, epoch, s->stream));
+    LaunchTimer t(s, PSKV_K_DENSE_CHECK, g.elems);
+    PSKV_HIP(launch_dense_check(g.ga, g.nwg, s->dview(), s->flag, epoch, s->stream));
     t.done();
   }
   {
-    const uint32_t grid = std::min<uint32_t>(nchunks, s->tune_tile_grid);
-    LaunchTimer t(s, PSKV_K_ACC_DENSE, elems);
-    PSKV_HIP(launch_acc_dense(s->dtype, ga, grid, s->dview(), s->flag, epoch, s->stream));
+    const uint32_t grid = std::min<uint32_t>(g.nwg, s->tune_tile_grid);
+    LaunchTimer t(s, PSKV_K_ACC_DENSE, g.elems);
+    PSKV_HIP(launch_acc_dense(s->dtype, g.ga, grid, s->dview(), s->flag, epoch, s->stream));
     t.done();
   }
   s->n_sorted++;
@@ -1211,111 +1177,43 @@ int dense_accumulate(pskv_shard* s, const std::vector<pskv_batch>& v, size_t b, 
   return PSKV_OK;
 }
 
-// One contiguous piece of a host->pinned (or pinned->host) copy.
-struct Piece {
-  const char* src;
-  char* dst;
-  size_t bytes;
-  int key_batch;  // >= 0: keys of that batch (checked while copied), -1: values
-  // results of the key check
-  bool sorted;
-  bool dense;  // every key is its predecessor + 1
-  uint32_t first, last;
-  uint64_t outside;
-};
-
-// The key check, written so the compiler vectorises it (no loop-carried
-// state but the or / sum reductions): 2-4x the rate of the sequential form.
-void check_keys(Piece& p, const uint32_t* k, size_t n, uint32_t key_begin, uint64_t range) {
-  p.sorted = p.dense = true;
-  p.first = p.last = 0;
-  p.outside = 0;
-  if (!n) return;
-  const uint32_t rmax = range ? (uint32_t)(range - 1) : 0u;  // in range: (x - key_begin) <= rmax
-  uint32_t unsorted = 0, gap = 0, out = (uint32_t)(k[0] - key_begin) > rmax;
-  for (size_t i = 1; i < n; ++i) {
-    const uint32_t a = k[i - 1], x = k[i];
-    unsorted |= (uint32_t)(a > x);
-    gap |= (uint32_t)(x != a + 1u);
-    out += (uint32_t)((uint32_t)(x - key_begin) > rmax);
-  }
-  p.sorted = unsorted == 0;
-  p.dense = gap == 0;
-  p.first = k[0];
-  p.last = k[n - 1];
-  p.outside = range ? out : n;  // pieces hold < 2^32 keys
-}
-
-void copy_piece(Piece& p, uint32_t key_begin, uint64_t range) {
-  if (p.key_batch < 0) {
-    std::memcpy(p.dst, p.src, p.bytes);
-    return;
-  }
-  if (p.dst) std::memcpy(p.dst, p.src, p.bytes);  // else a page-locked caller buffer: check only
-  check_keys(p, reinterpret_cast<const uint32_t*>(p.src), p.bytes / 4, key_begin, range);
-}
-
-// Cut [src, src+bytes) into pieces appended to `out`; check-only pieces
-// (dst null) are smaller, so a pool spreads a medium batch's check wider.
-void add_pieces(std::vector<Piece>& out, const void* src, char* dst, size_t bytes, int key_batch) {
-  const char* s = static_cast<const char*>(src);
-  const size_t piece = dst ? kPieceBytes : kCheckPieceBytes;
-  for (size_t off = 0; off < bytes; off += piece) {
-    Piece p{};
-    p.src = s + off;
-    p.dst = dst ? dst + off : nullptr;
-    p.bytes = std::min(piece, bytes - off);
-    p.key_batch = key_batch;
-    p.sorted = true;
-    p.dense = true;
-    out.push_back(p);
-  }
-}
-
-// Combine the per-piece key checks: every piece sorted, and each piece's first
-// key not below the previous piece's last key within the same batch.
-void combine_checks(const std::vector<Piece>& pieces, bool* all_sorted_in_range,
-                    uint64_t* n_outside, bool* all_dense_in_range) {
-  bool ok = true, dense = true;
-  uint64_t outside = 0;
-  int prev_batch = -1;
-  uint32_t prev_last = 0;
-  for (const auto& p : pieces) {
-    if (p.key_batch < 0) continue;
-    outside += p.outside;
-    ok &= p.sorted;
-    dense &= p.dense;
-    if (p.key_batch == prev_batch) {
-      ok &= prev_last <= p.first;
-      dense &= p.first == prev_last + 1u;
-    }
-    prev_batch = p.key_batch;
-    prev_last = p.last;
-  }
-  *all_sorted_in_range = ok && outside == 0;
-  if (all_dense_in_range) *all_dense_in_range = dense && outside == 0;
-  *n_outside = outside;
+void run_copies(pskv_shard* s, std::vector<Piece>& pieces, size_t b, size_t e) {
+  run_pieces(pieces, b, e, [&](Piece& p) { copy_piece(p, s->key_begin, s->range); });
 }
 
 // Copy pieces window by window (pool in parallel) and DMA each window to the
 // device as soon as it is staged, so the copy of window w+1 overlaps the H2D
-// of window w.  Pieces must be in increasing staging order.
-int pipelined_h2d(pskv_shard* s, std::vector<Piece>& pieces, char* h, char* d) {
-  size_t i = 0;
-  while (i < pieces.size()) {
-    size_t j = i, win = 0;
-    while (j < pieces.size() && (win < kWindowBytes || j == i)) win += pieces[j++].bytes;
-    run_pieces(pieces, i, j, [&](Piece& p) { copy_piece(p, s->key_begin, s->range); });
-    char* lo = pieces[i].dst;
-    char* hi = pieces[j - 1].dst + pieces[j - 1].bytes;
-    const hipError_t e = hipMemcpyAsync(d + (lo - h), lo, (size_t)(hi - lo), hipMemcpyHostToDevice, s->stream);
-    if (e != hipSuccess) {
-      if (i) hold_hstage(s);  // the windows queued before still read the staging
-      PSKV_HIP(e);
-    }
-    i = j;
+// of window w.  Pieces must be in increasing staging order.  `hold` is armed
+// once a window's H2D from the staging is queued.
+int pipelined_h2d(pskv_shard* s, std::vector<Piece>& pieces, char* h, char* d, HstageHold& hold) {
+  for (const Span& w : piece_windows(pieces)) {
+    run_copies(s, pieces, w.first, w.second);
+    char* lo = pieces[w.first].dst;
+    char* hi = pieces[w.second - 1].dst + pieces[w.second - 1].bytes;
+    PSKV_HIP(hipMemcpyAsync(d + (lo - h), lo, (size_t)(hi - lo), hipMemcpyHostToDevice, s->stream));
+    hold.arm();
   }
   return PSKV_OK;
+}
+
+// Host batches -> device staging through pinned staging, every batch's keys
+// then every batch's values (`lay`, kKeysFirst): the keys -- and, for an Add,
+// the values -- are copied in and queued for DMA; a Get's values get room
+// behind them.  Returns the device views in `dv`; the pinned copy of a range
+// lies at the same offset of hstage.
+int stage_keys_first(pskv_shard* s, const std::vector<pskv_batch>& v, const StageLayout& lay, size_t vb,
+                     bool with_values, HstageHold& hold, std::vector<pskv_batch>* dv) {
+  int rc = ensure_hstage(s, lay.total);
+  if (rc) return rc;
+  rc = ensure_dstage(s, lay.total);
+  if (rc) return rc;
+  char* h = static_cast<char*>(s->hstage);
+  std::vector<Piece> pieces;
+  for (size_t i = 0; i < v.size(); ++i) add_pieces(pieces, v[i].keys, h + lay.at[i].keys, v[i].n * 4, -1);
+  if (with_values)
+    for (size_t i = 0; i < v.size(); ++i) add_pieces(pieces, v[i].vals, h + lay.at[i].vals, v[i].n * vb, -1);
+  *dv = lay.views(v, static_cast<char*>(s->dstage));
+  return pipelined_h2d(s, pieces, h, static_cast<char*>(s->dstage), hold);
 }
 
 // Page-locked (hipHostMalloc'd / registered) host memory: the DMA engine can
@@ -1368,14 +1266,25 @@ bool pinned_views(const std::vector<pskv_batch>& in, size_t vb, std::vector<pskv
   return true;
 }
 
+// Queue the DMA of host batches straight from the caller's buffers to their
+// device views `dv`.
+hipError_t dma_batches(pskv_shard* s, const std::vector<pskv_batch>& in, const std::vector<pskv_batch>& dv) {
+  for (size_t j = 0; j < in.size(); ++j) {
+    hipError_t e = hipMemcpyAsync(const_cast<uint32_t*>(dv[j].keys), in[j].keys, in[j].n * 4,
+                                  hipMemcpyHostToDevice, s->stream);
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(dv[j].vals, in[j].vals, in[j].n * (size_t)s->vb, hipMemcpyHostToDevice, s->stream);
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
 // Stage host batches into one device buffer (keys then values per batch,
 // 16-byte aligned) through pinned memory, checking on the way whether every
 // batch is sorted and inside the dense range.  Returns device batch views.
-int stage_host_batches(pskv_shard* s, const std::vector<pskv_batch>& in,
-                       std::vector<pskv_batch>* out, bool* all_sorted_in_range,
-                       uint64_t* n_outside, bool* all_dense_in_range = nullptr) {
-  size_t bytes = 0;
-  for (auto& b : in) bytes += round16(b.n * 4) + round16(b.n * (size_t)s->vb);
+int stage_host_batches(pskv_shard* s, const std::vector<pskv_batch>& in, std::vector<pskv_batch>* out,
+                       bool* all_sorted_in_range, bool* all_dense_in_range) {
+  const StageLayout lay = stage_layout(in, (size_t)s->vb, StageOrder::kInterleaved);
   bool locked = true;
   for (const auto& b : in) locked = locked && is_pinned(b.keys) && is_pinned(b.vals);
   // page-locked buffers: DMA'd directly from tune_dma_min_bytes_pinned on
@@ -1383,47 +1292,24 @@ int stage_host_batches(pskv_shard* s, const std::vector<pskv_batch>& in,
   // buffers only when large (the runtime's pageable copy has a high fixed cost
   // and blocks until done).  Smaller ones are copied into pinned staging and
   // DMA'd asynchronously (the call returns after the host copy).
-  locked = locked && bytes >= s->tune_dma_min_bytes_pinned;
-  const bool pinned = locked || (s->tune_pageable_dma && bytes >= s->tune_dma_min_bytes);
-  int rc = pinned ? PSKV_OK : ensure_hstage(s, bytes);
+  locked = locked && lay.total >= s->tune_dma_min_bytes_pinned;
+  const bool pinned = locked || (s->tune_pageable_dma && lay.total >= s->tune_dma_min_bytes);
+  int rc = pinned ? PSKV_OK : ensure_hstage(s, lay.total);
   if (rc) return rc;
-  rc = ensure_dstage(s, bytes);
+  rc = ensure_dstage(s, lay.total);
   if (rc) return rc;
   char* h = static_cast<char*>(s->hstage);
-  char* d = static_cast<char*>(s->dstage);
+  *out = lay.views(in, static_cast<char*>(s->dstage));
+  // direct DMA: the CPU only checks the keys (dst null)
   std::vector<Piece> pieces;
-  size_t off = 0;
-  out->clear();
-  std::vector<std::pair<char*, const pskv_batch*>> dma;  // direct DMA: (device dst, batch)
   for (size_t j = 0; j < in.size(); ++j) {
-    const auto& b = in[j];
-    pskv_batch db;
-    if (pinned) {
-      // DMA straight from the caller's buffers; the CPU only checks
-      dma.emplace_back(d + off, &b);
-      add_pieces(pieces, b.keys, nullptr, b.n * 4, (int)j);
-    } else {
-      add_pieces(pieces, b.keys, h + off, b.n * 4, (int)j);
-    }
-    db.keys = reinterpret_cast<const uint32_t*>(d + off);
-    off += round16(b.n * 4);
-    if (!pinned) add_pieces(pieces, b.vals, h + off, b.n * (size_t)s->vb, -1);
-    db.vals = d + off;
-    db.n = b.n;
-    off += round16(b.n * (size_t)s->vb);
-    out->push_back(db);
+    add_pieces(pieces, in[j].keys, pinned ? nullptr : h + lay.at[j].keys, in[j].n * 4, (int)j);
+    if (!pinned) add_pieces(pieces, in[j].vals, h + lay.at[j].vals, in[j].n * (size_t)s->vb, -1);
   }
   if (pinned) {
     auto issue = [&]() -> hipError_t {
-      for (const auto& x : dma) {
-        const pskv_batch& b = *x.second;
-        hipError_t e = hipMemcpyAsync(x.first, b.keys, b.n * 4, hipMemcpyHostToDevice, s->stream);
-        if (e == hipSuccess)
-          e = hipMemcpyAsync(x.first + round16(b.n * 4), b.vals, b.n * (size_t)s->vb,
-                             hipMemcpyHostToDevice, s->stream);
-        if (e != hipSuccess) return e;
-      }
-      return hipEventRecord(s->h2d_done, s->stream);
+      const hipError_t e = dma_batches(s, in, *out);
+      return e == hipSuccess ? hipEventRecord(s->h2d_done, s->stream) : e;
     };
     auto check = [&]() {
       HostPool::get().run(pieces.size(),
@@ -1456,12 +1342,12 @@ int stage_host_batches(pskv_shard* s, const std::vector<pskv_batch>& in,
     // the caller may reuse its buffers once this returns
     if (int rc2 = wait_event(s, s->h2d_done, "host-buffer DMA completion event", s->h2d_done)) return rc2;
   } else {
-    rc = pipelined_h2d(s, pieces, h, d);
+    // the call returns before its DMA: the hold stays armed
+    HstageHold hold(s);
+    rc = pipelined_h2d(s, pieces, h, static_cast<char*>(s->dstage), hold);
     if (rc) return rc;
-    PSKV_HIP(hipEventRecord(s->hstage_free, s->stream));
-    s->hstage_pending = true;
   }
-  combine_checks(pieces, all_sorted_in_range, n_outside, all_dense_in_range);
+  combine_checks(pieces, all_sorted_in_range, all_dense_in_range);
   return PSKV_OK;
 }
 
@@ -1486,35 +1372,21 @@ bool frame_views(const std::vector<pskv_batch>& in, size_t vb, std::vector<pskv_
 // into device staging.  Either way nothing waits: the frames stay unmodified
 // until freed, and pskv_host_free holds them until this call's work has run
 // (note_frame_uses).
-int frame_batches(pskv_shard* s, const std::vector<pskv_batch>& in,
-                  const std::vector<pskv_batch>& views, std::vector<pskv_batch>* out,
-                  bool* all_sorted_in_range, uint64_t* n_outside, bool* all_dense_in_range) {
-  size_t bytes = 0;
-  for (auto& b : in) bytes += round16(b.n * 4) + round16(b.n * (size_t)s->vb);
+int frame_batches(pskv_shard* s, const std::vector<pskv_batch>& in, const std::vector<pskv_batch>& views,
+                  std::vector<pskv_batch>* out, bool* all_sorted_in_range, bool* all_dense_in_range) {
   std::vector<Piece> pieces;
   for (size_t j = 0; j < in.size(); ++j) add_pieces(pieces, in[j].keys, nullptr, in[j].n * 4, (int)j);
-  if (bytes <= s->tune_frame_zc_max_bytes) {
+  if (staged_bytes(in, (size_t)s->vb) <= s->tune_frame_zc_max_bytes) {
     *out = views;
   } else {
-    int rc = ensure_dstage(s, bytes);
+    const StageLayout lay = stage_layout(in, (size_t)s->vb, StageOrder::kInterleaved);
+    int rc = ensure_dstage(s, lay.total);
     if (rc) return rc;
-    char* d = static_cast<char*>(s->dstage);
-    size_t off = 0;
-    out->clear();
-    for (const auto& b : in) {
-      pskv_batch db;
-      PSKV_HIP(hipMemcpyAsync(d + off, b.keys, b.n * 4, hipMemcpyHostToDevice, s->stream));
-      db.keys = reinterpret_cast<const uint32_t*>(d + off);
-      off += round16(b.n * 4);
-      PSKV_HIP(hipMemcpyAsync(d + off, b.vals, b.n * (size_t)s->vb, hipMemcpyHostToDevice, s->stream));
-      db.vals = d + off;
-      off += round16(b.n * (size_t)s->vb);
-      db.n = b.n;
-      out->push_back(db);
-    }
+    *out = lay.views(in, static_cast<char*>(s->dstage));
+    PSKV_HIP(dma_batches(s, in, *out));
   }
-  run_pieces(pieces, 0, pieces.size(), [&](Piece& p) { copy_piece(p, s->key_begin, s->range); });
-  combine_checks(pieces, all_sorted_in_range, n_outside, all_dense_in_range);
+  run_copies(s, pieces, 0, pieces.size());
+  combine_checks(pieces, all_sorted_in_range, all_dense_in_range);
   return PSKV_OK;
 }
 
@@ -1688,10 +1560,11 @@ int inline_get(pskv_shard* s, const std::vector<pskv_batch>& v, uint64_t total) 
 //               then k_row_commit: the element whose tag equals its key's stamp
 //               copies its whole row; timed together as PSKV_K_ROW_COMMIT
 //   accumulate  k_row_accumulate
-// Host buffers are staged through the pinned and device staging buffers (keys
-// then rows per batch, 16-byte aligned).  Keys outside the owned range are
-// not stored (pskv.h): a host Add refuses them before anything is queued, the
-// kernels drop them and set kErrRowOutOfRange.
+// Host buffers are staged through the pinned and device staging buffers
+// (stage_keys_first: every batch's keys, then every batch's rows, 16-byte
+// aligned); the row D2H of a Get is one copy and one wait.  Keys outside the
+// owned range are not stored (pskv.h): a host Add refuses them before anything
+// is queued, the kernels drop them and set kErrRowOutOfRange.
 size_t row_bytes(const pskv_shard* s) { return (size_t)s->width * (size_t)s->vb; }
 
 int rows_pieces(pskv_shard* s, const std::vector<pskv_batch>& in, const char* what, std::vector<pskv_batch>* v) {
@@ -1703,71 +1576,25 @@ int rows_pieces(pskv_shard* s, const std::vector<pskv_batch>& in, const char* wh
   return PSKV_OK;
 }
 
-// Host batches -> device staging through pinned staging: keys (and, for an
-// Add, rows) copied in and queued for DMA; a Get's rows get room behind them.
-// `dv`: the device views.  The pinned copy of batch i's rows lies at
-// hstage + (dv[i].vals - dstage).
-int rows_stage(pskv_shard* s, const std::vector<pskv_batch>& v, bool with_rows, std::vector<pskv_batch>* dv,
-               size_t* in_bytes, size_t* total_bytes) {
-  const size_t rb = row_bytes(s);
-  size_t kbytes = 0, vbytes = 0;
-  for (auto& b : v) {
-    kbytes += round16(b.n * 4);
-    vbytes += round16(b.n * rb);
-  }
-  int rc = ensure_hstage(s, kbytes + vbytes);
-  if (rc) return rc;
-  rc = ensure_dstage(s, kbytes + vbytes);
-  if (rc) return rc;
-  char* h = static_cast<char*>(s->hstage);
-  char* d = static_cast<char*>(s->dstage);
-  std::vector<Piece> pieces;
-  *dv = v;
-  size_t off = 0;
-  for (size_t i = 0; i < v.size(); ++i) {
-    add_pieces(pieces, v[i].keys, h + off, v[i].n * 4, -1);
-    (*dv)[i].keys = reinterpret_cast<const uint32_t*>(d + off);
-    off += round16(v[i].n * 4);
-  }
-  for (size_t i = 0; i < v.size(); ++i) {
-    if (with_rows) add_pieces(pieces, v[i].vals, h + off, v[i].n * rb, -1);
-    (*dv)[i].vals = d + off;
-    off += round16(v[i].n * rb);
-  }
-  *in_bytes = with_rows ? off : kbytes;
-  *total_bytes = off;
-  return pipelined_h2d(s, pieces, h, d);
-}
-
 int rows_add_device(pskv_shard* s, const std::vector<pskv_batch>& v) {
   bool vec = row_bytes(s) % 16 == 0 && aligned16(s->dense);
   for (auto& b : v) vec = vec && aligned16(b.vals);
-  for (auto& g : split_groups(v)) {
-    GroupArgs ga;
-    const uint32_t nwg = build_group(v, g.first, g.second, kGeneralChunk, &ga);
-    uint64_t elems = 0;
-    for (size_t i = g.first; i < g.second; ++i) elems += v[i].n;
+  for (const Span& sp : split_groups(v)) {
+    const LaunchGroup g = make_group(v, sp.first, sp.second, kGeneralChunk);
     if (s->mode == PSKV_ACCUMULATE) {
-      LaunchTimer t(s, PSKV_K_ROW_ACCUMULATE, elems);
-      PSKV_HIP(launch_row_accumulate(s->dtype, ga, nwg, s->dview(), s->ovf, row_shape(s->width, s->vb, false),
+      LaunchTimer t(s, PSKV_K_ROW_ACCUMULATE, g.elems);
+      PSKV_HIP(launch_row_accumulate(s->dtype, g.ga, g.nwg, s->dview(), s->ovf, row_shape(s->width, s->vb, false),
                                      s->stream));
       t.done();
       s->n_general++;
       continue;
     }
-    if (!s->owner) {  // 8 B per owned KEY (not per value), on first use
-      const size_t bytes = s->range * sizeof(unsigned long long);
-      if (hipMalloc(&s->owner, bytes) != hipSuccess) {
-        s->owner = nullptr;
-        return fail(PSKV_ENOMEM, "stamp array allocation failed");
-      }
-      PSKV_HIP(hipMemsetAsync(s->owner, 0, bytes, s->stream));
-    }
+    if (int rc = ensure_owner(s)) return rc;
     const uint32_t epoch = next_epoch(s);
-    LaunchTimer t(s, PSKV_K_ROW_COMMIT, elems);
-    PSKV_HIP(launch_general_mark(s->dtype, PSKV_ASSIGN, ga, nwg, s->dview(), s->flag + 1, s->owner, nullptr, epoch,
-                                 s->stream));
-    PSKV_HIP(launch_row_commit(s->vb, ga, nwg, s->dview(), s->owner, s->ovf, epoch,
+    LaunchTimer t(s, PSKV_K_ROW_COMMIT, g.elems);
+    PSKV_HIP(launch_general_mark(s->dtype, PSKV_ASSIGN, g.ga, g.nwg, s->dview(), s->flag + 1, s->owner, nullptr,
+                                 epoch, s->stream));
+    PSKV_HIP(launch_row_commit(s->vb, g.ga, g.nwg, s->dview(), s->owner, s->ovf, epoch,
                                row_shape(s->width, s->vb, vec), s->stream));
     t.done();
     s->n_general += 2;
@@ -1794,12 +1621,25 @@ int rows_add(pskv_shard* s, const std::vector<pskv_batch>& in, int flags) {
                                      " is outside [key_begin, key_end); a row shard stores no out-of-range "
                                      "keys (nothing was applied)");
   }
+  // the call returns before its DMA: the hold stays armed
+  HstageHold hold(s);
   std::vector<pskv_batch> dv;
-  size_t in_bytes = 0, total = 0;
-  rc = rows_stage(s, v, /*with_rows=*/true, &dv, &in_bytes, &total);
-  if (!rc) rc = rows_add_device(s, dv);
-  hold_hstage(s);  // until the queued H2D copies have read the staging
-  return rc;
+  rc = stage_keys_first(s, v, stage_layout(v, row_bytes(s), StageOrder::kKeysFirst), row_bytes(s),
+                        /*with_values=*/true, hold, &dv);
+  return rc ? rc : rows_add_device(s, dv);
+}
+
+int rows_gather(pskv_shard* s, const std::vector<pskv_batch>& dv) {
+  bool vec = row_bytes(s) % 16 == 0 && aligned16(s->dense);
+  for (auto& b : dv) vec = vec && aligned16(b.vals);
+  const RowShape rs = row_shape(s->width, s->vb, vec);
+  for (const Span& sp : split_groups(dv)) {
+    const LaunchGroup g = make_group(dv, sp.first, sp.second, kGeneralChunk);
+    LaunchTimer t(s, PSKV_K_ROW_GATHER, g.elems);
+    PSKV_HIP(launch_row_gather(s->vb, s->tune_nt, g.ga, g.nwg, s->dview(), rs, s->stream));
+    t.done();
+  }
+  return PSKV_OK;
 }
 
 int rows_get(pskv_shard* s, const std::vector<pskv_batch>& in, int flags) {
@@ -1809,51 +1649,24 @@ int rows_get(pskv_shard* s, const std::vector<pskv_batch>& in, int flags) {
   if (v.empty()) return PSKV_OK;
   int rc = use_device(s);
   if (rc) return rc;
-  const bool device = (flags & PSKV_DEVICE) != 0;
-  std::vector<pskv_batch> dv = v;
-  size_t in_bytes = 0, total = 0;
-  if (!device) {
-    rc = rows_stage(s, v, /*with_rows=*/false, &dv, &in_bytes, &total);
-    if (rc) {
-      hold_hstage(s);
-      return rc;
-    }
-  }
-  bool vec = row_bytes(s) % 16 == 0 && aligned16(s->dense);
-  for (auto& b : dv) vec = vec && aligned16(b.vals);
-  const RowShape rs = row_shape(s->width, s->vb, vec);
-  for (auto& g : split_groups(dv)) {
-    GroupArgs ga;
-    const uint32_t nwg = build_group(dv, g.first, g.second, kGeneralChunk, &ga);
-    uint64_t elems = 0;
-    for (size_t i = g.first; i < g.second; ++i) elems += dv[i].n;
-    LaunchTimer t(s, PSKV_K_ROW_GATHER, elems);
-    const hipError_t e = launch_row_gather(s->vb, s->tune_nt, ga, nwg, s->dview(), rs, s->stream);
-    if (e != hipSuccess) {
-      if (!device) hold_hstage(s);
-      PSKV_HIP(e);
-    }
-    t.done();
-  }
-  if (device) return PSKV_OK;
+  if (flags & PSKV_DEVICE) return rows_gather(s, v);
+  HstageHold hold(s);
+  const StageLayout lay = stage_layout(v, row_bytes(s), StageOrder::kKeysFirst);
+  std::vector<pskv_batch> dv;
+  rc = stage_keys_first(s, v, lay, row_bytes(s), /*with_values=*/false, hold, &dv);
+  if (!rc) rc = rows_gather(s, dv);
+  if (rc) return rc;
   // rows: device staging -> pinned staging -> the caller's buffers
   char* h = static_cast<char*>(s->hstage);
   char* d = static_cast<char*>(s->dstage);
-  const hipError_t e =
-      hipMemcpyAsync(h + in_bytes, d + in_bytes, total - in_bytes, hipMemcpyDeviceToHost, s->stream);
-  if (e != hipSuccess) {
-    hold_hstage(s);
-    PSKV_HIP(e);
-  }
-  if (int rc2 = wait_stream(s, s->stream, "shard stream (row Get to host)")) {
-    hold_hstage(s);
-    return rc2;
-  }
+  PSKV_HIP(hipMemcpyAsync(h + lay.key_bytes, d + lay.key_bytes, lay.total - lay.key_bytes, hipMemcpyDeviceToHost,
+                          s->stream));
+  if (int rc2 = wait_stream(s, s->stream, "shard stream (row Get to host)")) return rc2;
+  hold.dismiss();
   std::vector<Piece> pieces;
   for (size_t i = 0; i < v.size(); ++i)
-    add_pieces(pieces, h + (static_cast<const char*>(dv[i].vals) - d), static_cast<char*>(v[i].vals),
-               v[i].n * row_bytes(s), -1);
-  run_pieces(pieces, 0, pieces.size(), [&](Piece& p) { copy_piece(p, s->key_begin, s->range); });
+    add_pieces(pieces, h + lay.at[i].vals, static_cast<char*>(v[i].vals), v[i].n * row_bytes(s), -1);
+  run_copies(s, pieces, 0, pieces.size());
   return PSKV_OK;
 }
 
@@ -1885,22 +1698,19 @@ int add_impl(pskv_shard* s, const std::vector<pskv_batch>& in, int flags) {
   auto run = [&]() -> int {
     int rc = PSKV_OK;
     if (!device) {
-      std::vector<pskv_batch> staged, views;
-      uint64_t outside = 0;
-      if ((flags & PSKV_HOST_FRAME) && frame_views(v, (size_t)s->vb, &views)) {
-        framed = v;
-        rc = frame_batches(s, v, views, &staged, &host_verified, &outside, &host_dense);
-      } else {
-        rc = stage_host_batches(s, v, &staged, &host_verified, &outside, &host_dense);
-      }
-      if (rc) return rc;
       // (out-of-range keys need no host step: the single workgroup that
       // inserts them reserves room on the device, ovf_reserve)
-      (void)outside;
+      std::vector<pskv_batch> staged, views;
+      if ((flags & PSKV_HOST_FRAME) && frame_views(v, (size_t)s->vb, &views)) {
+        framed = v;
+        rc = frame_batches(s, v, views, &staged, &host_verified, &host_dense);
+      } else {
+        rc = stage_host_batches(s, v, &staged, &host_verified, &host_dense);
+      }
+      if (rc) return rc;
       v.swap(staged);
     }
-    bool vec = true;
-    for (auto& b : v) vec &= aligned16(b.keys) & aligned16(b.vals);
+    const bool vec = all_aligned16(v);
     for (auto& g : split_groups(v)) {
       // a replay held by the previous group goes before this group's launches
       if ((rc = flush_replay(s))) return rc;
@@ -1915,7 +1725,7 @@ int add_impl(pskv_shard* s, const std::vector<pskv_batch>& in, int flags) {
           // K5 (no global atomics) measured faster than K4a (LDS sums + one
           // atomic add per distinct key per chunk) on cfg 3: 322 vs 380 us per
           // 8M Zipf keys; PSKV_GENERAL=stamps selects K4a
-          rc = general_add(s, v, g.first, g.second, epoch, nullptr);
+          rc = general_add(s, v, g.first, g.second, epoch);
         }
       } else if (!device && host_verified) {
         // the CPU proved the batches sorted and in range while staging them.
@@ -1928,7 +1738,7 @@ int add_impl(pskv_shard* s, const std::vector<pskv_batch>& in, int flags) {
       } else if (device && (flags & PSKV_SORTED_HINT)) {
         rc = sorted_add(s, v, g.first, g.second, vec, epoch, /*repair=*/true, /*maybe_windows=*/true);
       } else {
-        rc = general_add(s, v, g.first, g.second, epoch, nullptr);
+        rc = general_add(s, v, g.first, g.second, epoch);
       }
       if (rc) return rc;
     }
@@ -1947,66 +1757,57 @@ int add_impl(pskv_shard* s, const std::vector<pskv_batch>& in, int flags) {
   return rc;
 }
 
+// K1 over one launch group, batches [b, e) of `v`.  fold_replay: a replay the
+// Add of pskv_add_get_grouped held rides on this launch (K1r); it stays held
+// (for add_get_impl's trailing K4r) unless the launch is queued.
+int gather_group(pskv_shard* s, const std::vector<pskv_batch>& v, size_t b, size_t e, bool vec, bool fold_replay) {
+  int gu = 0;
+  const LaunchGroup g = make_group_by(v, b, e, [&](uint64_t elems) {
+    gu = gather_unroll(s, elems);
+    return (uint64_t)stream_chunk(gu);
+  });
+  LaunchTimer t(s, PSKV_K_GATHER, g.elems);
+  if (fold_replay && s->pend_replay && g.nwg > 0) {
+    PSKV_HIP(launch_gather_replay(s->vb, vec, gu, s->tune_nt, g.ga, g.nwg, s->dview(), s->ovf, s->pend_rg,
+                                  s->flag, s->pend_epoch, s->flag + 16, s->stream));
+    s->pend_replay = false;
+  } else {
+    PSKV_HIP(launch_gather(s->vb, vec, gu, s->tune_nt, g.ga, g.nwg, s->dview(), s->ovf, s->stream));
+  }
+  t.done();
+  return PSKV_OK;
+}
+
+// K1 over every launch group of `v`: the K1 loop of every Get path.
+int gather_all(pskv_shard* s, const std::vector<pskv_batch>& v, bool vec, bool fold_replay = false) {
+  for (const Span& g : split_groups(v))
+    if (int rc = gather_group(s, v, g.first, g.second, vec, fold_replay)) return rc;
+  return PSKV_OK;
+}
+
+// Get in place, page-locked keys and outputs (frames, PSKV_HOST_FRAME, or any
+// other pinned memory): K1 reads the keys from and writes the values into the
+// caller's buffers, no copy on either side.
+int zero_copy_get_views(pskv_shard* s, const std::vector<pskv_batch>& hv) {
+  if (int rc = gather_all(s, hv, all_aligned16(hv))) return rc;
+  return wait_stream(s, s->stream, "shard stream (Get into page-locked memory)");
+}
+
 // Zero-copy host Get of a medium batch: the keys are copied into pinned staging
 // by the calling thread, K1 reads them from there and writes the values into
 // pinned staging over PCIe (no DMA engine on either side), and the calling
 // thread copies the values out.  The staging is default (non-coherent) pinned
 // memory: the kernel's writes are visible once the stream is synchronised.
-// Frames (PSKV_HOST_FRAME) skip both copies: K1 reads the keys from and
-// writes the values into the caller's frames.
-int zero_copy_get_views(pskv_shard* s, const std::vector<pskv_batch>& hv) {
-  bool vec = true;
-  for (auto& b : hv) vec &= aligned16(b.keys) & aligned16(b.vals);
-  for (auto& g : split_groups(hv)) {
-    GroupArgs ga;
-    uint64_t elems = 0;
-    for (size_t i = g.first; i < g.second; ++i) elems += hv[i].n;
-    const int gu = gather_unroll(s, elems);
-    const uint32_t nwg = build_group(hv, g.first, g.second, stream_chunk(gu), &ga);
-    LaunchTimer t(s, PSKV_K_GATHER, elems);
-    PSKV_HIP(launch_gather(s->vb, vec, gu, s->tune_nt, ga, nwg, s->dview(), s->ovf, s->stream));
-    t.done();
-  }
-  if (int rc = wait_stream(s, s->stream, "shard stream (Get into page-locked memory)")) return rc;
-  return PSKV_OK;
-}
-
-int zero_copy_get(pskv_shard* s, const std::vector<pskv_batch>& v, bool vec) {
-  size_t kbytes = 0, obytes = 0;
-  for (const auto& b : v) {
-    kbytes += round16(b.n * 4);
-    obytes += round16(b.n * (size_t)s->vb);
-  }
-  int rc = ensure_hstage(s, kbytes + obytes);
-  if (rc) return rc;
-  char* h = static_cast<char*>(s->hstage);
-  std::vector<pskv_batch> hv = v;
-  size_t ko = 0, oo = kbytes;
-  for (size_t i = 0; i < v.size(); ++i) {
-    std::memcpy(h + ko, v[i].keys, v[i].n * 4);
-    hv[i].keys = reinterpret_cast<const uint32_t*>(h + ko);
-    hv[i].vals = h + oo;
-    ko += round16(v[i].n * 4);
-    oo += round16(v[i].n * (size_t)s->vb);
-  }
-  for (auto& g : split_groups(hv)) {
-    GroupArgs ga;
-    uint64_t elems = 0;
-    for (size_t i = g.first; i < g.second; ++i) elems += hv[i].n;
-    const int gu = gather_unroll(s, elems);
-    const uint32_t nwg = build_group(hv, g.first, g.second, stream_chunk(gu), &ga);
-    LaunchTimer t(s, PSKV_K_GATHER, elems);
-    const hipError_t e = launch_gather(s->vb, vec, gu, s->tune_nt, ga, nwg, s->dview(), s->ovf, s->stream);
-    if (e != hipSuccess) {
-      hold_hstage(s);  // earlier groups' K1 still read / write the staging
-      PSKV_HIP(e);
-    }
-    t.done();
-  }
-  if (int rc = wait_stream(s, s->stream, "shard stream (zero-copy Get)")) {
-    hold_hstage(s);  // its K1 may still write into the staging
-    return rc;
-  }
+int zero_copy_get(pskv_shard* s, const std::vector<pskv_batch>& v) {
+  const StageLayout lay = stage_layout(v, (size_t)s->vb, StageOrder::kKeysFirst);
+  if (int rc = ensure_hstage(s, lay.total)) return rc;
+  const std::vector<pskv_batch> hv = lay.views(v, static_cast<char*>(s->hstage));
+  for (size_t i = 0; i < v.size(); ++i) std::memcpy(const_cast<uint32_t*>(hv[i].keys), v[i].keys, v[i].n * 4);
+  HstageHold hold(s);
+  hold.arm();  // K1 reads the keys from and writes the values into the staging
+  if (int rc = gather_all(s, hv, /*vec=*/true)) return rc;
+  if (int rc = wait_stream(s, s->stream, "shard stream (zero-copy Get)")) return rc;
+  hold.dismiss();
   for (size_t i = 0; i < v.size(); ++i) std::memcpy(v[i].vals, hv[i].vals, v[i].n * (size_t)s->vb);
   return PSKV_OK;
 }
@@ -2019,40 +1820,16 @@ int zero_copy_get(pskv_shard* s, const std::vector<pskv_batch>& v, bool vec) {
 // two directions use different DMA engines).  The call returns when every
 // value has arrived.
 int pinned_get(pskv_shard* s, const std::vector<pskv_batch>& v) {
-  size_t bytes = 0;
-  for (auto& b : v) bytes += round16(b.n * 4) + round16(b.n * (size_t)s->vb);
-  int rc = ensure_dstage(s, bytes);
+  const StageLayout lay = stage_layout(v, (size_t)s->vb, StageOrder::kInterleaved);
+  int rc = ensure_dstage(s, lay.total);
   if (rc) return rc;
   if (!s->out_stream) {
     PSKV_HIP(hipStreamCreateWithFlags(&s->out_stream, hipStreamNonBlocking));
     g_queues.add_stream(s->device, 1);
   }
-  std::vector<pskv_batch> dv = v;
-  char* d = static_cast<char*>(s->dstage);
-  size_t off = 0;
-  bool vec = true;
-  for (size_t i = 0; i < v.size(); ++i) {
-    dv[i].keys = reinterpret_cast<const uint32_t*>(d + off);
-    off += round16(v[i].n * 4);
-    dv[i].vals = d + off;
-    off += round16(v[i].n * (size_t)s->vb);
-    vec &= aligned16(dv[i].keys) & aligned16(dv[i].vals);
-  }
-  // windows [first batch, end batch): >= kWindowBytes of keys, <= kMaxBatches
-  // batches, < 2^32 elements (split_groups' limits for one launch)
-  std::vector<std::pair<size_t, size_t>> wins;
-  for (size_t i = 0; i < v.size();) {
-    size_t j = i, kb = 0;
-    uint64_t elems = 0;
-    while (j < v.size() && (j == i || (kb < kWindowBytes && j - i < (size_t)kMaxBatches &&
-                                       elems + v[j].n < (1ull << 32)))) {
-      kb += v[j].n * 4;
-      elems += v[j].n;
-      ++j;
-    }
-    wins.emplace_back(i, j);
-    i = j;
-  }
+  const std::vector<pskv_batch> dv = lay.views(v, static_cast<char*>(s->dstage));
+  const bool vec = all_aligned16(dv);
+  const std::vector<Span> wins = batch_windows(v);  // each one launch group
   while (s->out_events.size() < wins.size()) {
     hipEvent_t e = nullptr;
     PSKV_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -2063,15 +1840,7 @@ int pinned_get(pskv_shard* s, const std::vector<pskv_batch>& v) {
     for (size_t i = b; i < e; ++i)
       PSKV_HIP(hipMemcpyAsync(const_cast<uint32_t*>(dv[i].keys), v[i].keys, v[i].n * 4, hipMemcpyHostToDevice,
                               s->stream));
-    GroupArgs ga;
-    uint64_t elems = 0;
-    for (size_t i = b; i < e; ++i) elems += dv[i].n;
-    const int gu = gather_unroll(s, elems);
-    const uint32_t nwg = build_group(dv, b, e, stream_chunk(gu), &ga);
-    LaunchTimer t(s, PSKV_K_GATHER, elems);
-    PSKV_HIP(launch_gather(s->vb, vec, gu, s->tune_nt, ga, nwg, s->dview(),
-                           s->ovf, s->stream));
-    t.done();
+    if ((rc = gather_group(s, dv, b, e, vec, /*fold_replay=*/false))) return rc;
     PSKV_HIP(hipEventRecord(s->out_events[w], s->stream));
     PSKV_HIP(hipStreamWaitEvent(s->out_stream, s->out_events[w], 0));
     for (size_t i = b; i < e; ++i)
@@ -2079,11 +1848,50 @@ int pinned_get(pskv_shard* s, const std::vector<pskv_batch>& v) {
                               s->out_stream));
   }
   // the stage is free again once the out stream is done; both streams drained
-  if (int rc = wait_stream(s, s->out_stream, "D2H output stream (page-locked Get)")) return rc;
-  if (int rc = wait_stream(s, s->stream, "shard stream (page-locked Get)")) return rc;
+  if ((rc = wait_stream(s, s->out_stream, "D2H output stream (page-locked Get)"))) return rc;
+  return wait_stream(s, s->stream, "shard stream (page-locked Get)");
+}
+
+// Pageable host Get through both stagings: keys -> pinned -> device
+// (pipelined), K1, then the values D2H into the pinned staging behind the keys
+// window by window; the pool copies window w out to the caller while window
+// w+1 is still in flight.
+int staged_get(pskv_shard* s, const std::vector<pskv_batch>& v) {
+  HstageHold hold(s);
+  const StageLayout lay = stage_layout(v, (size_t)s->vb, StageOrder::kKeysFirst);
+  std::vector<pskv_batch> dv;
+  int rc = stage_keys_first(s, v, lay, (size_t)s->vb, /*with_values=*/false, hold, &dv);
+  if (!rc) rc = gather_all(s, dv, all_aligned16(dv));
+  if (rc) return rc;
+  char* h = static_cast<char*>(s->hstage);
+  char* d = static_cast<char*>(s->dstage);
+  std::vector<Piece> pieces;  // pinned -> caller
+  for (size_t i = 0; i < v.size(); ++i)
+    add_pieces(pieces, h + lay.at[i].vals, static_cast<char*>(v[i].vals), v[i].n * (size_t)s->vb, -1);
+  const std::vector<Span> wins = piece_windows(pieces);
+  while (s->win_events.size() < wins.size()) {
+    hipEvent_t e = nullptr;
+    PSKV_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    s->win_events.push_back(e);
+  }
+  for (size_t w = 0; w < wins.size(); ++w) {
+    const char* lo = pieces[wins[w].first].src;
+    const char* hi = pieces[wins[w].second - 1].src + pieces[wins[w].second - 1].bytes;
+    PSKV_HIP(hipMemcpyAsync(const_cast<char*>(lo), d + (lo - h), (size_t)(hi - lo), hipMemcpyDeviceToHost,
+                            s->stream));
+    PSKV_HIP(hipEventRecord(s->win_events[w], s->stream));
+  }
+  for (size_t w = 0; w < wins.size(); ++w) {
+    if ((rc = wait_event(s, s->win_events[w], "D2H window event (Get to host)", s->win_events[w]))) return rc;
+    run_copies(s, pieces, wins[w].first, wins[w].second);
+  }
+  hold.dismiss();
   return PSKV_OK;
 }
 
+// The path choice of a Get.  Host calls, in this order: inline (K8 / K9),
+// in-place zero copy, staged zero copy, DMA (page-locked, or pageable and
+// large), staged windowed.
 int get_impl(pskv_shard* s, const std::vector<pskv_batch>& in, int flags) {
   if (s->width > 1) return rows_get(s, in, flags);
   std::vector<pskv_batch> v;
@@ -2104,135 +1912,19 @@ int get_impl(pskv_shard* s, const std::vector<pskv_batch>& in, int flags) {
   }
   rc = srv_stop(s);
   if (rc) return rc;
-  if (!device) {  // page-locked keys and outputs (frames or not): zero copy in place
-    size_t bytes = 0;
-    for (auto& b : v) bytes += round16(b.n * 4) + round16(b.n * (size_t)s->vb);
-    std::vector<pskv_batch> views;
-    if (bytes <= s->tune_frame_zc_max_bytes &&
-        (((flags & PSKV_HOST_FRAME) && frame_views(v, (size_t)s->vb, &views)) ||
-         pinned_views(v, (size_t)s->vb, &views)))
-      return zero_copy_get_views(s, views);
-  }
-  std::vector<pskv_batch> dv = v;
-  size_t out_off = 0;
-  bool pinned = !device;
+  if (device) return gather_all(s, v, all_aligned16(v), /*fold_replay=*/true);
+  const size_t bytes = staged_bytes(v, (size_t)s->vb);
+  std::vector<pskv_batch> views;
+  if (bytes <= s->tune_frame_zc_max_bytes &&
+      (((flags & PSKV_HOST_FRAME) && frame_views(v, (size_t)s->vb, &views)) ||
+       pinned_views(v, (size_t)s->vb, &views)))
+    return zero_copy_get_views(s, views);
+  bool pinned = true;
   for (const auto& b : v) pinned = pinned && is_pinned(b.keys) && is_pinned(b.vals);
-  if (!device && !pinned && s->tune_zc_max_bytes) {  // medium pageable Get: zero copy
-    size_t bytes = 0;
-    for (auto& b : v) bytes += round16(b.n * 4) + round16(b.n * (size_t)s->vb);
-    if (bytes <= s->tune_zc_max_bytes) return zero_copy_get(s, v, true);
-  }
-  if (!device && !pinned && s->tune_pageable_dma) {  // pageable: direct DMA only when large
-    size_t bytes = 0;
-    for (auto& b : v) bytes += round16(b.n * 4) + round16(b.n * (size_t)s->vb);
-    pinned = bytes >= s->tune_dma_min_bytes_get;
-  }
-  if (pinned) return pinned_get(s, v);
-  if (!device) {
-    // keys -> pinned -> device (pipelined); outputs land after the keys in the stage
-    size_t kbytes = 0, obytes = 0;
-    for (auto& b : v) {
-      kbytes += round16(b.n * 4);
-      obytes += round16(b.n * (size_t)s->vb);
-    }
-    rc = ensure_hstage(s, kbytes + obytes);
-    if (rc) return rc;
-    rc = ensure_dstage(s, kbytes + obytes);
-    if (rc) return rc;
-    char* h = static_cast<char*>(s->hstage);
-    char* d = static_cast<char*>(s->dstage);
-    std::vector<Piece> pieces;
-    size_t off = 0;
-    for (size_t i = 0; i < v.size(); ++i) {
-      add_pieces(pieces, v[i].keys, h + off, v[i].n * 4, -1);
-      dv[i].keys = reinterpret_cast<const uint32_t*>(d + off);
-      off += round16(v[i].n * 4);
-    }
-    rc = pipelined_h2d(s, pieces, h, d);
-    if (rc) return rc;
-    out_off = off;
-    for (size_t i = 0; i < v.size(); ++i) {
-      dv[i].vals = d + off;
-      off += round16(v[i].n * (size_t)s->vb);
-    }
-  }
-  bool vec = true;
-  for (auto& b : dv) vec &= aligned16(b.keys) & aligned16(b.vals);
-  for (auto& g : split_groups(dv)) {
-    GroupArgs ga;
-    uint64_t elems = 0;
-    for (size_t i = g.first; i < g.second; ++i) elems += dv[i].n;
-    const int gu = gather_unroll(s, elems);
-    const uint32_t nwg = build_group(dv, g.first, g.second, stream_chunk(gu), &ga);
-    LaunchTimer t(s, PSKV_K_GATHER, elems);
-    hipError_t e;
-    if (s->pend_replay && nwg > 0) {
-      // the Add's held replay rides on this first K1 (pskv_add_get_grouped);
-      // it stays held (for add_get_impl's trailing K4r) unless this launch is queued
-      e = launch_gather_replay(s->vb, vec, gu, s->tune_nt, ga, nwg, s->dview(), s->ovf, s->pend_rg,
-                               s->flag, s->pend_epoch, s->flag + 16, s->stream);
-      if (e == hipSuccess) s->pend_replay = false;
-    } else {
-      e = launch_gather(s->vb, vec, gu, s->tune_nt, ga, nwg, s->dview(), s->ovf, s->stream);
-    }
-    if (e != hipSuccess) {
-      if (!device) hold_hstage(s);  // the keys' H2D from the staging is queued
-      PSKV_HIP(e);
-    }
-    t.done();
-  }
-  if (!device) {
-    // D2H window by window; the pool copies window w out to the caller while
-    // window w+1 is still in flight
-    char* h = static_cast<char*>(s->hstage);
-    char* d = static_cast<char*>(s->dstage);
-    std::vector<Piece> pieces;  // pinned -> caller
-    size_t off = out_off;
-    for (auto& b : v) {
-      Piece p{};
-      const size_t nb = b.n * (size_t)s->vb;
-      for (size_t o = 0; o < nb; o += kPieceBytes) {
-        p.src = h + off + o;
-        p.dst = static_cast<char*>(b.vals) + o;
-        p.bytes = std::min(kPieceBytes, nb - o);
-        p.key_batch = -1;
-        pieces.push_back(p);
-      }
-      off += round16(nb);
-    }
-    std::vector<std::pair<size_t, size_t>> wins;  // [first piece, end piece)
-    for (size_t i = 0; i < pieces.size();) {
-      size_t j = i, win = 0;
-      while (j < pieces.size() && (win < kWindowBytes || j == i)) win += pieces[j++].bytes;
-      wins.emplace_back(i, j);
-      i = j;
-    }
-    while (s->win_events.size() < wins.size()) {
-      hipEvent_t e = nullptr;
-      PSKV_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-      s->win_events.push_back(e);
-    }
-    for (size_t w = 0; w < wins.size(); ++w) {
-      const char* lo = pieces[wins[w].first].src;
-      const char* hi = pieces[wins[w].second - 1].src + pieces[wins[w].second - 1].bytes;
-      hipError_t e = hipMemcpyAsync(const_cast<char*>(lo), d + (lo - h), (size_t)(hi - lo),
-                                    hipMemcpyDeviceToHost, s->stream);
-      if (e == hipSuccess) e = hipEventRecord(s->win_events[w], s->stream);
-      if (e != hipSuccess) {
-        hold_hstage(s);  // earlier windows' D2H still write into the staging
-        PSKV_HIP(e);
-      }
-    }
-    for (size_t w = 0; w < wins.size(); ++w) {
-      if (int rc = wait_event(s, s->win_events[w], "D2H window event (Get to host)", s->win_events[w])) {
-        hold_hstage(s);  // the queued D2H copies still write into the staging
-        return rc;
-      }
-      run_pieces(pieces, wins[w].first, wins[w].second,
-                 [&](Piece& p) { copy_piece(p, s->key_begin, s->range); });
-    }
-  }
-  return PSKV_OK;
+  if (!pinned && s->tune_zc_max_bytes && bytes <= s->tune_zc_max_bytes) return zero_copy_get(s, v);
+  // pageable: direct DMA only when large
+  if (!pinned && s->tune_pageable_dma) pinned = bytes >= s->tune_dma_min_bytes_get;
+  return pinned ? pinned_get(s, v) : staged_get(s, v);
 }
 
 // ------------------------------------------------------------ Add then Get

@@ -273,3 +273,21 @@ def test_queue_accounting_per_device(tmp_path):
     r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
     assert r.returncode == 0, r.stdout + r.stderr
     assert " 0 failed" in r.stdout
+
+
+def test_host_plan(tmp_path):
+    """The host planner (parameter_server_amd/csrc/pskv_plan.h):
+    pieces, launch groups, staging layouts, DMA / copy windows, the key check
+    and K5's bucket rule, as a host-only C++ program built with g++ here."""
+    import subprocess
+
+    src = os.path.join(ROOT, "tests", "cpp", "host_plan_test.cpp")
+    exe = str(tmp_path / "host_plan_test")
+    r = subprocess.run(["g++", "-O1", "-std=c++17", "-Wall", "-Werror",
+                        "-I", os.path.join(ROOT, "include"),
+                        "-I", os.path.join(ROOT, "parameter_server_amd", "csrc"), src, "-o", exe],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert " 0 failed" in r.stdout

@@ -1423,6 +1423,124 @@ def test_pinned_host_buffers_direct_dma(cuda, oracle_mod, mode, pageable_path, p
         assert_bits_equal(outs["pinned"], ref.get(q), "pinned vs oracle")
 
 
+def _host_buffers(ps, kind, arrays):
+    """Copies of 4-byte-element `arrays` packed back to back in host memory of
+    `kind`: "pageable", "pinned" (one page-locked allocation) or "frame" (one
+    HostFrame).  Returns (views, whatever keeps the memory alive)."""
+    import torch
+
+    total = max(1, sum(a.size for a in arrays))
+    if kind == "pageable":
+        buf, keep = np.empty(total, np.uint32), None
+    elif kind == "pinned":
+        keep = torch.empty(total, dtype=torch.int32).pin_memory()
+        buf = keep.numpy().view(np.uint32)
+    else:
+        keep = ps.HostFrame(4 * total)
+        buf = keep.array(np.uint32, total)
+    views, off = [], 0
+    for a in arrays:
+        v = buf[off:off + a.size].view(a.dtype).reshape(a.shape)
+        v[...] = a
+        views.append(v)
+        off += a.size
+    return views, keep
+
+
+def _column_oracle(oracle_mod, width, adds, q):
+    """Assign oracle of a shard of `width` float32 values per key: one
+    MapStorageRef per column."""
+    want = np.empty((q.size, width), np.float32)
+    for c in range(width):
+        ref = oracle_mod.MapStorageRef(np.float32)
+        for k, v in adds:
+            ref.add(k, np.ascontiguousarray(v.reshape(k.size, width)[:, c]))
+        want[:, c] = ref.get(q)
+    return want if width > 1 else want[:, 0]
+
+
+# every host Add staging and host Get path of pskv_shard.cpp, by the options
+# and the kind of caller memory that select it: (Add staging - Get path,
+# options, Add memory, Get memory, width)
+HOST_PATHS = [
+    ("inline-inline", {}, "pageable", "pageable", 1),
+    ("copied-zc_staged", {"INLINE": 0}, "pageable", "pageable", 1),
+    ("copied-staged", {"INLINE": 0, "ZC_MAX_BYTES": 0, "PAGEABLE_DMA": 0}, "pageable", "pageable", 1),
+    ("copied-zc_in_place", {"INLINE": 0}, "pinned", "pinned", 1),
+    ("dma-dma", {"INLINE": 0, "DMA_MIN_BYTES_PINNED": 0, "FRAME_ZC_MAX_BYTES": 0}, "pinned", "pinned", 1),
+    ("frames-frames", {"INLINE": 0}, "frame", "frame", 1),
+    ("frames_dma-frames_dma", {"INLINE": 0, "FRAME_ZC_MAX_BYTES": 0}, "frame", "frame", 1),
+    ("rows", {"INLINE": 0}, "pageable", "pageable", 3),
+]
+
+
+@pytest.mark.parametrize("path,opts,add_mem,get_mem,width", HOST_PATHS, ids=[p[0] for p in HOST_PATHS])
+def test_host_paths_with_more_than_64_batches(cuda, oracle_mod, path, opts, add_mem, get_mem, width):
+    """65 batches of 3 keys in one grouped host Add and one grouped host Get --
+    one more than a launch group holds, so every path cuts the call into two
+    launches -- through each host Add staging (copied, direct DMA, frames in
+    place, frames DMA'd) and each host Get path (inline, in-place zero copy,
+    staged zero copy, DMA, staged windowed), and a row shard's staged paths.
+    Bit-exact against the oracle; the launch counts show the two groups."""
+    import parameter_server_amd as ps
+    from parameter_server_amd import _lib
+
+    rng = np.random.default_rng(65)
+    kb, ke = 1000, 1000 + 4096
+    lo, hi = (kb, ke) if width > 1 else (kb - 20, ke + 20)  # a row shard stores no out-of-range keys
+    ks = [rng.integers(lo, hi, size=3).astype(np.uint32) for _ in range(65)]
+    ks[7][:] = ks[3]  # a later batch rewrites an earlier one's keys
+    vs = [rng.standard_normal(3 * width).astype(np.float32) for _ in ks]
+    qs = [rng.integers(lo, hi, size=3).astype(np.uint32) for _ in range(65)]
+    qs[1][:] = ks[7]
+    q = np.concatenate(qs)
+    want = _column_oracle(oracle_mod, width, list(zip(ks, vs)), q)
+    with ps.Shard(kb, ke, np.float32, width=width, overflow_slots=1 << 10, options=opts) as sh:
+        sh.set_timing(True)
+        abufs, akeep = _host_buffers(ps, add_mem, ks + vs)
+        sh.add_grouped(list(zip(abufs[:65], abufs[65:])), frame=add_mem == "frame")
+        gbufs, gkeep = _host_buffers(ps, get_mem, qs + [np.zeros(3 * width, np.float32) for _ in qs])
+        sh.get_grouped(list(zip(gbufs[:65], gbufs[65:])), frame=get_mem == "frame")
+        got = np.concatenate(gbufs[65:]).reshape(want.shape)
+        launches = {k: sh.kernel_time(k)["launches"] for k in range(_lib.PSKV_K_COUNT)}
+        sh.sync()
+        for f in (akeep, gkeep):
+            if isinstance(f, ps.HostFrame):
+                f.free()
+    assert_bits_equal(got, want, path)
+    if path == "inline-inline":  # 195 keys: one K8 message each way, no group
+        assert launches[_lib.PSKV_K_INLINE_ADD] == 1 and launches[_lib.PSKV_K_INLINE_GET] == 1
+        assert launches[_lib.PSKV_K_GATHER] == 0 and launches[_lib.PSKV_K_RADIX] == 0
+    elif width > 1:
+        assert launches[_lib.PSKV_K_ROW_COMMIT] == 2 and launches[_lib.PSKV_K_ROW_GATHER] == 2
+    else:
+        assert launches[_lib.PSKV_K_RADIX] == 2 and launches[_lib.PSKV_K_GATHER] == 2
+        assert launches[_lib.PSKV_K_INLINE_ADD] == 0 and launches[_lib.PSKV_K_INLINE_GET] == 0
+
+
+@pytest.mark.parametrize("width", [1, 3])
+def test_staged_host_get_just_over_two_copy_windows(cuda, oracle_mod, width):
+    """One pageable host Get through both stagings whose values are two 8 MiB
+    copy windows and one key more (float32: 4 Mi + 1 keys, so the keys' H2D is
+    three windows as well; a row shard of width 3: its D2H is one copy)."""
+    import parameter_server_amd as ps
+
+    rng = np.random.default_rng(8 << 20)
+    kb, ke = 1000, 1000 + 4096
+    n = -(-(16 << 20) // (4 * width)) + 1
+    k = rng.integers(kb, ke, size=3000).astype(np.uint32)
+    v = rng.standard_normal(3000 * width).astype(np.float32)
+    lo, hi = (kb, ke) if width > 1 else (kb - 50, ke + 50)
+    q = rng.integers(lo, hi, size=n).astype(np.uint32)
+    want = _column_oracle(oracle_mod, width, [(k, v)], q)
+    with ps.Shard(kb, ke, np.float32, width=width,
+                  options={"INLINE": 0, "ZC_MAX_BYTES": 0, "PAGEABLE_DMA": 0}) as sh:
+        sh.add(k, v)
+        got = sh.get(q)
+    assert got.nbytes >= 2 * (8 << 20) + 4 * width
+    assert_bits_equal(got, want, f"width {width}")
+
+
 # ---------------------------------------------------------------- K8 inline
 # Small host messages (<= 256 keys per Add, <= 512 per Get) travel inside the
 # kernel arguments.  They are the reference's live traffic shape (one LR

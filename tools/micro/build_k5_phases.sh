@@ -12,8 +12,13 @@ C=$R/parameter_server_amd/csrc
 O=${1:-$R/tools/micro}
 shift || true
 mkdir -p "$O"
+# the library's sources: parameter_server_amd/build.py's LIB_SOURCES
+srcs=()
+for f in $(python3 -c "import runpy; print(' '.join(runpy.run_path('$R/parameter_server_amd/build.py')['LIB_SOURCES']))"); do
+  srcs+=("$C/$f")
+done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -DPSKV_K5_STAMPS "$@" \
-  -I "$R/include" -I "$C" "$C/pskv_kernels.hip" "$C/pskv_shard.cpp" "$C/pskv_frames.cpp" \
+  -I "$R/include" -I "$C" "${srcs[@]}" \
   -o "$O/libpskv_diag.so"
 g++ -O2 -std=c++11 -I "$R/include" "$R/tools/micro/k5_phases.cpp" -L "$O" -lpskv_diag \
   '-Wl,-rpath,$ORIGIN' -o "$O/k5_phases"
