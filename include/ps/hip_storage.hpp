@@ -25,6 +25,11 @@
 // `width` values; SubAdd takes keys.size() * width values (row-major), SubGet
 // replies with as many.  Such a storage holds only the keys of its range
 // (pskv.h), so construct it with the range the server owns.
+// Optimizer (last constructor argument, pskv_shard_set_optimizer): the storage
+// applies optimizer steps.  SubAdd then carries GRADIENTS and is one step
+// (pskv_apply); AddGrouped, the BSP model's flush, is ONE step over the summed
+// gradients of all its messages (pskv_apply_grouped).  Float Val only; keys
+// outside the range abort the call (pskv.h "Optimizer steps").
 #pragma once
 
 #include <cstdint>
@@ -70,11 +75,13 @@ class HipStorage : public AbstractStorage {
  public:
   // No arguments = the reference's construction: whole key space, assign.
   explicit HipStorage(int device = 0, uint32_t key_begin = 0, uint64_t key_end = 1ull << 32,
-                      int mode = PSKV_ASSIGN, uint64_t overflow_slots = 0, uint32_t width = 1)
-      : width_(width) {
+                      int mode = PSKV_ASSIGN, uint64_t overflow_slots = 0, uint32_t width = 1,
+                      const pskv_optimizer* optimizer = nullptr)
+      : width_(width), stepping_(optimizer != nullptr && optimizer->kind != PSKV_OPT_NONE) {
     pskv_check(pskv_shard_create_rows(device, key_begin, key_end, PskvDtype<Val>::value, mode, width,
                                       overflow_slots, &shard_),
                "pskv_shard_create");
+    if (optimizer) pskv_check(pskv_shard_set_optimizer(shard_, optimizer), "pskv_shard_set_optimizer");
   }
   ~HipStorage() override { pskv_shard_destroy(shard_); }
   HipStorage(const HipStorage&) = delete;
@@ -87,6 +94,12 @@ class HipStorage : public AbstractStorage {
       std::fprintf(stderr, "Check failed: typed_keys.size() * width == typed_vals.size() (%zu * %u vs %zu)\n",
                    (size_t)typed_keys.size(), (unsigned)width_, (size_t)typed_vals.size());
       std::abort();
+    }
+    if (stepping_) {
+      pskv_check(pskv_apply(shard_, typed_keys.data(), typed_vals.data(), typed_keys.size(),
+                            PSKV_HOST | PSKV_HOST_FRAME),
+                 "pskv_apply");
+      return;
     }
     pskv_check(pskv_add(shard_, typed_keys.data(), typed_vals.data(), typed_keys.size(),
                         PSKV_HOST | PSKV_HOST_FRAME),
@@ -112,6 +125,11 @@ class HipStorage : public AbstractStorage {
         std::abort();
       }
       batches.push_back(pskv_batch{keep_k.back().data(), keep_v.back().data(), keep_k.back().size()});
+    }
+    if (stepping_) {
+      pskv_check(pskv_apply_grouped(shard_, batches.data(), batches.size(), PSKV_HOST | PSKV_HOST_FRAME),
+                 "pskv_apply_grouped");
+      return;
     }
     pskv_check(pskv_add_grouped(shard_, batches.data(), batches.size(), PSKV_HOST | PSKV_HOST_FRAME),
                "pskv_add_grouped");
@@ -139,6 +157,7 @@ class HipStorage : public AbstractStorage {
  private:
   pskv_shard* shard_ = nullptr;
   uint32_t width_ = 1;
+  bool stepping_ = false;  // an optimizer is set: Adds are optimizer steps
 };
 
 }  // namespace csci5570

@@ -61,6 +61,43 @@
  * next pskv_sync returns PSKV_ESTATE ("row shard ... out-of-range"; pskv_clear
  * resets it); a Get of such a key returns a row of zeros.
  *
+ * Optimizer steps (pskv_shard_set_optimizer, pskv_apply): a
+ * shard may carry an optimizer, and workers then push GRADIENTS.  pskv_apply
+ * and pskv_apply_grouped take (key, gradient-row) batches shaped exactly like
+ * an Add's, and ONE CALL IS ONE OPTIMIZER STEP:
+ *   1. for every distinct in-range key k of the call (over all batches of a
+ *      grouped call) g[k] is the element-wise sum of the gradient rows of all
+ *      its occurrences, in unspecified order (as in accumulate);
+ *   2. the rule is applied exactly once to that key's row, in the shard's
+ *      value type T, with the hyper-parameters rounded to T once:
+ *          d = g + weight_decay * p
+ *          SGD:      p <- p - lr * d
+ *          Adagrad:  h <- h + d*d ;  p <- p - lr * d / (sqrt(h) + eps)
+ *      h is one accumulator per value (the shape of the dense array),
+ *      starting at init_accum;
+ *   3. keys not in the call keep p and h bit for bit.  Non-finite gradients
+ *      propagate by IEEE rules; nothing checks for them.
+ * A BSP flush of several workers' deferred pushes is one grouped call, hence
+ * one step over the summed minibatch gradient.  Scope and limits:
+ *   - float shards only (PSKV_F32, PSKV_F64); PSKV_I32 gives PSKV_EINVAL;
+ *   - any width, 1 included (a width-1 step runs on the row kernels);
+ *   - either creation mode; pskv_add and pskv_get keep their meaning on such
+ *     a shard (an assign Add initialises the parameters);
+ *   - keys outside [key_begin, key_end) are refused as a row shard's Add
+ *     refuses them, also at width 1: a host call returns PSKV_EINVAL naming
+ *     the first and applies nothing; a device call applies the in-range keys,
+ *     drops the others, and the next pskv_sync returns PSKV_ESTATE
+ *     (pskv_clear resets it).  The overflow table is not involved;
+ *   - pskv_apply without an optimizer gives PSKV_EINVAL;
+ *   - pskv_clear zeroes the parameters, resets h to init_accum and leaves the
+ *     gradient scratch zero;
+ *   - PSKV_SORTED_HINT is accepted and changes nothing; PSKV_HOST_FRAME
+ *     buffers are treated as plain host memory;
+ *   - with the resident request server (SERVE = 1) a step first ends the
+ *     server, as every stream path of pskv_add / pskv_get does;
+ *   - not provided: momentum, Adam, restoring h from a checkpoint, optimizer
+ *     state for overflow keys.
+ *
  * Threading: one shard handle is used by one host thread at a time (the
  * reference calls a storage only from its ServerThread, server_thread.cpp:20-50);
  * distinct handles may be used concurrently.  Every call selects the shard's
@@ -218,6 +255,40 @@ int pskv_get_grouped(pskv_shard* s, const pskv_batch* batches, uint64_t nb, int 
 int pskv_add_get_grouped(pskv_shard* s, const pskv_batch* adds, uint64_t na, const pskv_batch* gets,
                          uint64_t ng, int flags);
 
+/* Optimizers (semantics: the header comment, "Optimizer steps"). */
+enum pskv_optimizer_kind { PSKV_OPT_NONE = 0, PSKV_OPT_SGD = 1, PSKV_OPT_ADAGRAD = 2 };
+typedef struct pskv_optimizer {
+  int kind;
+  double lr;            /* finite, > 0 */
+  double weight_decay;  /* finite, >= 0 */
+  double eps;           /* Adagrad: finite, > 0; ignored by SGD */
+  double init_accum;    /* Adagrad: finite, >= 0 */
+} pskv_optimizer;
+/* Give the shard an optimizer, change its hyper-parameters, or (kind
+ * PSKV_OPT_NONE) take it away.  The configuration is validated before the
+ * handle is looked at: a bad field returns PSKV_EINVAL naming the field, also
+ * for a null shard.  The same kind again only changes the hyper-parameters of
+ * later calls (they travel by value with each launch, so the change is ordered
+ * by the stream; h keeps its contents and a new init_accum only takes effect
+ * at the next pskv_clear).  Another kind reallocates the state and resets it
+ * to init_accum, in stream order.  The gradient scratch, the accumulator and
+ * the stamp array are allocated here, never in pskv_apply; PSKV_ENOMEM leaves
+ * the shard as it was. */
+int pskv_shard_set_optimizer(pskv_shard* s, const pskv_optimizer* cfg);
+/* The current configuration and what the optimizer holds in HBM beyond the
+ * dense array: gradient scratch (dense_bytes) + h (dense_bytes, Adagrad only)
+ * + the stamp array (8 bytes per key); 0 without an optimizer.  Either output
+ * may be null. */
+int pskv_shard_get_optimizer(pskv_shard* s, pskv_optimizer* out, uint64_t* state_bytes);
+/* One optimizer step from n (key, gradient-row) pairs / from nb batches.
+ * Asynchronous for PSKV_DEVICE inputs; host inputs are staged before return. */
+int pskv_apply(pskv_shard* s, const uint32_t* keys, const void* grads, uint64_t n, int flags);
+int pskv_apply_grouped(pskv_shard* s, const pskv_batch* batches, uint64_t nb, int flags);
+/* A Get on Adagrad's accumulator h (flags and paths as pskv_get; a key outside
+ * the range reads as zeros): for checkpoints and tests.  PSKV_EINVAL unless
+ * the optimizer is PSKV_OPT_ADAGRAD. */
+int pskv_get_state(pskv_shard* s, const uint32_t* keys, uint64_t n, void* out, int flags);
+
 /* Wait for the shard's stream, adopt the overflow table as the kernels left
  * it (freeing arrays a device-side growth replaced; trimming its load to
  * <= 1/2), report sticky device errors.  Every host wait of the library (this one, a host
@@ -232,7 +303,8 @@ int pskv_add_get_grouped(pskv_shard* s, const pskv_batch* adds, uint64_t na, con
  * unmodified until a later pskv_sync succeeds.  (The library's own staging is
  * held back the same way: the next call waits for it, bounded.) */
 int pskv_sync(pskv_shard* s);
-/* Zero every value (dense array and overflow table). */
+/* Zero every value (dense array and overflow table); with an optimizer, also
+ * reset h to init_accum. */
 int pskv_clear(pskv_shard* s);
 
 /* Run the shard's work on an external hipStream_t (NULL = the shard's own
@@ -276,6 +348,12 @@ int pskv_set_timing_mask(pskv_shard* s, uint32_t kernel_mask);
 int pskv_kernel_time(pskv_shard* s, int kernel, uint64_t* launches, double* total_ms,
                      uint64_t* elements);
 int pskv_reset_timing(pskv_shard* s);
+/* An optimizer step's launches are timed as ONE operation in a slot of its
+ * own, outside enum pskv_kernel: enabled by pskv_set_timing(s, 1) or by this
+ * bit of pskv_set_timing_mask, cleared by pskv_reset_timing.  launches counts
+ * one operation per launch group (a call of at most 64 batches is one). */
+#define PSKV_TIME_APPLY (1u << 14)
+int pskv_apply_time(pskv_shard* s, uint64_t* launches, double* total_ms, uint64_t* elements);
 
 /* Mirror of RangePartitionManager::Slice (base/range_partition_manager.hpp:19-46):
  * walk `keys` once; a key goes to the current range if it lies in it or the

@@ -42,6 +42,8 @@ PSKV_K_ROW_COMMIT = 12
 PSKV_K_ROW_ACCUMULATE = 13
 PSKV_K_COUNT = 14
 PSKV_MAX_WIDTH = 4096
+PSKV_TIME_APPLY = 1 << 14
+PSKV_OPT_NONE, PSKV_OPT_SGD, PSKV_OPT_ADAGRAD = 0, 1, 2
 KERNEL_NAMES = {
     PSKV_K_GATHER: "k_gather",
     PSKV_K_ASSIGN_SORTED: "k_assign_sorted",
@@ -68,6 +70,8 @@ EXPORTED = [
     "pskv_abi_version", "pskv_device_count", "pskv_host_alloc", "pskv_host_free",
     "pskv_host_pool_stats", "pskv_host_pool_trim", "pskv_set_option", "pskv_get_option",
     "pskv_shard_create_rows", "pskv_shard_width",
+    "pskv_shard_set_optimizer", "pskv_shard_get_optimizer", "pskv_apply", "pskv_apply_grouped",
+    "pskv_get_state", "pskv_apply_time",
 ]
 
 
@@ -84,6 +88,11 @@ class PskvInfo(ctypes.Structure):
         ("n_get_calls", ctypes.c_uint64), ("n_sorted_launches", ctypes.c_uint64),
         ("n_general_launches", ctypes.c_uint64),
     ]
+
+
+class PskvOptimizer(ctypes.Structure):
+    _fields_ = [("kind", ctypes.c_int), ("lr", ctypes.c_double), ("weight_decay", ctypes.c_double),
+                ("eps", ctypes.c_double), ("init_accum", ctypes.c_double)]
 
 
 class PskvError(RuntimeError):
@@ -132,6 +141,12 @@ def _load():
         "pskv_host_pool_trim": ([], i32),
         "pskv_set_option": ([vp, ctypes.c_char_p, ctypes.c_int64], i32),
         "pskv_get_option": ([vp, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int64)], i32),
+        "pskv_shard_set_optimizer": ([vp, ctypes.POINTER(PskvOptimizer)], i32),
+        "pskv_shard_get_optimizer": ([vp, ctypes.POINTER(PskvOptimizer), ctypes.POINTER(u64)], i32),
+        "pskv_apply": ([vp, vp, vp, u64, i32], i32),
+        "pskv_apply_grouped": ([vp, ctypes.POINTER(PskvBatch), u64, i32], i32),
+        "pskv_get_state": ([vp, vp, u64, vp, i32], i32),
+        "pskv_apply_time": ([vp, ctypes.POINTER(u64), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(u64)], i32),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)

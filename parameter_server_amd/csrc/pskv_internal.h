@@ -12,6 +12,8 @@
 //                       slots, sticky error bits}, the growth mailbox
 //   keys[cap]           u64 overflow hash keys, EMPTY = ~0
 //   vals[cap]           overflow values
+//   gsum, h             with an optimizer: gradient scratch and Adagrad's
+//                       accumulator, each shaped as dense
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -258,5 +260,32 @@ hipError_t launch_row_commit(int vb, const GroupArgs& ga, uint32_t nwg, const De
 // One no-return atomic add per element (rs built with unit16 = false).
 hipError_t launch_row_accumulate(int dtype, const GroupArgs& ga, uint32_t nwg, const DenseView& d,
                                  const Ovf& o, const RowShape& rs, hipStream_t st);
+
+// Optimizer steps (pskv_apply), float shards of any width
+// (1 included).  The hyper-parameters travel by value, rounded to the value
+// type once per launch, so a change is ordered by the stream.
+struct OptHyper {
+  double lr, wd, eps;
+};
+template <typename T>
+struct OptArgs {
+  T lr, wd, eps;
+};
+// Behind launch_general_mark (stamp mode) over the same `ga` and epoch: every
+// in-range element that is NOT its key's winner adds its gradient row into
+// gsum (shaped as the dense array, zero between calls), one no-return atomic
+// per element (rs built with unit16 = false).  Out-of-range keys set
+// kErrRowOutOfRange.  d.param is not touched.
+hipError_t launch_row_grad_losers(int dtype, const GroupArgs& ga, uint32_t nwg, const DenseView& d, void* gsum,
+                                  const unsigned long long* owner, const Ovf& o, uint32_t epoch,
+                                  const RowShape& rs, hipStream_t st);
+// Each winner applies the rule (kind: pskv_optimizer_kind, 1 or 2) once to its
+// key's row from its own gradient row plus the gsum row, and writes zeros back
+// to the gsum units it read non-zero.  state: Adagrad's accumulator.
+hipError_t launch_row_apply(int dtype, int kind, const GroupArgs& ga, uint32_t nwg, const DenseView& d, void* gsum,
+                            void* state, const unsigned long long* owner, uint32_t epoch, const RowShape& rs,
+                            const OptHyper& hy, hipStream_t st);
+// p[0..n) = v (float or double by dtype): the accumulator's initial value.
+hipError_t launch_fill(int dtype, void* p, uint64_t n, double v, hipStream_t st);
 
 }  // namespace pskv

@@ -4,8 +4,10 @@
 //   k_row_gather      Get: out[i] = row(keys[i]), zeros for a key outside the range
 //   k_row_commit      assign Add: the stamped winner of each key copies its whole row
 //   k_row_accumulate  accumulate Add: one no-return atomic add per element
+//   k_row_grad_losers optimizer step: gradient rows of non-winners summed into gsum
+//   k_row_apply       optimizer step: each key's winner applies SGD / Adagrad once
 //
-// Lane mapping (all three).  A row is U units long (RowShape); a group of
+// Lane mapping (all of them).  A row is U units long (RowShape); a group of
 // L = min(64, next_pow2(U)) consecutive lanes owns one row at a time, lane l
 // of the group taking units l, l + L, ...  A wave therefore covers 64 / L
 // rows per instruction, each as one contiguous segment, and every lane of a
@@ -205,7 +207,182 @@ __global__ __launch_bounds__(kBlock) void k_row_accumulate(GroupArgs ga, DenseVi
   }
 }
 
+// ------------------------------------------------------- optimizer steps
+// One pskv_apply call is one step: behind K4a's stamps,
+// k_row_grad_losers sums the gradient rows of every element that is not its
+// key's winner into `gsum` (zero between calls), then k_row_apply lets each
+// winner apply the rule once to its key's row and put the gsum row back to zero.
+
+// A unit of V consecutive elements: V = 1, or 16 bytes' worth.
+template <typename T, int V>
+struct OptUnit {
+  T e[V];
+};
+
+template <typename T, int V>
+__device__ __forceinline__ OptUnit<T, V> load_opt_unit(const T* p, uint64_t unit) {
+  OptUnit<T, V> r;
+  if constexpr (V == 1) {
+    r.e[0] = p[unit];
+  } else {
+    typedef T vt __attribute__((ext_vector_type(V)));
+    const vt v = *reinterpret_cast<const vt*>(p + unit * V);
+#pragma unroll
+    for (int i = 0; i < V; ++i) r.e[i] = v[i];
+  }
+  return r;
+}
+
+template <typename T, int V>
+__device__ __forceinline__ void store_opt_unit(T* p, uint64_t unit, const OptUnit<T, V>& r) {
+  if constexpr (V == 1) {
+    p[unit] = r.e[0];
+  } else {
+    typedef T vt __attribute__((ext_vector_type(V)));
+    vt v;
+#pragma unroll
+    for (int i = 0; i < V; ++i) v[i] = r.e[i];
+    *reinterpret_cast<vt*>(p + unit * V) = v;
+  }
+}
+
+__device__ __forceinline__ bool nonzero_bits(float x) { return __float_as_uint(x) != 0u; }
+__device__ __forceinline__ bool nonzero_bits(double x) { return __double_as_longlong(x) != 0ll; }
+
+// One element per lane, as k_row_accumulate.  `tag` of an element as in
+// k_row_commit; an in-range element whose tag is not its key's stamp is a loser.
+template <typename AT>
+__global__ __launch_bounds__(kBlock) void k_row_grad_losers(GroupArgs ga, DenseView d, AT* __restrict__ gsum,
+                                                            const unsigned long long* __restrict__ owner,
+                                                            uint32_t* err, uint32_t epoch, RowShape rs) {
+  const uint32_t lane = threadIdx.x & (rs.lanes - 1u);
+  const uint32_t grp = threadIdx.x >> rs.lshift;
+  const uint32_t G = (uint32_t)kBlock >> rs.lshift;
+  const uint32_t U = rs.units;
+  const uint32_t nvwg = ga.wg_prefix[ga.nb];
+  for (uint32_t wg = blockIdx.x; wg < nvwg; wg += gridDim.x) {
+    const int j = row_batch_of(ga, wg);
+    const uint32_t* __restrict__ keys = ga.b[j].keys;
+    const AT* __restrict__ vals = reinterpret_cast<const AT*>(ga.b[j].vals);
+    const uint64_t n = ga.b[j].n;
+    const uint64_t base = (uint64_t)(wg - ga.wg_prefix[j]) * kGeneralChunk;
+    const uint64_t gbase = row_elem_prefix(ga, j) + base;
+    for (uint32_t r0 = grp; r0 < (uint32_t)kGeneralChunk; r0 += kRowsInFlight * G) {
+      if (base + r0 >= n) break;
+      RowStep s;
+      load_step(s, keys, n, base, r0, G, d);
+      bool lose[kRowsInFlight];
+      bool any = false;
+#pragma unroll
+      for (int r = 0; r < kRowsInFlight; ++r) {
+        const unsigned long long tag =
+            ((unsigned long long)epoch << 32) | (gbase + r0 + (uint32_t)r * G);
+        lose[r] = s.in[r] && owner[s.off[r]] != tag;
+        any |= lose[r];
+        if (s.live[r] && !s.in[r] && lane == 0) atomicOr(err, kErrRowOutOfRange);
+      }
+      if (!any) continue;  // distinct keys: only keys and stamps were read
+      for (uint32_t u = lane; u < U; u += rs.lanes) {
+        AT v[kRowsInFlight];
+#pragma unroll
+        for (int r = 0; r < kRowsInFlight; ++r) v[r] = lose[r] ? vals[s.i[r] * U + u] : AT(0);
+#pragma unroll
+        for (int r = 0; r < kRowsInFlight; ++r)
+          if (lose[r]) (void)atomicAdd(gsum + (uint64_t)s.off[r] * U + u, v[r]);
+      }
+    }
+  }
+}
+
+// KIND: 1 = SGD, 2 = Adagrad (pskv_optimizer_kind).  One writer per row.
+template <typename T, int KIND, int V>
+__global__ __launch_bounds__(kBlock) void k_row_apply(GroupArgs ga, DenseView d, T* __restrict__ gsum,
+                                                      T* __restrict__ state,
+                                                      const unsigned long long* __restrict__ owner,
+                                                      uint32_t epoch, RowShape rs, OptArgs<T> o) {
+  const uint32_t lane = threadIdx.x & (rs.lanes - 1u);
+  const uint32_t grp = threadIdx.x >> rs.lshift;
+  const uint32_t G = (uint32_t)kBlock >> rs.lshift;
+  const uint32_t U = rs.units;
+  T* __restrict__ param = reinterpret_cast<T*>(d.param);
+  const uint32_t nvwg = ga.wg_prefix[ga.nb];
+  for (uint32_t wg = blockIdx.x; wg < nvwg; wg += gridDim.x) {
+    const int j = row_batch_of(ga, wg);
+    const uint32_t* __restrict__ keys = ga.b[j].keys;
+    const T* __restrict__ vals = reinterpret_cast<const T*>(ga.b[j].vals);
+    const uint64_t n = ga.b[j].n;
+    const uint64_t base = (uint64_t)(wg - ga.wg_prefix[j]) * kGeneralChunk;
+    const uint64_t gbase = row_elem_prefix(ga, j) + base;
+    for (uint32_t r0 = grp; r0 < (uint32_t)kGeneralChunk; r0 += kRowsInFlight * G) {
+      if (base + r0 >= n) break;
+      RowStep s;
+      load_step(s, keys, n, base, r0, G, d);
+      bool win[kRowsInFlight];
+      bool any = false;
+#pragma unroll
+      for (int r = 0; r < kRowsInFlight; ++r) {
+        const unsigned long long tag =
+            ((unsigned long long)epoch << 32) | (gbase + r0 + (uint32_t)r * G);
+        win[r] = s.in[r] && owner[s.off[r]] == tag;
+        any |= win[r];
+      }
+      if (!any) continue;
+      for (uint32_t u = lane; u < U; u += rs.lanes) {
+        OptUnit<T, V> g[kRowsInFlight], gs[kRowsInFlight], p[kRowsInFlight], h[kRowsInFlight];
+#pragma unroll
+        for (int r = 0; r < kRowsInFlight; ++r) {
+          if (!win[r]) continue;
+          const uint64_t at = (uint64_t)s.off[r] * U + u;
+          g[r] = load_opt_unit<T, V>(vals, s.i[r] * U + u);
+          gs[r] = load_opt_unit<T, V>(gsum, at);
+          p[r] = load_opt_unit<T, V>(param, at);
+          if (KIND == 2) h[r] = load_opt_unit<T, V>(state, at);
+        }
+#pragma unroll
+        for (int r = 0; r < kRowsInFlight; ++r) {
+          if (!win[r]) continue;
+          const uint64_t at = (uint64_t)s.off[r] * U + u;
+          bool dirty = false;
+#pragma unroll
+          for (int i = 0; i < V; ++i) {
+            dirty |= nonzero_bits(gs[r].e[i]);
+            const T dd = (g[r].e[i] + gs[r].e[i]) + o.wd * p[r].e[i];
+            if (KIND == 2) {
+              h[r].e[i] = h[r].e[i] + dd * dd;
+              p[r].e[i] = p[r].e[i] - o.lr * (dd / (sqrt(h[r].e[i]) + o.eps));
+            } else {
+              p[r].e[i] = p[r].e[i] - o.lr * dd;
+            }
+            gs[r].e[i] = T(0);
+          }
+          store_opt_unit<T, V>(param, at, p[r]);
+          if (KIND == 2) store_opt_unit<T, V>(state, at, h[r]);
+          if (dirty) store_opt_unit<T, V>(gsum, at, gs[r]);
+        }
+      }
+    }
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_fill(T* __restrict__ p, uint64_t n, T v) {
+  for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) p[i] = v;
+}
+
 uint32_t row_grid(uint32_t nwg) { return nwg < 4096u ? nwg : 4096u; }
+
+template <typename T, int V>
+void launch_row_apply_kind(int kind, uint32_t grid, const GroupArgs& ga, const DenseView& d, void* gsum, void* state,
+                           const unsigned long long* owner, uint32_t epoch, const RowShape& rs, const OptHyper& hy,
+                           hipStream_t st) {
+  const OptArgs<T> o{(T)hy.lr, (T)hy.wd, (T)hy.eps};
+  if (kind == 2)
+    k_row_apply<T, 2, V><<<grid, kBlock, 0, st>>>(ga, d, static_cast<T*>(gsum), static_cast<T*>(state), owner, epoch,
+                                                  rs, o);
+  else
+    k_row_apply<T, 1, V><<<grid, kBlock, 0, st>>>(ga, d, static_cast<T*>(gsum), static_cast<T*>(state), owner, epoch,
+                                                  rs, o);
+}
 
 }  // namespace
 
@@ -271,6 +448,53 @@ hipError_t launch_row_accumulate(int dtype, const GroupArgs& ga, uint32_t nwg, c
     k_row_accumulate<float><<<grid, kBlock, 0, st>>>(ga, d, err, rs);
   else
     k_row_accumulate<double><<<grid, kBlock, 0, st>>>(ga, d, err, rs);
+  return hipGetLastError();
+}
+
+hipError_t launch_row_grad_losers(int dtype, const GroupArgs& ga, uint32_t nwg, const DenseView& d, void* gsum,
+                                  const unsigned long long* owner, const Ovf& o, uint32_t epoch,
+                                  const RowShape& rs, hipStream_t st) {
+  if (nwg == 0) return hipSuccess;
+  if (dtype != 1 && dtype != 2) return hipErrorInvalidValue;
+  const uint32_t grid = row_grid(nwg);
+  uint32_t* err = &o.c->stat[1];
+  if (dtype == 1)
+    k_row_grad_losers<float><<<grid, kBlock, 0, st>>>(ga, d, static_cast<float*>(gsum), owner, err, epoch, rs);
+  else
+    k_row_grad_losers<double><<<grid, kBlock, 0, st>>>(ga, d, static_cast<double*>(gsum), owner, err, epoch, rs);
+  return hipGetLastError();
+}
+
+hipError_t launch_row_apply(int dtype, int kind, const GroupArgs& ga, uint32_t nwg, const DenseView& d, void* gsum,
+                            void* state, const unsigned long long* owner, uint32_t epoch, const RowShape& rs,
+                            const OptHyper& hy, hipStream_t st) {
+  if (nwg == 0) return hipSuccess;
+  if ((dtype != 1 && dtype != 2) || (kind != 1 && kind != 2) || (kind == 2 && !state)) return hipErrorInvalidValue;
+  const uint32_t grid = row_grid(nwg);
+  const bool u16 = rs.unit_bytes == 16;
+  if (dtype == 1) {
+    if (u16)
+      launch_row_apply_kind<float, 4>(kind, grid, ga, d, gsum, state, owner, epoch, rs, hy, st);
+    else
+      launch_row_apply_kind<float, 1>(kind, grid, ga, d, gsum, state, owner, epoch, rs, hy, st);
+  } else {
+    if (u16)
+      launch_row_apply_kind<double, 2>(kind, grid, ga, d, gsum, state, owner, epoch, rs, hy, st);
+    else
+      launch_row_apply_kind<double, 1>(kind, grid, ga, d, gsum, state, owner, epoch, rs, hy, st);
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_fill(int dtype, void* p, uint64_t n, double v, hipStream_t st) {
+  if (n == 0) return hipSuccess;
+  if (dtype != 1 && dtype != 2) return hipErrorInvalidValue;
+  const uint64_t nwg = (n + kBlock - 1) / kBlock;
+  const uint32_t grid = (uint32_t)(nwg < 65536u ? nwg : 65536u);
+  if (dtype == 1)
+    k_fill<float><<<grid, kBlock, 0, st>>>(static_cast<float*>(p), n, (float)v);
+  else
+    k_fill<double><<<grid, kBlock, 0, st>>>(static_cast<double*>(p), n, v);
   return hipGetLastError();
 }
 

@@ -90,7 +90,14 @@ struct TimedLaunch {
   int kernel;
   hipEvent_t a, b;
   uint64_t elems;
+  uint64_t count = 1;  // operations the bracket stands for (an optimizer step: its launch groups)
 };
+
+// Timing slots: the kernels of enum pskv_kernel, then one slot for a whole
+// optimizer step (pskv_apply_time; PSKV_TIME_APPLY is its mask bit).
+constexpr int kTimeApply = PSKV_K_COUNT;
+constexpr int kTimeSlots = PSKV_K_COUNT + 1;
+static_assert(PSKV_TIME_APPLY == (1u << kTimeApply), "the apply slot follows the kernel ids");
 
 // ---------------------------------------------------------------- host pool
 // A small persistent pool for the host side of the path: copying zmq-buffer
@@ -249,9 +256,9 @@ struct pskv_shard {
   uint32_t timing_mask = 0;  // bit k: bracket kernel k with events
   std::vector<TimedLaunch> pending;
   std::vector<hipEvent_t> event_pool;
-  uint64_t t_launches[PSKV_K_COUNT] = {};
-  double t_ms[PSKV_K_COUNT] = {};
-  uint64_t t_elems[PSKV_K_COUNT] = {};
+  uint64_t t_launches[kTimeSlots] = {};
+  double t_ms[kTimeSlots] = {};
+  uint64_t t_elems[kTimeSlots] = {};
   // stats
   uint64_t n_add = 0, n_get = 0, n_sorted = 0, n_general = 0;
   // K5 radix-bucket scratch (grown on demand)
@@ -354,6 +361,12 @@ struct pskv_shard {
   ReplayGroup pend_rg{};
   uint32_t pend_epoch = 0;
   uint64_t pend_elems = 0;
+  // optimizer (pskv_shard_set_optimizer): the configuration, the gradient
+  // scratch (shaped as the dense array, zero between calls) and Adagrad's
+  // accumulator; both allocated when the optimizer is set
+  pskv_optimizer opt{};
+  void* opt_gsum = nullptr;
+  void* opt_state = nullptr;
 
   DenseView dview() const { return DenseView{dense, key_begin, range}; }
 };
@@ -397,6 +410,7 @@ struct LaunchTimer {
   pskv_shard* s;
   int kernel;
   uint64_t elems;
+  uint64_t count = 1;
   hipEvent_t a = nullptr, b = nullptr;
   LaunchTimer(pskv_shard* s_, int k, uint64_t e) : s(s_), kernel(k), elems(e) {
     s->last_kernel = k;
@@ -410,7 +424,7 @@ struct LaunchTimer {
   void done() {
     if (a && b) {
       (void)hipEventRecord(b, s->stream);
-      s->pending.push_back(TimedLaunch{kernel, a, b, elems});
+      s->pending.push_back(TimedLaunch{kernel, a, b, elems, count});
     }
     a = b = nullptr;
   }
@@ -426,12 +440,13 @@ struct LaunchTimer {
 // item 1).  Nothing is restarted or cancelled: the work stays queued.  Polls
 // spin for the first millisecond (a small call's latency), then yield, then
 // sleep 100 us between polls after 50 ms.
-const char* const kKernelNames[PSKV_K_COUNT] = {
+const char* const kKernelNames[kTimeSlots] = {
     "k_gather (K1 Get)",          "k_assign_sorted (K2)",          "k_assign_group (K2g)",
     "k_general_mark (K4a)",       "k_general_commit (K4b)",        "k_rb_bin + k_rb_resolve (K5 Add)",
     "k_dense_check (K6)",         "k_acc_dense (K7)",              "k_inline_add (K8)",
     "k_inline_get (K8)",          "k_replay (K4r)",                "k_row_gather (row Get)",
-    "k_general_mark + k_row_commit (row assign Add)",              "k_row_accumulate (row accumulate Add)"};
+    "k_general_mark + k_row_commit (row assign Add)",              "k_row_accumulate (row accumulate Add)",
+    "k_general_mark + k_row_grad_losers + k_row_apply (optimizer step)"};
 
 std::string wait_report(const pskv_shard* s, const char* what, const void* handle, double ms) {
   char buf[384];
@@ -439,7 +454,7 @@ std::string wait_report(const pskv_shard* s, const char* what, const void* handl
                 "%s (%p) on device %d not complete after %.0f ms (PSKV_SYNC_TIMEOUT_MS); last kernel this shard "
                 "queued: %s (%llu launches); the work stays queued",
                 what, handle, s->device, ms,
-                s->last_kernel >= 0 && s->last_kernel < PSKV_K_COUNT ? kKernelNames[s->last_kernel] : "none",
+                s->last_kernel >= 0 && s->last_kernel < kTimeSlots ? kKernelNames[s->last_kernel] : "none",
                 (unsigned long long)s->launches);
   return buf;
 }
@@ -484,7 +499,7 @@ int drain_timing(pskv_shard* s) {
     if (int rc = wait_event(s, t.b, "timing event of the shard's stream", t.b)) return rc;
     float ms = 0.f;
     PSKV_HIP(hipEventElapsedTime(&ms, t.a, t.b));
-    s->t_launches[t.kernel] += 1;
+    s->t_launches[t.kernel] += t.count;
     s->t_ms[t.kernel] += ms;
     s->t_elems[t.kernel] += t.elems;
     s->event_pool.push_back(t.a);
@@ -1629,32 +1644,35 @@ int rows_add(pskv_shard* s, const std::vector<pskv_batch>& in, int flags) {
   return rc ? rc : rows_add_device(s, dv);
 }
 
-int rows_gather(pskv_shard* s, const std::vector<pskv_batch>& dv) {
-  bool vec = row_bytes(s) % 16 == 0 && aligned16(s->dense);
+// `d`: the array gathered from: the dense array, or (pskv_get_state) the
+// optimizer's accumulator, which has the same shape.
+int rows_gather(pskv_shard* s, const std::vector<pskv_batch>& dv, const DenseView& d) {
+  bool vec = row_bytes(s) % 16 == 0 && aligned16(d.param);
   for (auto& b : dv) vec = vec && aligned16(b.vals);
   const RowShape rs = row_shape(s->width, s->vb, vec);
   for (const Span& sp : split_groups(dv)) {
     const LaunchGroup g = make_group(dv, sp.first, sp.second, kGeneralChunk);
     LaunchTimer t(s, PSKV_K_ROW_GATHER, g.elems);
-    PSKV_HIP(launch_row_gather(s->vb, s->tune_nt, g.ga, g.nwg, s->dview(), rs, s->stream));
+    PSKV_HIP(launch_row_gather(s->vb, s->tune_nt, g.ga, g.nwg, d, rs, s->stream));
     t.done();
   }
   return PSKV_OK;
 }
 
-int rows_get(pskv_shard* s, const std::vector<pskv_batch>& in, int flags) {
+int rows_get_from(pskv_shard* s, const std::vector<pskv_batch>& in, int flags, const DenseView& src,
+                  const char* what, bool count_get) {
   std::vector<pskv_batch> v;
-  if (int rc = rows_pieces(s, in, "pskv_get", &v)) return rc;
-  s->n_get++;
+  if (int rc = rows_pieces(s, in, what, &v)) return rc;
+  if (count_get) s->n_get++;
   if (v.empty()) return PSKV_OK;
   int rc = use_device(s);
   if (rc) return rc;
-  if (flags & PSKV_DEVICE) return rows_gather(s, v);
+  if (flags & PSKV_DEVICE) return rows_gather(s, v, src);
   HstageHold hold(s);
   const StageLayout lay = stage_layout(v, row_bytes(s), StageOrder::kKeysFirst);
   std::vector<pskv_batch> dv;
   rc = stage_keys_first(s, v, lay, row_bytes(s), /*with_values=*/false, hold, &dv);
-  if (!rc) rc = rows_gather(s, dv);
+  if (!rc) rc = rows_gather(s, dv, src);
   if (rc) return rc;
   // rows: device staging -> pinned staging -> the caller's buffers
   char* h = static_cast<char*>(s->hstage);
@@ -1668,6 +1686,113 @@ int rows_get(pskv_shard* s, const std::vector<pskv_batch>& in, int flags) {
     add_pieces(pieces, h + lay.at[i].vals, static_cast<char*>(v[i].vals), v[i].n * row_bytes(s), -1);
   run_copies(s, pieces, 0, pieces.size());
   return PSKV_OK;
+}
+
+int rows_get(pskv_shard* s, const std::vector<pskv_batch>& in, int flags) {
+  return rows_get_from(s, in, flags, s->dview(), "pskv_get", /*count_get=*/true);
+}
+
+// -------------------------------------------------------- optimizer steps
+// pskv_apply (pskv.h): one call is one step.  Any width, 1
+// included: a width-1 shard's step runs on these row kernels, not on the
+// scalar paths.  Launches per call of G launch groups (split_groups):
+//   G x K4a (stamp mode, one epoch per group)   the winner element of each key
+//   G x k_row_grad_losers                       every other element's row -> gsum
+//   G x k_row_apply                             each winner steps its key's row
+// All marks come first: a key's stamp then belongs to the last group that
+// holds it, the key's elements in earlier groups all see a foreign stamp and
+// go to gsum, and exactly one element of the call applies the rule.
+size_t opt_array_bytes(const pskv_shard* s) { return s->range * row_bytes(s); }
+
+// The accumulator back to init_accum, the gradient scratch to zero (stream-ordered).
+int opt_reset_state(pskv_shard* s) {
+  if (s->opt_gsum) PSKV_HIP(hipMemsetAsync(s->opt_gsum, 0, opt_array_bytes(s), s->stream));
+  if (s->opt_state)
+    PSKV_HIP(launch_fill(s->dtype, s->opt_state, s->range * (uint64_t)s->width, s->opt.init_accum, s->stream));
+  return PSKV_OK;
+}
+
+int apply_device(pskv_shard* s, const std::vector<pskv_batch>& v) {
+  if (int rc = ensure_owner(s)) return rc;
+  bool vec = row_bytes(s) % 16 == 0 && aligned16(s->dense) && aligned16(s->opt_gsum) && aligned16(s->opt_state);
+  for (auto& b : v) vec = vec && aligned16(b.vals);
+  const std::vector<Span> spans = split_groups(v);
+  std::vector<LaunchGroup> groups;
+  std::vector<uint32_t> epochs;
+  uint64_t elems = 0;
+  // the call's epochs must not straddle a wrap-around (next_epoch resets the
+  // stamps there): take the wrap first
+  if (0xFFFFFFFFu - s->epoch < spans.size()) s->epoch = 0xFFFFFFFFu;
+  for (const Span& sp : spans) {
+    groups.push_back(make_group(v, sp.first, sp.second, kGeneralChunk));
+    epochs.push_back(next_epoch(s));
+    elems += groups.back().elems;
+  }
+  const OptHyper hy{s->opt.lr, s->opt.weight_decay, s->opt.eps};
+  const RowShape rs1 = row_shape(s->width, s->vb, false);
+  const RowShape rsv = row_shape(s->width, s->vb, vec);
+  LaunchTimer t(s, kTimeApply, elems);
+  t.count = groups.size();
+  for (size_t i = 0; i < groups.size(); ++i)
+    PSKV_HIP(launch_general_mark(s->dtype, PSKV_ASSIGN, groups[i].ga, groups[i].nwg, s->dview(), s->flag + 1,
+                                 s->owner, nullptr, epochs[i], s->stream));
+  for (size_t i = 0; i < groups.size(); ++i)
+    PSKV_HIP(launch_row_grad_losers(s->dtype, groups[i].ga, groups[i].nwg, s->dview(), s->opt_gsum, s->owner, s->ovf,
+                                    epochs[i], rs1, s->stream));
+  for (size_t i = 0; i < groups.size(); ++i)
+    PSKV_HIP(launch_row_apply(s->dtype, s->opt.kind, groups[i].ga, groups[i].nwg, s->dview(), s->opt_gsum,
+                              s->opt_state, s->owner, epochs[i], rsv, hy, s->stream));
+  t.done();
+  s->n_general += 3 * groups.size();
+  return PSKV_OK;
+}
+
+int apply_impl(pskv_shard* s, const std::vector<pskv_batch>& in, int flags) {
+  if (s->opt.kind == PSKV_OPT_NONE)
+    return fail(PSKV_EINVAL, "pskv_apply: the shard has no optimizer (pskv_shard_set_optimizer)");
+  std::vector<pskv_batch> v;
+  if (int rc = rows_pieces(s, in, "pskv_apply", &v)) return rc;
+  if (v.empty()) return PSKV_OK;
+  int rc = use_device(s);
+  if (rc) return rc;
+  // a width-1 shard's resident request server runs alone on the shard: as
+  // every stream path of add_impl / get_impl, end it first (K8 launches are
+  // ordinary work of the shard's stream and need nothing)
+  rc = srv_stop(s);
+  if (rc) return rc;
+  if (flags & PSKV_DEVICE) return apply_device(s, v);
+  // the keys are checked before anything is queued: nothing is applied
+  for (const auto& b : v) {
+    Piece p{};
+    check_keys(p, b.keys, b.n, s->key_begin, s->range);
+    if (!p.outside) continue;
+    for (uint64_t i = 0; i < b.n; ++i)
+      if ((uint64_t)(uint32_t)(b.keys[i] - s->key_begin) >= s->range)
+        return fail(PSKV_EINVAL, "pskv_apply: key " + std::to_string(b.keys[i]) +
+                                     " is outside [key_begin, key_end); an optimizer step takes no out-of-range "
+                                     "keys (nothing was applied)");
+  }
+  // the call returns before its DMA: the hold stays armed
+  HstageHold hold(s);
+  std::vector<pskv_batch> dv;
+  rc = stage_keys_first(s, v, stage_layout(v, row_bytes(s), StageOrder::kKeysFirst), row_bytes(s),
+                        /*with_values=*/true, hold, &dv);
+  return rc ? rc : apply_device(s, dv);
+}
+
+// What is wrong with a configuration, or null (checked before any handle).
+const char* opt_config_error(const pskv_optimizer* c) {
+  if (!c) return "null configuration";
+  if (c->kind != PSKV_OPT_NONE && c->kind != PSKV_OPT_SGD && c->kind != PSKV_OPT_ADAGRAD)
+    return "kind must be PSKV_OPT_NONE, PSKV_OPT_SGD or PSKV_OPT_ADAGRAD";
+  if (c->kind == PSKV_OPT_NONE) return nullptr;
+  if (!std::isfinite(c->lr) || !(c->lr > 0)) return "lr must be finite and > 0";
+  if (!std::isfinite(c->weight_decay) || !(c->weight_decay >= 0)) return "weight_decay must be finite and >= 0";
+  if (c->kind == PSKV_OPT_ADAGRAD) {
+    if (!std::isfinite(c->eps) || !(c->eps > 0)) return "eps must be finite and > 0";
+    if (!std::isfinite(c->init_accum) || !(c->init_accum >= 0)) return "init_accum must be finite and >= 0";
+  }
+  return nullptr;
 }
 
 int add_impl(pskv_shard* s, const std::vector<pskv_batch>& in, int flags) {
@@ -2253,6 +2378,8 @@ int pskv_shard_destroy(pskv_shard* s) {
   if (s->sync_ev) (void)hipEventDestroy(s->sync_ev);
   if (s->dense) (void)hipFree(s->dense);
   if (s->owner) (void)hipFree(s->owner);
+  if (s->opt_gsum) (void)hipFree(s->opt_gsum);
+  if (s->opt_state) (void)hipFree(s->opt_state);
   if (s->flag) (void)hipFree(s->flag);
   for (const auto& t : s->tables) {  // (the service no longer touches the list)
     (void)hipFree(t.keys);
@@ -2317,6 +2444,112 @@ int pskv_get_grouped(pskv_shard* s, const pskv_batch* batches, uint64_t nb, int 
   return get_impl(s, std::vector<pskv_batch>(batches, batches + nb), flags);
 }
 
+int pskv_shard_set_optimizer(pskv_shard* s, const pskv_optimizer* cfg) {
+  // the configuration first: a bad field is reported whatever the handle
+  if (const char* what = opt_config_error(cfg))
+    return fail(PSKV_EINVAL, std::string("pskv_shard_set_optimizer: ") + what);
+  if (!s) return fail(PSKV_EINVAL, "pskv_shard_set_optimizer: null shard");
+  if (cfg->kind != PSKV_OPT_NONE && s->dtype != PSKV_F32 && s->dtype != PSKV_F64)
+    return fail(PSKV_EINVAL, "pskv_shard_set_optimizer: optimizers need a float shard (PSKV_F32, PSKV_F64)");
+  int rc = use_device(s);
+  if (rc) return rc;
+  if (cfg->kind == s->opt.kind) {  // hyper-parameters only: they travel by value with each later launch
+    s->opt = *cfg;
+    return PSKV_OK;
+  }
+  // a change of kind: allocate what the new kind needs before anything is
+  // given up, so a failure leaves the shard as it was
+  const size_t bytes = opt_array_bytes(s);
+  void* gsum = s->opt_gsum;
+  void* state = nullptr;
+  if (cfg->kind != PSKV_OPT_NONE) {
+    if (!gsum && hipMalloc(&gsum, bytes) != hipSuccess)
+      return fail(PSKV_ENOMEM, "pskv_shard_set_optimizer: gradient scratch allocation failed");
+    if (cfg->kind == PSKV_OPT_ADAGRAD && hipMalloc(&state, bytes) != hipSuccess) {
+      if (gsum != s->opt_gsum) (void)hipFree(gsum);
+      return fail(PSKV_ENOMEM, "pskv_shard_set_optimizer: accumulator allocation failed");
+    }
+    if ((rc = ensure_owner(s))) {
+      if (gsum != s->opt_gsum) (void)hipFree(gsum);
+      if (state) (void)hipFree(state);
+      return rc;
+    }
+  }
+  // queued steps may still use the arrays that go
+  if (s->opt_state || (cfg->kind == PSKV_OPT_NONE && s->opt_gsum)) {
+    if ((rc = srv_stop(s)) || (rc = wait_stream(s, s->stream, "shard stream (optimizer change)"))) {
+      if (gsum != s->opt_gsum) (void)hipFree(gsum);
+      if (state) (void)hipFree(state);
+      return rc;
+    }
+    if (s->opt_state) (void)hipFree(s->opt_state);
+    s->opt_state = nullptr;
+    if (cfg->kind == PSKV_OPT_NONE) {
+      (void)hipFree(s->opt_gsum);
+      gsum = nullptr;
+    }
+  }
+  s->opt_gsum = gsum;
+  s->opt_state = state;
+  s->opt = *cfg;
+  return opt_reset_state(s);
+}
+
+int pskv_shard_get_optimizer(pskv_shard* s, pskv_optimizer* out, uint64_t* state_bytes) {
+  if (!s) return fail(PSKV_EINVAL, "pskv_shard_get_optimizer: null shard");
+  if (out) *out = s->opt;
+  if (state_bytes) {
+    // gradient scratch + accumulator (Adagrad) + the stamp array (8 bytes per key)
+    uint64_t b = 0;
+    if (s->opt.kind != PSKV_OPT_NONE) {
+      b = opt_array_bytes(s) + s->range * sizeof(unsigned long long);
+      if (s->opt.kind == PSKV_OPT_ADAGRAD) b += opt_array_bytes(s);
+    }
+    *state_bytes = b;
+  }
+  return PSKV_OK;
+}
+
+int pskv_apply(pskv_shard* s, const uint32_t* keys, const void* grads, uint64_t n, int flags) {
+  if (!s) return fail(PSKV_EINVAL, "pskv_apply: null shard");
+  if (bad_flags(flags)) return fail(PSKV_EINVAL, "pskv_apply: unknown flags");
+  pskv_batch b{keys, const_cast<void*>(grads), n};
+  return apply_impl(s, std::vector<pskv_batch>{b}, flags);
+}
+
+int pskv_apply_grouped(pskv_shard* s, const pskv_batch* batches, uint64_t nb, int flags) {
+  if (!s) return fail(PSKV_EINVAL, "pskv_apply_grouped: null shard");
+  if (nb && !batches) return fail(PSKV_EINVAL, "pskv_apply_grouped: null batches");
+  if (bad_flags(flags)) return fail(PSKV_EINVAL, "pskv_apply_grouped: unknown flags");
+  return apply_impl(s, std::vector<pskv_batch>(batches, batches + nb), flags);
+}
+
+int pskv_get_state(pskv_shard* s, const uint32_t* keys, uint64_t n, void* out, int flags) {
+  if (!s) return fail(PSKV_EINVAL, "pskv_get_state: null shard");
+  if (bad_flags(flags)) return fail(PSKV_EINVAL, "pskv_get_state: unknown flags");
+  if (s->opt.kind != PSKV_OPT_ADAGRAD || !s->opt_state)
+    return fail(PSKV_EINVAL, "pskv_get_state: the shard's optimizer keeps no state (only PSKV_OPT_ADAGRAD does)");
+  int rc = use_device(s);
+  if (rc) return rc;
+  rc = srv_stop(s);
+  if (rc) return rc;
+  pskv_batch b{keys, out, n};
+  return rows_get_from(s, std::vector<pskv_batch>{b}, flags, DenseView{s->opt_state, s->key_begin, s->range},
+                       "pskv_get_state", /*count_get=*/false);
+}
+
+int pskv_apply_time(pskv_shard* s, uint64_t* launches, double* total_ms, uint64_t* elements) {
+  if (!s) return fail(PSKV_EINVAL, "pskv_apply_time: null shard");
+  int rc = use_device(s);
+  if (rc) return rc;
+  rc = drain_timing(s);
+  if (rc) return rc;
+  if (launches) *launches = s->t_launches[kTimeApply];
+  if (total_ms) *total_ms = s->t_ms[kTimeApply];
+  if (elements) *elements = s->t_elems[kTimeApply];
+  return PSKV_OK;
+}
+
 int pskv_sync(pskv_shard* s) {
   if (!s) return fail(PSKV_EINVAL, "pskv_sync: null shard");
   int rc = use_device(s);
@@ -2332,8 +2565,9 @@ int pskv_sync(pskv_shard* s) {
                 "request was not answered within SYNC_TIMEOUT_MS, or its allocation failed)");
   if (err & kErrRowOutOfRange)
     return fail(PSKV_ESTATE,
-                "row shard: a device Add held out-of-range keys; their rows were dropped (a row shard stores "
-                "no key outside [key_begin, key_end); pskv_clear resets this)");
+                "row shard: a device Add or optimizer step held out-of-range keys; their rows were dropped (a row "
+                "shard, and an optimizer step at any width, stores no key outside [key_begin, key_end); pskv_clear "
+                "resets this)");
   if (2 * (uint64_t)cnt > s->ocap) return grow_overflow(s, cnt);
   return PSKV_OK;
 }
@@ -2349,6 +2583,7 @@ int pskv_clear(pskv_shard* s) {
   PSKV_HIP(hipMemsetAsync(s->cur.keys, 0xFF, s->ocap * sizeof(unsigned long long), s->stream));
   PSKV_HIP(hipMemsetAsync(s->cur.vals, 0, s->ocap * (size_t)s->vb, s->stream));
   PSKV_HIP(hipMemsetAsync(s->ovf.c->stat, 0, 2 * sizeof(uint32_t), s->stream));
+  if (int rc2 = opt_reset_state(s)) return rc2;
   s->ocount_known = 0;
   if (int rc2 = wait_stream(s, s->stream, "shard stream (clear)")) return rc2;
   return PSKV_OK;
@@ -2390,13 +2625,13 @@ int pskv_shard_info(pskv_shard* s, pskv_info* info) {
 
 int pskv_set_timing(pskv_shard* s, int enable) {
   if (!s) return fail(PSKV_EINVAL, "pskv_set_timing: null shard");
-  s->timing_mask = enable ? (1u << PSKV_K_COUNT) - 1 : 0u;
+  s->timing_mask = enable ? (1u << kTimeSlots) - 1 : 0u;
   return PSKV_OK;
 }
 
 int pskv_set_timing_mask(pskv_shard* s, uint32_t kernel_mask) {
   if (!s) return fail(PSKV_EINVAL, "pskv_set_timing_mask: null shard");
-  s->timing_mask = kernel_mask & ((1u << PSKV_K_COUNT) - 1);
+  s->timing_mask = kernel_mask & ((1u << kTimeSlots) - 1);
   return PSKV_OK;
 }
 
@@ -2420,7 +2655,7 @@ int pskv_reset_timing(pskv_shard* s) {
   if (rc) return rc;
   rc = drain_timing(s);
   if (rc) return rc;
-  for (int k = 0; k < PSKV_K_COUNT; ++k) {
+  for (int k = 0; k < kTimeSlots; ++k) {
     s->t_launches[k] = 0;
     s->t_ms[k] = 0;
     s->t_elems[k] = 0;

@@ -187,6 +187,72 @@ class Shard:
             flags |= _lib.PSKV_SORTED_HINT
         check(lib.pskv_add_get_grouped(self._h, ba.arr, ba.n, bg.arr, bg.n, flags))
 
+    # ------------------------------------------------------------ optimizer steps
+    _OPT_KIND = {None: _lib.PSKV_OPT_NONE, "none": _lib.PSKV_OPT_NONE, "sgd": _lib.PSKV_OPT_SGD,
+                 "adagrad": _lib.PSKV_OPT_ADAGRAD}
+    _OPT_NAME = {_lib.PSKV_OPT_NONE: None, _lib.PSKV_OPT_SGD: "sgd", _lib.PSKV_OPT_ADAGRAD: "adagrad"}
+
+    def set_optimizer(self, kind, lr: float = 0.0, weight_decay: float = 0.0, eps: float = 1e-10,
+                      init_accum: float = 0.0):
+        """pskv_shard_set_optimizer: kind "sgd", "adagrad" or None.  The same kind
+        again changes the hyper-parameters of later steps only; another kind
+        resets the accumulator to init_accum."""
+        cfg = _lib.PskvOptimizer(self._OPT_KIND[kind], float(lr), float(weight_decay), float(eps),
+                                 float(init_accum))
+        check(lib.pskv_shard_set_optimizer(self._h, ctypes.byref(cfg)))
+
+    def optimizer(self) -> dict:
+        """The configuration, and `state_bytes`: what the optimizer holds in HBM
+        beyond the dense array."""
+        cfg, nbytes = _lib.PskvOptimizer(), ctypes.c_uint64()
+        check(lib.pskv_shard_get_optimizer(self._h, ctypes.byref(cfg), ctypes.byref(nbytes)))
+        return {"kind": self._OPT_NAME[cfg.kind], "lr": cfg.lr, "weight_decay": cfg.weight_decay,
+                "eps": cfg.eps, "init_accum": cfg.init_accum, "state_bytes": nbytes.value}
+
+    def apply(self, keys, grads):
+        """One optimizer step from one batch of (key, gradient-row) pairs, shaped
+        as add's.  numpy -> host path; torch CUDA tensors -> device path."""
+        if _is_torch(keys):
+            self._check_dev(keys, grads)
+            self._check_dev_count(keys, grads)
+            check(lib.pskv_apply(self._h, keys.data_ptr(), grads.data_ptr(), keys.numel(), _lib.PSKV_DEVICE))
+            return
+        k = self._host_keys(keys)
+        g = self._host_vals(grads, k.size)
+        check(lib.pskv_apply(self._h, k.ctypes.data, g.ctypes.data, k.size, _lib.PSKV_HOST))
+
+    def apply_grouped(self, batches):
+        """ONE optimizer step over every batch: list of (keys, grads) or a BatchSet."""
+        bs = batches if isinstance(batches, BatchSet) else self.prepare(batches)
+        check(lib.pskv_apply_grouped(self._h, bs.arr, bs.n, bs.flags))
+
+    def get_state(self, keys, out=None):
+        """Adagrad's accumulator rows of `keys` (pskv_get_state), as get returns values."""
+        if _is_torch(keys):
+            import torch
+
+            if out is None:
+                shape = (keys.numel(), self.width) if self.width > 1 else keys.numel()
+                out = torch.empty(shape, dtype=_torch_dtype(self.dtype), device=keys.device)
+            self._check_dev(keys, out)
+            self._check_dev_count(keys, out)
+            check(lib.pskv_get_state(self._h, keys.data_ptr(), keys.numel(), out.data_ptr(), _lib.PSKV_DEVICE))
+            return out
+        k = self._host_keys(keys)
+        if out is None:
+            out = np.empty((k.size, self.width) if self.width > 1 else k.size, dtype=self.dtype)
+        elif not (isinstance(out, np.ndarray) and out.dtype == self.dtype and out.flags.c_contiguous
+                  and out.size == k.size * self.width):
+            raise ValueError("get_state: out must be a C-contiguous array of keys * width values")
+        check(lib.pskv_get_state(self._h, k.ctypes.data, k.size, out.ctypes.data, _lib.PSKV_HOST))
+        return out
+
+    def apply_time(self):
+        """Optimizer steps timed as one operation each (pskv_apply_time)."""
+        n, ms, el = ctypes.c_uint64(), ctypes.c_double(), ctypes.c_uint64()
+        check(lib.pskv_apply_time(self._h, ctypes.byref(n), ctypes.byref(ms), ctypes.byref(el)))
+        return {"launches": n.value, "total_ms": ms.value, "elements": el.value}
+
     def _batch_array(self, batches, is_get):
         arr = (_lib.PskvBatch * max(1, len(batches)))()
         keep = []

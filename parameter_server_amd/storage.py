@@ -109,14 +109,25 @@ class HipStorage(AbstractStorage):
     Defaults reproduce the reference's argument-less construction
     (driver/engine.hpp:100-109): the whole uint32 key space, assign semantics.
     width > 1: a row-valued storage, `width` values per key (the value frame
-    of an Add holds keys * width values, row-major, and so does a Get reply)."""
+    of an Add holds keys * width values, row-major, and so does a Get reply).
+    optimizer: a dict for Shard.set_optimizer (kind, lr, ...).  The storage then
+    applies optimizer steps: an Add message carries GRADIENTS and is one step
+    (pskv_apply); AddGrouped, a BSP flush, is one step over all its messages."""
 
     def __init__(self, val_dtype=np.float32, key_begin: int = 0, key_end: int = 1 << 32,
-                 device: int = 0, mode: str = "assign", overflow_slots: int = 0, width: int = 1):
+                 device: int = 0, mode: str = "assign", overflow_slots: int = 0, width: int = 1,
+                 optimizer=None):
         self.val_dtype = np.dtype(val_dtype)
         self.width = int(width)
         self.shard = Shard(key_begin, key_end, self.val_dtype, mode=mode, device=device,
                            overflow_slots=overflow_slots, width=self.width)
+        self.optimizer = dict(optimizer) if optimizer else None
+        if self.optimizer:
+            try:
+                self.shard.set_optimizer(**self.optimizer)
+            except Exception:
+                self.shard.close()
+                raise
 
     def SubAdd(self, typed_keys, vals) -> None:
         typed_vals = typed(vals, self.val_dtype)
@@ -127,7 +138,30 @@ class HipStorage(AbstractStorage):
         else:
             CHECK(typed_keys.size == typed_vals.size,
                   f"CHECK_EQ(typed_keys.size(), typed_vals.size()) failed: {typed_keys.size} vs {typed_vals.size}")
-        self.shard.add(typed_keys, typed_vals)
+        if self.optimizer:
+            self.shard.apply(typed_keys, typed_vals)
+        else:
+            self.shard.add(typed_keys, typed_vals)
+
+    def AddGrouped(self, msgs) -> None:
+        """Every Add message of a flush in one call (include/ps/hip_storage.hpp
+        AddGrouped): pskv_add_grouped, or with an optimizer ONE step over the
+        summed gradients (pskv_apply_grouped)."""
+        batches = []
+        for msg in msgs:
+            CHECK(len(msg.data) == 2, "CHECK(msg.data.size() == 2)")
+            k = typed(msg.data[0], np.uint32)
+            v = typed(msg.data[1], self.val_dtype)
+            CHECK(k.size * self.width == v.size,
+                  f"CHECK_EQ(typed_keys.size() * width, typed_vals.size()) failed: "
+                  f"{k.size} * {self.width} vs {v.size}")
+            batches.append((k, v))
+        if not batches:
+            return
+        if self.optimizer:
+            self.shard.apply_grouped(batches)
+        else:
+            self.shard.add_grouped(batches)
 
     def SubGet(self, typed_keys) -> np.ndarray:
         vals = self.shard.get(np.ascontiguousarray(typed_keys, dtype=np.uint32))
