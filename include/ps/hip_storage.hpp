@@ -25,8 +25,9 @@
 // `width` values; SubAdd takes keys.size() * width values (row-major), SubGet
 // replies with as many.  Such a storage holds only the keys of its range
 // (pskv.h), so construct it with the range the server owns.
-// Optimizer (last constructor argument, pskv_shard_set_optimizer): the storage
-// applies optimizer steps.  SubAdd then carries GRADIENTS and is one step
+// Optimizer (last constructor argument, pskv_shard_set_optimizer; a
+// pskv_optimizer_ex there, pskv_shard_set_optimizer_ex, also gives momentum
+// and Adam): the storage applies optimizer steps.  SubAdd then carries GRADIENTS and is one step
 // (pskv_apply); AddGrouped, the BSP model's flush, is ONE step over the summed
 // gradients of all its messages (pskv_apply_grouped).  Float Val only; keys
 // outside the range abort the call (pskv.h "Optimizer steps").
@@ -82,6 +83,15 @@ class HipStorage : public AbstractStorage {
                                       overflow_slots, &shard_),
                "pskv_shard_create");
     if (optimizer) pskv_check(pskv_shard_set_optimizer(shard_, optimizer), "pskv_shard_set_optimizer");
+  }
+  // The same with the extended configuration (momentum, Adam; every argument given).
+  HipStorage(int device, uint32_t key_begin, uint64_t key_end, int mode, uint64_t overflow_slots, uint32_t width,
+             const pskv_optimizer_ex* optimizer)
+      : width_(width), stepping_(optimizer != nullptr && optimizer->kind != PSKV_OPT_NONE) {
+    pskv_check(pskv_shard_create_rows(device, key_begin, key_end, PskvDtype<Val>::value, mode, width,
+                                      overflow_slots, &shard_),
+               "pskv_shard_create");
+    if (optimizer) pskv_check(pskv_shard_set_optimizer_ex(shard_, optimizer), "pskv_shard_set_optimizer_ex");
   }
   ~HipStorage() override { pskv_shard_destroy(shard_); }
   HipStorage(const HipStorage&) = delete;

@@ -95,8 +95,39 @@
  *     buffers are treated as plain host memory;
  *   - with the resident request server (SERVE = 1) a step first ends the
  *     server, as every stream path of pskv_add / pskv_get does;
- *   - not provided: momentum, Adam, restoring h from a checkpoint, optimizer
- *     state for overflow keys.
+ *   - not provided: optimizer state for overflow keys.
+ *
+ * Momentum and Adam (pskv_shard_set_optimizer_ex).  Steps 1 and
+ * 3 above are unchanged; d = g + weight_decay * p in T, every hyper-parameter
+ * rounded to T once per launch:
+ *   MOMENTUM  slot 0 is v, starting at 0:
+ *               v <- momentum * v + d
+ *               p <- p - lr * v        or, with nesterov,
+ *               p <- p - lr * (d + momentum * v)   (the new v)
+ *   ADAM      slot 0 is m, slot 1 is v, both starting at 0; t is this call's
+ *             step number (1 for the first step after creation, pskv_clear or
+ *             a kind change):
+ *               m <- beta1 * m + (1 - beta1) * d
+ *               v <- beta2 * v + (1 - beta2) * d * d
+ *               p <- p - a * m / (sqrt(v) * b + eps)
+ *             with a = lr / (1 - beta1^t) and b = 1 / sqrt(1 - beta2^t); a, b,
+ *             1 - beta1 and 1 - beta2 are computed on the host in double and
+ *             rounded to T once.  This is LAZY Adam: a key not in the call
+ *             keeps p, m and v bit for bit, and the bias correction follows
+ *             the shard's step count, not the key's.
+ * Step counter: one uint64 per shard on the host, kept for every kind.  Every
+ * pskv_apply / pskv_apply_grouped call that queues work advances it by one,
+ * however many launch groups the call has (all use the same t); a call with no
+ * keys or a refused call (host call with an out-of-range key, no optimizer, bad
+ * argument) does not; a device call that drops out-of-range keys does.  The
+ * same kind again keeps t and the state, another kind resets both; pskv_clear
+ * resets t to 0 and the state to its start values.  pskv_set_step lets a
+ * restored shard continue where the saved one stopped.
+ * State slots (pskv_get_state_slot, pskv_put_state): SGD has none, Adagrad one
+ * (h), momentum one (v), Adam two (m, v).  Saving p and every slot of the
+ * whole range with the step count, and putting them back with pskv_add,
+ * pskv_put_state and pskv_set_step, restores a shard bit for bit.
+ * Not provided: decoupled weight decay (AdamW), amsgrad, per-key step counts.
  *
  * Threading: one shard handle is used by one host thread at a time (the
  * reference calls a storage only from its ServerThread, server_thread.cpp:20-50);
@@ -256,7 +287,13 @@ int pskv_add_get_grouped(pskv_shard* s, const pskv_batch* adds, uint64_t na, con
                          uint64_t ng, int flags);
 
 /* Optimizers (semantics: the header comment, "Optimizer steps"). */
-enum pskv_optimizer_kind { PSKV_OPT_NONE = 0, PSKV_OPT_SGD = 1, PSKV_OPT_ADAGRAD = 2 };
+enum pskv_optimizer_kind {
+  PSKV_OPT_NONE = 0,
+  PSKV_OPT_SGD = 1,
+  PSKV_OPT_ADAGRAD = 2,
+  PSKV_OPT_MOMENTUM = 3, /* only through pskv_shard_set_optimizer_ex */
+  PSKV_OPT_ADAM = 4      /* only through pskv_shard_set_optimizer_ex */
+};
 typedef struct pskv_optimizer {
   int kind;
   double lr;            /* finite, > 0 */
@@ -289,6 +326,42 @@ int pskv_apply_grouped(pskv_shard* s, const pskv_batch* batches, uint64_t nb, in
  * the optimizer is PSKV_OPT_ADAGRAD. */
 int pskv_get_state(pskv_shard* s, const uint32_t* keys, uint64_t n, void* out, int flags);
 
+/* The extended configuration: every kind, PSKV_OPT_MOMENTUM and PSKV_OPT_ADAM
+ * included (rules: the header comment, "Momentum and Adam").  Fields a kind
+ * does not use are ignored. */
+typedef struct pskv_optimizer_ex {
+  uint32_t size;        /* sizeof(pskv_optimizer_ex); any other value is PSKV_EINVAL naming "size" */
+  int kind;             /* NONE, SGD, ADAGRAD, MOMENTUM, ADAM */
+  double lr;            /* as pskv_optimizer */
+  double weight_decay;  /* as pskv_optimizer */
+  double eps;           /* ADAGRAD and ADAM: finite, > 0 */
+  double init_accum;    /* ADAGRAD: finite, >= 0 */
+  double momentum;      /* MOMENTUM: finite, in [0, 1) */
+  int nesterov;         /* MOMENTUM: 0 or 1 */
+  double beta1, beta2;  /* ADAM: finite, in [0, 1) */
+} pskv_optimizer_ex;
+/* As pskv_shard_set_optimizer (validated before the handle; the same kind
+ * again keeps the state and the step count, another kind resets both; every
+ * array is allocated here, PSKV_ENOMEM leaves the shard as it was).  With kind
+ * NONE, SGD or ADAGRAD exactly pskv_shard_set_optimizer. */
+int pskv_shard_set_optimizer_ex(pskv_shard* s, const pskv_optimizer_ex* cfg);
+/* state_bytes: gradient scratch + one dense-sized array per state slot + the
+ * stamp array (8 bytes per key).  (pskv_shard_get_optimizer on a shard with a
+ * new kind fills the fields it has and reports the new kind number.) */
+int pskv_shard_get_optimizer_ex(pskv_shard* s, pskv_optimizer_ex* out, uint64_t* state_bytes);
+/* pskv_get_state with a slot number (slots per kind: SGD 0, Adagrad 1,
+ * momentum 1, Adam 2); a slot the kind lacks is PSKV_EINVAL. */
+int pskv_get_state_slot(pskv_shard* s, int slot, const uint32_t* keys, uint64_t n, void* out, int flags);
+/* Write state rows: a row shard's assign Add aimed at a state array (the last
+ * occurrence of a key wins with its whole row; host and device paths as
+ * pskv_add on a row shard, at any width, 1 included).  Keys outside the range
+ * are refused as pskv_apply refuses them.  For restoring a checkpoint. */
+int pskv_put_state(pskv_shard* s, int slot, const uint32_t* keys, const void* vals, uint64_t n, int flags);
+/* The step counter: the number of steps since creation, pskv_clear or a kind
+ * change (the next step is t + 1). */
+int pskv_get_step(pskv_shard* s, uint64_t* t);
+int pskv_set_step(pskv_shard* s, uint64_t t);
+
 /* Wait for the shard's stream, adopt the overflow table as the kernels left
  * it (freeing arrays a device-side growth replaced; trimming its load to
  * <= 1/2), report sticky device errors.  Every host wait of the library (this one, a host
@@ -304,7 +377,8 @@ int pskv_get_state(pskv_shard* s, const uint32_t* keys, uint64_t n, void* out, i
  * held back the same way: the next call waits for it, bounded.) */
 int pskv_sync(pskv_shard* s);
 /* Zero every value (dense array and overflow table); with an optimizer, also
- * reset h to init_accum. */
+ * reset h to init_accum, the other kinds' state slots to 0 and the step
+ * counter to 0. */
 int pskv_clear(pskv_shard* s);
 
 /* Run the shard's work on an external hipStream_t (NULL = the shard's own

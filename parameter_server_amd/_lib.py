@@ -44,6 +44,7 @@ PSKV_K_COUNT = 14
 PSKV_MAX_WIDTH = 4096
 PSKV_TIME_APPLY = 1 << 14
 PSKV_OPT_NONE, PSKV_OPT_SGD, PSKV_OPT_ADAGRAD = 0, 1, 2
+PSKV_OPT_MOMENTUM, PSKV_OPT_ADAM = 3, 4  # only through pskv_shard_set_optimizer_ex
 KERNEL_NAMES = {
     PSKV_K_GATHER: "k_gather",
     PSKV_K_ASSIGN_SORTED: "k_assign_sorted",
@@ -72,6 +73,8 @@ EXPORTED = [
     "pskv_shard_create_rows", "pskv_shard_width",
     "pskv_shard_set_optimizer", "pskv_shard_get_optimizer", "pskv_apply", "pskv_apply_grouped",
     "pskv_get_state", "pskv_apply_time",
+    "pskv_shard_set_optimizer_ex", "pskv_shard_get_optimizer_ex", "pskv_get_state_slot", "pskv_put_state",
+    "pskv_get_step", "pskv_set_step",
 ]
 
 
@@ -93,6 +96,13 @@ class PskvInfo(ctypes.Structure):
 class PskvOptimizer(ctypes.Structure):
     _fields_ = [("kind", ctypes.c_int), ("lr", ctypes.c_double), ("weight_decay", ctypes.c_double),
                 ("eps", ctypes.c_double), ("init_accum", ctypes.c_double)]
+
+
+class PskvOptimizerEx(ctypes.Structure):
+    _fields_ = [("size", ctypes.c_uint32), ("kind", ctypes.c_int), ("lr", ctypes.c_double),
+                ("weight_decay", ctypes.c_double), ("eps", ctypes.c_double), ("init_accum", ctypes.c_double),
+                ("momentum", ctypes.c_double), ("nesterov", ctypes.c_int), ("beta1", ctypes.c_double),
+                ("beta2", ctypes.c_double)]
 
 
 class PskvError(RuntimeError):
@@ -147,6 +157,12 @@ def _load():
         "pskv_apply_grouped": ([vp, ctypes.POINTER(PskvBatch), u64, i32], i32),
         "pskv_get_state": ([vp, vp, u64, vp, i32], i32),
         "pskv_apply_time": ([vp, ctypes.POINTER(u64), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(u64)], i32),
+        "pskv_shard_set_optimizer_ex": ([vp, ctypes.POINTER(PskvOptimizerEx)], i32),
+        "pskv_shard_get_optimizer_ex": ([vp, ctypes.POINTER(PskvOptimizerEx), ctypes.POINTER(u64)], i32),
+        "pskv_get_state_slot": ([vp, i32, vp, u64, vp, i32], i32),
+        "pskv_put_state": ([vp, i32, vp, vp, u64, i32], i32),
+        "pskv_get_step": ([vp, ctypes.POINTER(u64)], i32),
+        "pskv_set_step": ([vp, u64], i32),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)

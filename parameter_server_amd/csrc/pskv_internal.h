@@ -12,8 +12,9 @@
 //                       slots, sticky error bits}, the growth mailbox
 //   keys[cap]           u64 overflow hash keys, EMPTY = ~0
 //   vals[cap]           overflow values
-//   gsum, h             with an optimizer: gradient scratch and Adagrad's
-//                       accumulator, each shaped as dense
+//   gsum, state slots   with an optimizer: gradient scratch and up to
+//                       two state arrays (Adagrad's h; momentum's v; Adam's m and v),
+//                       each shaped as dense
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -264,12 +265,19 @@ hipError_t launch_row_accumulate(int dtype, const GroupArgs& ga, uint32_t nwg, c
 // Optimizer steps (pskv_apply), float shards of any width
 // (1 included).  The hyper-parameters travel by value, rounded to the value
 // type once per launch, so a change is ordered by the stream.
+// Momentum: mu, nesterov.  Adam: beta1, omb1 = 1 - beta1,
+// beta2, omb2 = 1 - beta2, and the step's bias corrections a = lr / (1 -
+// beta1^t), b = 1 / sqrt(1 - beta2^t), all computed on the host in double.
 struct OptHyper {
   double lr, wd, eps;
+  double mu, beta1, omb1, beta2, omb2, a, b;
+  int nesterov;
 };
 template <typename T>
 struct OptArgs {
   T lr, wd, eps;
+  T mu, beta1, omb1, beta2, omb2, a, b;
+  int nesterov;
 };
 // Behind launch_general_mark (stamp mode) over the same `ga` and epoch: every
 // in-range element that is NOT its key's winner adds its gradient row into
@@ -279,12 +287,13 @@ struct OptArgs {
 hipError_t launch_row_grad_losers(int dtype, const GroupArgs& ga, uint32_t nwg, const DenseView& d, void* gsum,
                                   const unsigned long long* owner, const Ovf& o, uint32_t epoch,
                                   const RowShape& rs, hipStream_t st);
-// Each winner applies the rule (kind: pskv_optimizer_kind, 1 or 2) once to its
+// Each winner applies the rule (kind: pskv_optimizer_kind, 1 to 4) once to its
 // key's row from its own gradient row plus the gsum row, and writes zeros back
-// to the gsum units it read non-zero.  state: Adagrad's accumulator.
+// to the gsum units it read non-zero.  state: slot 0 (Adagrad's h, momentum's
+// v, Adam's m); state2: slot 1 (Adam's v).
 hipError_t launch_row_apply(int dtype, int kind, const GroupArgs& ga, uint32_t nwg, const DenseView& d, void* gsum,
-                            void* state, const unsigned long long* owner, uint32_t epoch, const RowShape& rs,
-                            const OptHyper& hy, hipStream_t st);
+                            void* state, void* state2, const unsigned long long* owner, uint32_t epoch,
+                            const RowShape& rs, const OptHyper& hy, hipStream_t st);
 // p[0..n) = v (float or double by dtype): the accumulator's initial value.
 hipError_t launch_fill(int dtype, void* p, uint64_t n, double v, hipStream_t st);
 

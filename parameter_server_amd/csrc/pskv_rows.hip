@@ -5,7 +5,7 @@
 //   k_row_commit      assign Add: the stamped winner of each key copies its whole row
 //   k_row_accumulate  accumulate Add: one no-return atomic add per element
 //   k_row_grad_losers optimizer step: gradient rows of non-winners summed into gsum
-//   k_row_apply       optimizer step: each key's winner applies SGD / Adagrad once
+//   k_row_apply       optimizer step: each key's winner applies SGD / Adagrad / momentum / Adam once
 //
 // Lane mapping (all of them).  A row is U units long (RowShape); a group of
 // L = min(64, next_pow2(U)) consecutive lanes owns one row at a time, lane l
@@ -294,10 +294,13 @@ __global__ __launch_bounds__(kBlock) void k_row_grad_losers(GroupArgs ga, DenseV
   }
 }
 
-// KIND: 1 = SGD, 2 = Adagrad (pskv_optimizer_kind).  One writer per row.
+// KIND: 1 = SGD, 2 = Adagrad, 3 = momentum, 4 = Adam (pskv_optimizer_kind).
+// One writer per row.  `state` is slot 0 (h / v / m), `state2` slot 1 (Adam's
+// v).  No instantiation spills with kRowsInFlight rows in flight (DESIGN.md
+// §8d has the resource table), Adam's five units per row included.
 template <typename T, int KIND, int V>
 __global__ __launch_bounds__(kBlock) void k_row_apply(GroupArgs ga, DenseView d, T* __restrict__ gsum,
-                                                      T* __restrict__ state,
+                                                      T* __restrict__ state, T* __restrict__ state2,
                                                       const unsigned long long* __restrict__ owner,
                                                       uint32_t epoch, RowShape rs, OptArgs<T> o) {
   const uint32_t lane = threadIdx.x & (rs.lanes - 1u);
@@ -328,7 +331,7 @@ __global__ __launch_bounds__(kBlock) void k_row_apply(GroupArgs ga, DenseView d,
       }
       if (!any) continue;
       for (uint32_t u = lane; u < U; u += rs.lanes) {
-        OptUnit<T, V> g[kRowsInFlight], gs[kRowsInFlight], p[kRowsInFlight], h[kRowsInFlight];
+        OptUnit<T, V> g[kRowsInFlight], gs[kRowsInFlight], p[kRowsInFlight], h[kRowsInFlight], h2[kRowsInFlight];
 #pragma unroll
         for (int r = 0; r < kRowsInFlight; ++r) {
           if (!win[r]) continue;
@@ -336,7 +339,8 @@ __global__ __launch_bounds__(kBlock) void k_row_apply(GroupArgs ga, DenseView d,
           g[r] = load_opt_unit<T, V>(vals, s.i[r] * U + u);
           gs[r] = load_opt_unit<T, V>(gsum, at);
           p[r] = load_opt_unit<T, V>(param, at);
-          if (KIND == 2) h[r] = load_opt_unit<T, V>(state, at);
+          if (KIND >= 2) h[r] = load_opt_unit<T, V>(state, at);
+          if (KIND == 4) h2[r] = load_opt_unit<T, V>(state2, at);
         }
 #pragma unroll
         for (int r = 0; r < kRowsInFlight; ++r) {
@@ -350,13 +354,22 @@ __global__ __launch_bounds__(kBlock) void k_row_apply(GroupArgs ga, DenseView d,
             if (KIND == 2) {
               h[r].e[i] = h[r].e[i] + dd * dd;
               p[r].e[i] = p[r].e[i] - o.lr * (dd / (sqrt(h[r].e[i]) + o.eps));
+            } else if (KIND == 3) {
+              h[r].e[i] = o.mu * h[r].e[i] + dd;
+              const T step = o.nesterov ? dd + o.mu * h[r].e[i] : h[r].e[i];
+              p[r].e[i] = p[r].e[i] - o.lr * step;
+            } else if (KIND == 4) {
+              h[r].e[i] = o.beta1 * h[r].e[i] + o.omb1 * dd;
+              h2[r].e[i] = o.beta2 * h2[r].e[i] + o.omb2 * (dd * dd);
+              p[r].e[i] = p[r].e[i] - o.a * (h[r].e[i] / (sqrt(h2[r].e[i]) * o.b + o.eps));
             } else {
               p[r].e[i] = p[r].e[i] - o.lr * dd;
             }
             gs[r].e[i] = T(0);
           }
           store_opt_unit<T, V>(param, at, p[r]);
-          if (KIND == 2) store_opt_unit<T, V>(state, at, h[r]);
+          if (KIND >= 2) store_opt_unit<T, V>(state, at, h[r]);
+          if (KIND == 4) store_opt_unit<T, V>(state2, at, h2[r]);
           if (dirty) store_opt_unit<T, V>(gsum, at, gs[r]);
         }
       }
@@ -373,15 +386,21 @@ uint32_t row_grid(uint32_t nwg) { return nwg < 4096u ? nwg : 4096u; }
 
 template <typename T, int V>
 void launch_row_apply_kind(int kind, uint32_t grid, const GroupArgs& ga, const DenseView& d, void* gsum, void* state,
-                           const unsigned long long* owner, uint32_t epoch, const RowShape& rs, const OptHyper& hy,
-                           hipStream_t st) {
-  const OptArgs<T> o{(T)hy.lr, (T)hy.wd, (T)hy.eps};
-  if (kind == 2)
-    k_row_apply<T, 2, V><<<grid, kBlock, 0, st>>>(ga, d, static_cast<T*>(gsum), static_cast<T*>(state), owner, epoch,
-                                                  rs, o);
+                           void* state2, const unsigned long long* owner, uint32_t epoch, const RowShape& rs,
+                           const OptHyper& hy, hipStream_t st) {
+  const OptArgs<T> o{(T)hy.lr,   (T)hy.wd,    (T)hy.eps,  (T)hy.mu, (T)hy.beta1,
+                     (T)hy.omb1, (T)hy.beta2, (T)hy.omb2, (T)hy.a,  (T)hy.b,    hy.nesterov};
+  T* g = static_cast<T*>(gsum);
+  T* s1 = static_cast<T*>(state);
+  T* s2 = static_cast<T*>(state2);
+  if (kind == 4)
+    k_row_apply<T, 4, V><<<grid, kBlock, 0, st>>>(ga, d, g, s1, s2, owner, epoch, rs, o);
+  else if (kind == 3)
+    k_row_apply<T, 3, V><<<grid, kBlock, 0, st>>>(ga, d, g, s1, s2, owner, epoch, rs, o);
+  else if (kind == 2)
+    k_row_apply<T, 2, V><<<grid, kBlock, 0, st>>>(ga, d, g, s1, s2, owner, epoch, rs, o);
   else
-    k_row_apply<T, 1, V><<<grid, kBlock, 0, st>>>(ga, d, static_cast<T*>(gsum), static_cast<T*>(state), owner, epoch,
-                                                  rs, o);
+    k_row_apply<T, 1, V><<<grid, kBlock, 0, st>>>(ga, d, g, s1, s2, owner, epoch, rs, o);
 }
 
 }  // namespace
@@ -466,22 +485,23 @@ hipError_t launch_row_grad_losers(int dtype, const GroupArgs& ga, uint32_t nwg, 
 }
 
 hipError_t launch_row_apply(int dtype, int kind, const GroupArgs& ga, uint32_t nwg, const DenseView& d, void* gsum,
-                            void* state, const unsigned long long* owner, uint32_t epoch, const RowShape& rs,
-                            const OptHyper& hy, hipStream_t st) {
+                            void* state, void* state2, const unsigned long long* owner, uint32_t epoch,
+                            const RowShape& rs, const OptHyper& hy, hipStream_t st) {
   if (nwg == 0) return hipSuccess;
-  if ((dtype != 1 && dtype != 2) || (kind != 1 && kind != 2) || (kind == 2 && !state)) return hipErrorInvalidValue;
+  if ((dtype != 1 && dtype != 2) || kind < 1 || kind > 4 || (kind >= 2 && !state) || (kind == 4 && !state2))
+    return hipErrorInvalidValue;
   const uint32_t grid = row_grid(nwg);
   const bool u16 = rs.unit_bytes == 16;
   if (dtype == 1) {
     if (u16)
-      launch_row_apply_kind<float, 4>(kind, grid, ga, d, gsum, state, owner, epoch, rs, hy, st);
+      launch_row_apply_kind<float, 4>(kind, grid, ga, d, gsum, state, state2, owner, epoch, rs, hy, st);
     else
-      launch_row_apply_kind<float, 1>(kind, grid, ga, d, gsum, state, owner, epoch, rs, hy, st);
+      launch_row_apply_kind<float, 1>(kind, grid, ga, d, gsum, state, state2, owner, epoch, rs, hy, st);
   } else {
     if (u16)
-      launch_row_apply_kind<double, 2>(kind, grid, ga, d, gsum, state, owner, epoch, rs, hy, st);
+      launch_row_apply_kind<double, 2>(kind, grid, ga, d, gsum, state, state2, owner, epoch, rs, hy, st);
     else
-      launch_row_apply_kind<double, 1>(kind, grid, ga, d, gsum, state, owner, epoch, rs, hy, st);
+      launch_row_apply_kind<double, 1>(kind, grid, ga, d, gsum, state, state2, owner, epoch, rs, hy, st);
   }
   return hipGetLastError();
 }

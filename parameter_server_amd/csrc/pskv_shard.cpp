@@ -362,11 +362,14 @@ struct pskv_shard {
   uint32_t pend_epoch = 0;
   uint64_t pend_elems = 0;
   // optimizer (pskv_shard_set_optimizer): the configuration, the gradient
-  // scratch (shaped as the dense array, zero between calls) and Adagrad's
-  // accumulator; both allocated when the optimizer is set
-  pskv_optimizer opt{};
+  // scratch (shaped as the dense array, zero between calls) and the kind's
+  // state slots (Adagrad h; momentum v; Adam m, v); all allocated when the
+  // optimizer is set.  opt_step: steps since creation, clear or a kind change.
+  pskv_optimizer_ex opt{};
   void* opt_gsum = nullptr;
-  void* opt_state = nullptr;
+  void* opt_state = nullptr;   // slot 0
+  void* opt_state2 = nullptr;  // slot 1
+  uint64_t opt_step = 0;
 
   DenseView dview() const { return DenseView{dense, key_begin, range}; }
 };
@@ -1591,14 +1594,17 @@ int rows_pieces(pskv_shard* s, const std::vector<pskv_batch>& in, const char* wh
   return PSKV_OK;
 }
 
-int rows_add_device(pskv_shard* s, const std::vector<pskv_batch>& v) {
-  bool vec = row_bytes(s) % 16 == 0 && aligned16(s->dense);
+// `d`: the array written: the dense array in the shard's mode, or
+// (pskv_put_state) one of the optimizer's state arrays, which have the same
+// shape, always as an assign.
+int rows_add_device(pskv_shard* s, const std::vector<pskv_batch>& v, const DenseView& d, int mode) {
+  bool vec = row_bytes(s) % 16 == 0 && aligned16(d.param);
   for (auto& b : v) vec = vec && aligned16(b.vals);
   for (const Span& sp : split_groups(v)) {
     const LaunchGroup g = make_group(v, sp.first, sp.second, kGeneralChunk);
-    if (s->mode == PSKV_ACCUMULATE) {
+    if (mode == PSKV_ACCUMULATE) {
       LaunchTimer t(s, PSKV_K_ROW_ACCUMULATE, g.elems);
-      PSKV_HIP(launch_row_accumulate(s->dtype, g.ga, g.nwg, s->dview(), s->ovf, row_shape(s->width, s->vb, false),
+      PSKV_HIP(launch_row_accumulate(s->dtype, g.ga, g.nwg, d, s->ovf, row_shape(s->width, s->vb, false),
                                      s->stream));
       t.done();
       s->n_general++;
@@ -1607,9 +1613,9 @@ int rows_add_device(pskv_shard* s, const std::vector<pskv_batch>& v) {
     if (int rc = ensure_owner(s)) return rc;
     const uint32_t epoch = next_epoch(s);
     LaunchTimer t(s, PSKV_K_ROW_COMMIT, g.elems);
-    PSKV_HIP(launch_general_mark(s->dtype, PSKV_ASSIGN, g.ga, g.nwg, s->dview(), s->flag + 1, s->owner, nullptr,
-                                 epoch, s->stream));
-    PSKV_HIP(launch_row_commit(s->vb, g.ga, g.nwg, s->dview(), s->owner, s->ovf, epoch,
+    PSKV_HIP(launch_general_mark(s->dtype, PSKV_ASSIGN, g.ga, g.nwg, d, s->flag + 1, s->owner, nullptr, epoch,
+                                 s->stream));
+    PSKV_HIP(launch_row_commit(s->vb, g.ga, g.nwg, d, s->owner, s->ovf, epoch,
                                row_shape(s->width, s->vb, vec), s->stream));
     t.done();
     s->n_general += 2;
@@ -1617,14 +1623,17 @@ int rows_add_device(pskv_shard* s, const std::vector<pskv_batch>& v) {
   return PSKV_OK;
 }
 
-int rows_add(pskv_shard* s, const std::vector<pskv_batch>& in, int flags) {
+// `what`: the call's name in messages; `refusal`, `why`: what stands in front
+// of and behind an out-of-range key.
+int rows_add_to(pskv_shard* s, const std::vector<pskv_batch>& in, int flags, const DenseView& d, int mode,
+                const char* what, const char* refusal, const char* why, bool count_add) {
   std::vector<pskv_batch> v;
-  if (int rc = rows_pieces(s, in, "pskv_add", &v)) return rc;
-  s->n_add++;
+  if (int rc = rows_pieces(s, in, what, &v)) return rc;
+  if (count_add) s->n_add++;
   if (v.empty()) return PSKV_OK;
   int rc = use_device(s);
   if (rc) return rc;
-  if (flags & PSKV_DEVICE) return rows_add_device(s, v);
+  if (flags & PSKV_DEVICE) return rows_add_device(s, v, d, mode);
   // the keys are checked before anything is queued: nothing is applied
   for (const auto& b : v) {
     Piece p{};
@@ -1632,16 +1641,21 @@ int rows_add(pskv_shard* s, const std::vector<pskv_batch>& in, int flags) {
     if (!p.outside) continue;
     for (uint64_t i = 0; i < b.n; ++i)
       if ((uint64_t)(uint32_t)(b.keys[i] - s->key_begin) >= s->range)
-        return fail(PSKV_EINVAL, "pskv_add: row shard: key " + std::to_string(b.keys[i]) +
-                                     " is outside [key_begin, key_end); a row shard stores no out-of-range "
-                                     "keys (nothing was applied)");
+        return fail(PSKV_EINVAL, std::string(what) + ": " + refusal + " " + std::to_string(b.keys[i]) +
+                                     " is outside [key_begin, key_end); " + why +
+                                     " (nothing was applied)");
   }
   // the call returns before its DMA: the hold stays armed
   HstageHold hold(s);
   std::vector<pskv_batch> dv;
   rc = stage_keys_first(s, v, stage_layout(v, row_bytes(s), StageOrder::kKeysFirst), row_bytes(s),
                         /*with_values=*/true, hold, &dv);
-  return rc ? rc : rows_add_device(s, dv);
+  return rc ? rc : rows_add_device(s, dv, d, mode);
+}
+
+int rows_add(pskv_shard* s, const std::vector<pskv_batch>& in, int flags) {
+  return rows_add_to(s, in, flags, s->dview(), s->mode, "pskv_add", "row shard: key",
+                     "a row shard stores no out-of-range keys", /*count_add=*/true);
 }
 
 // `d`: the array gathered from: the dense array, or (pskv_get_state) the
@@ -1702,19 +1716,35 @@ int rows_get(pskv_shard* s, const std::vector<pskv_batch>& in, int flags) {
 // All marks come first: a key's stamp then belongs to the last group that
 // holds it, the key's elements in earlier groups all see a foreign stamp and
 // go to gsum, and exactly one element of the call applies the rule.
+// Momentum and Adam add a second state array, the step
+// counter opt_step (one per call: Adam's bias corrections are computed from it
+// here, in double) and pskv_put_state, the row assign Add aimed at a state array.
 size_t opt_array_bytes(const pskv_shard* s) { return s->range * row_bytes(s); }
 
-// The accumulator back to init_accum, the gradient scratch to zero (stream-ordered).
+// State slots per kind (pskv_optimizer_kind).
+int opt_slots(int kind) {
+  return kind == PSKV_OPT_ADAM ? 2 : (kind == PSKV_OPT_ADAGRAD || kind == PSKV_OPT_MOMENTUM) ? 1 : 0;
+}
+
+// The state back to its start values (Adagrad's h: init_accum; every other
+// slot: 0), the gradient scratch to zero (stream-ordered), the step count to 0.
 int opt_reset_state(pskv_shard* s) {
+  s->opt_step = 0;
   if (s->opt_gsum) PSKV_HIP(hipMemsetAsync(s->opt_gsum, 0, opt_array_bytes(s), s->stream));
-  if (s->opt_state)
-    PSKV_HIP(launch_fill(s->dtype, s->opt_state, s->range * (uint64_t)s->width, s->opt.init_accum, s->stream));
+  if (s->opt_state) {
+    if (s->opt.kind == PSKV_OPT_ADAGRAD)
+      PSKV_HIP(launch_fill(s->dtype, s->opt_state, s->range * (uint64_t)s->width, s->opt.init_accum, s->stream));
+    else
+      PSKV_HIP(hipMemsetAsync(s->opt_state, 0, opt_array_bytes(s), s->stream));
+  }
+  if (s->opt_state2) PSKV_HIP(hipMemsetAsync(s->opt_state2, 0, opt_array_bytes(s), s->stream));
   return PSKV_OK;
 }
 
 int apply_device(pskv_shard* s, const std::vector<pskv_batch>& v) {
   if (int rc = ensure_owner(s)) return rc;
-  bool vec = row_bytes(s) % 16 == 0 && aligned16(s->dense) && aligned16(s->opt_gsum) && aligned16(s->opt_state);
+  bool vec = row_bytes(s) % 16 == 0 && aligned16(s->dense) && aligned16(s->opt_gsum) && aligned16(s->opt_state) &&
+             aligned16(s->opt_state2);
   for (auto& b : v) vec = vec && aligned16(b.vals);
   const std::vector<Span> spans = split_groups(v);
   std::vector<LaunchGroup> groups;
@@ -1728,7 +1758,23 @@ int apply_device(pskv_shard* s, const std::vector<pskv_batch>& v) {
     epochs.push_back(next_epoch(s));
     elems += groups.back().elems;
   }
-  const OptHyper hy{s->opt.lr, s->opt.weight_decay, s->opt.eps};
+  // one step number for the whole call, whatever its launch groups
+  const uint64_t step = ++s->opt_step;
+  OptHyper hy{};
+  hy.lr = s->opt.lr;
+  hy.wd = s->opt.weight_decay;
+  hy.eps = s->opt.eps;
+  if (s->opt.kind == PSKV_OPT_MOMENTUM) {
+    hy.mu = s->opt.momentum;
+    hy.nesterov = s->opt.nesterov;
+  } else if (s->opt.kind == PSKV_OPT_ADAM) {
+    hy.beta1 = s->opt.beta1;
+    hy.beta2 = s->opt.beta2;
+    hy.omb1 = 1.0 - s->opt.beta1;
+    hy.omb2 = 1.0 - s->opt.beta2;
+    hy.a = s->opt.lr / (1.0 - std::pow(s->opt.beta1, (double)step));
+    hy.b = 1.0 / std::sqrt(1.0 - std::pow(s->opt.beta2, (double)step));
+  }
   const RowShape rs1 = row_shape(s->width, s->vb, false);
   const RowShape rsv = row_shape(s->width, s->vb, vec);
   LaunchTimer t(s, kTimeApply, elems);
@@ -1741,7 +1787,7 @@ int apply_device(pskv_shard* s, const std::vector<pskv_batch>& v) {
                                     epochs[i], rs1, s->stream));
   for (size_t i = 0; i < groups.size(); ++i)
     PSKV_HIP(launch_row_apply(s->dtype, s->opt.kind, groups[i].ga, groups[i].nwg, s->dview(), s->opt_gsum,
-                              s->opt_state, s->owner, epochs[i], rsv, hy, s->stream));
+                              s->opt_state, s->opt_state2, s->owner, epochs[i], rsv, hy, s->stream));
   t.done();
   s->n_general += 3 * groups.size();
   return PSKV_OK;
@@ -1791,6 +1837,31 @@ const char* opt_config_error(const pskv_optimizer* c) {
   if (c->kind == PSKV_OPT_ADAGRAD) {
     if (!std::isfinite(c->eps) || !(c->eps > 0)) return "eps must be finite and > 0";
     if (!std::isfinite(c->init_accum) || !(c->init_accum >= 0)) return "init_accum must be finite and >= 0";
+  }
+  return nullptr;
+}
+
+// The same for the extended configuration (fields a kind does not use are ignored).
+const char* opt_config_error_ex(const pskv_optimizer_ex* c) {
+  if (!c) return "null configuration";
+  if (c->size != sizeof(pskv_optimizer_ex)) return "size must be sizeof(pskv_optimizer_ex)";
+  if (c->kind < PSKV_OPT_NONE || c->kind > PSKV_OPT_ADAM)
+    return "kind must be PSKV_OPT_NONE, PSKV_OPT_SGD, PSKV_OPT_ADAGRAD, PSKV_OPT_MOMENTUM or PSKV_OPT_ADAM";
+  if (c->kind == PSKV_OPT_NONE) return nullptr;
+  if (!std::isfinite(c->lr) || !(c->lr > 0)) return "lr must be finite and > 0";
+  if (!std::isfinite(c->weight_decay) || !(c->weight_decay >= 0)) return "weight_decay must be finite and >= 0";
+  if (c->kind == PSKV_OPT_ADAGRAD || c->kind == PSKV_OPT_ADAM)
+    if (!std::isfinite(c->eps) || !(c->eps > 0)) return "eps must be finite and > 0";
+  if (c->kind == PSKV_OPT_ADAGRAD)
+    if (!std::isfinite(c->init_accum) || !(c->init_accum >= 0)) return "init_accum must be finite and >= 0";
+  if (c->kind == PSKV_OPT_MOMENTUM) {
+    if (!std::isfinite(c->momentum) || !(c->momentum >= 0) || !(c->momentum < 1))
+      return "momentum must be finite and in [0, 1)";
+    if (c->nesterov != 0 && c->nesterov != 1) return "nesterov must be 0 or 1";
+  }
+  if (c->kind == PSKV_OPT_ADAM) {
+    if (!std::isfinite(c->beta1) || !(c->beta1 >= 0) || !(c->beta1 < 1)) return "beta1 must be finite and in [0, 1)";
+    if (!std::isfinite(c->beta2) || !(c->beta2 >= 0) || !(c->beta2 < 1)) return "beta2 must be finite and in [0, 1)";
   }
   return nullptr;
 }
@@ -2221,6 +2292,92 @@ int apply_env_options(pskv_shard* s) {
   return PSKV_OK;
 }
 
+// Both setters end here, with a validated configuration.
+int set_optimizer_impl(pskv_shard* s, const pskv_optimizer_ex& cfg, const std::string& who) {
+  if (!s) return fail(PSKV_EINVAL, who + ": null shard");
+  if (cfg.kind != PSKV_OPT_NONE && s->dtype != PSKV_F32 && s->dtype != PSKV_F64)
+    return fail(PSKV_EINVAL, who + ": optimizers need a float shard (PSKV_F32, PSKV_F64)");
+  int rc = use_device(s);
+  if (rc) return rc;
+  if (cfg.kind == s->opt.kind) {  // hyper-parameters only: they travel by value with each later launch
+    s->opt = cfg;
+    return PSKV_OK;
+  }
+  // a change of kind: allocate what the new kind needs before anything is
+  // given up, so a failure leaves the shard as it was
+  const size_t bytes = opt_array_bytes(s);
+  const int slots = opt_slots(cfg.kind);
+  void* gsum = s->opt_gsum;
+  void* state[2] = {nullptr, nullptr};
+  auto give_back = [&]() {
+    if (gsum && gsum != s->opt_gsum) (void)hipFree(gsum);
+    for (void* p : state)
+      if (p) (void)hipFree(p);
+  };
+  if (cfg.kind != PSKV_OPT_NONE) {
+    if (!gsum && hipMalloc(&gsum, bytes) != hipSuccess) {
+      gsum = nullptr;
+      return fail(PSKV_ENOMEM, who + ": gradient scratch allocation failed");
+    }
+    for (int i = 0; i < slots; ++i)
+      if (hipMalloc(&state[i], bytes) != hipSuccess) {
+        state[i] = nullptr;
+        give_back();
+        return fail(PSKV_ENOMEM, who + ": state allocation failed");
+      }
+    if ((rc = ensure_owner(s))) {
+      give_back();
+      return rc;
+    }
+  }
+  // queued steps may still use the arrays that go
+  if (s->opt_state || (cfg.kind == PSKV_OPT_NONE && s->opt_gsum)) {
+    if ((rc = srv_stop(s)) || (rc = wait_stream(s, s->stream, "shard stream (optimizer change)"))) {
+      give_back();
+      return rc;
+    }
+    if (s->opt_state) (void)hipFree(s->opt_state);
+    if (s->opt_state2) (void)hipFree(s->opt_state2);
+    s->opt_state = s->opt_state2 = nullptr;
+    if (cfg.kind == PSKV_OPT_NONE) {
+      (void)hipFree(s->opt_gsum);
+      gsum = nullptr;
+    }
+  }
+  s->opt_gsum = gsum;
+  s->opt_state = state[0];
+  s->opt_state2 = state[1];
+  s->opt = cfg;
+  return opt_reset_state(s);
+}
+
+uint64_t opt_state_bytes(const pskv_shard* s) {
+  if (s->opt.kind == PSKV_OPT_NONE) return 0;
+  // gradient scratch + one array per state slot + the stamp array (8 bytes per key)
+  return (uint64_t)(1 + opt_slots(s->opt.kind)) * opt_array_bytes(s) + s->range * sizeof(unsigned long long);
+}
+
+// The state array of `slot`, or null with the error set.
+void* opt_slot_array(pskv_shard* s, int slot, const char* who) {
+  if (slot < 0 || slot >= opt_slots(s->opt.kind)) {
+    (void)fail(PSKV_EINVAL, std::string(who) + ": the shard's optimizer has no state slot " + std::to_string(slot) +
+                                " (slots: SGD 0, Adagrad 1, momentum 1, Adam 2)");
+    return nullptr;
+  }
+  return slot == 0 ? s->opt_state : s->opt_state2;
+}
+
+// A Get on the state array `arr` (pskv_get_state, pskv_get_state_slot).
+int state_get(pskv_shard* s, void* arr, const uint32_t* keys, uint64_t n, void* out, int flags, const char* who) {
+  int rc = use_device(s);
+  if (rc) return rc;
+  rc = srv_stop(s);
+  if (rc) return rc;
+  pskv_batch b{keys, out, n};
+  return rows_get_from(s, std::vector<pskv_batch>{b}, flags, DenseView{arr, s->key_begin, s->range}, who,
+                       /*count_get=*/false);
+}
+
 }  // namespace
 
 extern "C" {
@@ -2380,6 +2537,7 @@ int pskv_shard_destroy(pskv_shard* s) {
   if (s->owner) (void)hipFree(s->owner);
   if (s->opt_gsum) (void)hipFree(s->opt_gsum);
   if (s->opt_state) (void)hipFree(s->opt_state);
+  if (s->opt_state2) (void)hipFree(s->opt_state2);
   if (s->flag) (void)hipFree(s->flag);
   for (const auto& t : s->tables) {  // (the service no longer touches the list)
     (void)hipFree(t.keys);
@@ -2448,65 +2606,55 @@ int pskv_shard_set_optimizer(pskv_shard* s, const pskv_optimizer* cfg) {
   // the configuration first: a bad field is reported whatever the handle
   if (const char* what = opt_config_error(cfg))
     return fail(PSKV_EINVAL, std::string("pskv_shard_set_optimizer: ") + what);
-  if (!s) return fail(PSKV_EINVAL, "pskv_shard_set_optimizer: null shard");
-  if (cfg->kind != PSKV_OPT_NONE && s->dtype != PSKV_F32 && s->dtype != PSKV_F64)
-    return fail(PSKV_EINVAL, "pskv_shard_set_optimizer: optimizers need a float shard (PSKV_F32, PSKV_F64)");
-  int rc = use_device(s);
-  if (rc) return rc;
-  if (cfg->kind == s->opt.kind) {  // hyper-parameters only: they travel by value with each later launch
-    s->opt = *cfg;
-    return PSKV_OK;
-  }
-  // a change of kind: allocate what the new kind needs before anything is
-  // given up, so a failure leaves the shard as it was
-  const size_t bytes = opt_array_bytes(s);
-  void* gsum = s->opt_gsum;
-  void* state = nullptr;
-  if (cfg->kind != PSKV_OPT_NONE) {
-    if (!gsum && hipMalloc(&gsum, bytes) != hipSuccess)
-      return fail(PSKV_ENOMEM, "pskv_shard_set_optimizer: gradient scratch allocation failed");
-    if (cfg->kind == PSKV_OPT_ADAGRAD && hipMalloc(&state, bytes) != hipSuccess) {
-      if (gsum != s->opt_gsum) (void)hipFree(gsum);
-      return fail(PSKV_ENOMEM, "pskv_shard_set_optimizer: accumulator allocation failed");
-    }
-    if ((rc = ensure_owner(s))) {
-      if (gsum != s->opt_gsum) (void)hipFree(gsum);
-      if (state) (void)hipFree(state);
-      return rc;
-    }
-  }
-  // queued steps may still use the arrays that go
-  if (s->opt_state || (cfg->kind == PSKV_OPT_NONE && s->opt_gsum)) {
-    if ((rc = srv_stop(s)) || (rc = wait_stream(s, s->stream, "shard stream (optimizer change)"))) {
-      if (gsum != s->opt_gsum) (void)hipFree(gsum);
-      if (state) (void)hipFree(state);
-      return rc;
-    }
-    if (s->opt_state) (void)hipFree(s->opt_state);
-    s->opt_state = nullptr;
-    if (cfg->kind == PSKV_OPT_NONE) {
-      (void)hipFree(s->opt_gsum);
-      gsum = nullptr;
-    }
-  }
-  s->opt_gsum = gsum;
-  s->opt_state = state;
-  s->opt = *cfg;
-  return opt_reset_state(s);
+  pskv_optimizer_ex x{};
+  x.size = sizeof(x);
+  x.kind = cfg->kind;
+  x.lr = cfg->lr;
+  x.weight_decay = cfg->weight_decay;
+  x.eps = cfg->eps;
+  x.init_accum = cfg->init_accum;
+  return set_optimizer_impl(s, x, "pskv_shard_set_optimizer");
+}
+
+int pskv_shard_set_optimizer_ex(pskv_shard* s, const pskv_optimizer_ex* cfg) {
+  if (const char* what = opt_config_error_ex(cfg))
+    return fail(PSKV_EINVAL, std::string("pskv_shard_set_optimizer_ex: ") + what);
+  return set_optimizer_impl(s, *cfg, "pskv_shard_set_optimizer_ex");
 }
 
 int pskv_shard_get_optimizer(pskv_shard* s, pskv_optimizer* out, uint64_t* state_bytes) {
   if (!s) return fail(PSKV_EINVAL, "pskv_shard_get_optimizer: null shard");
-  if (out) *out = s->opt;
-  if (state_bytes) {
-    // gradient scratch + accumulator (Adagrad) + the stamp array (8 bytes per key)
-    uint64_t b = 0;
-    if (s->opt.kind != PSKV_OPT_NONE) {
-      b = opt_array_bytes(s) + s->range * sizeof(unsigned long long);
-      if (s->opt.kind == PSKV_OPT_ADAGRAD) b += opt_array_bytes(s);
-    }
-    *state_bytes = b;
+  if (out) {
+    out->kind = s->opt.kind;
+    out->lr = s->opt.lr;
+    out->weight_decay = s->opt.weight_decay;
+    out->eps = s->opt.eps;
+    out->init_accum = s->opt.init_accum;
   }
+  if (state_bytes) *state_bytes = opt_state_bytes(s);
+  return PSKV_OK;
+}
+
+int pskv_shard_get_optimizer_ex(pskv_shard* s, pskv_optimizer_ex* out, uint64_t* state_bytes) {
+  if (!s) return fail(PSKV_EINVAL, "pskv_shard_get_optimizer_ex: null shard");
+  if (out) {
+    *out = s->opt;
+    out->size = sizeof(pskv_optimizer_ex);
+  }
+  if (state_bytes) *state_bytes = opt_state_bytes(s);
+  return PSKV_OK;
+}
+
+int pskv_get_step(pskv_shard* s, uint64_t* t) {
+  if (!s) return fail(PSKV_EINVAL, "pskv_get_step: null shard");
+  if (!t) return fail(PSKV_EINVAL, "pskv_get_step: null output");
+  *t = s->opt_step;
+  return PSKV_OK;
+}
+
+int pskv_set_step(pskv_shard* s, uint64_t t) {
+  if (!s) return fail(PSKV_EINVAL, "pskv_set_step: null shard");
+  s->opt_step = t;
   return PSKV_OK;
 }
 
@@ -2528,14 +2676,32 @@ int pskv_get_state(pskv_shard* s, const uint32_t* keys, uint64_t n, void* out, i
   if (!s) return fail(PSKV_EINVAL, "pskv_get_state: null shard");
   if (bad_flags(flags)) return fail(PSKV_EINVAL, "pskv_get_state: unknown flags");
   if (s->opt.kind != PSKV_OPT_ADAGRAD || !s->opt_state)
-    return fail(PSKV_EINVAL, "pskv_get_state: the shard's optimizer keeps no state (only PSKV_OPT_ADAGRAD does)");
+    return fail(PSKV_EINVAL, "pskv_get_state: the shard's optimizer is not PSKV_OPT_ADAGRAD (the other kinds' state: "
+                             "pskv_get_state_slot)");
+  return state_get(s, s->opt_state, keys, n, out, flags, "pskv_get_state");
+}
+
+int pskv_get_state_slot(pskv_shard* s, int slot, const uint32_t* keys, uint64_t n, void* out, int flags) {
+  if (!s) return fail(PSKV_EINVAL, "pskv_get_state_slot: null shard");
+  if (bad_flags(flags)) return fail(PSKV_EINVAL, "pskv_get_state_slot: unknown flags");
+  void* arr = opt_slot_array(s, slot, "pskv_get_state_slot");
+  if (!arr) return PSKV_EINVAL;
+  return state_get(s, arr, keys, n, out, flags, "pskv_get_state_slot");
+}
+
+int pskv_put_state(pskv_shard* s, int slot, const uint32_t* keys, const void* vals, uint64_t n, int flags) {
+  if (!s) return fail(PSKV_EINVAL, "pskv_put_state: null shard");
+  if (bad_flags(flags)) return fail(PSKV_EINVAL, "pskv_put_state: unknown flags");
+  void* arr = opt_slot_array(s, slot, "pskv_put_state");
+  if (!arr) return PSKV_EINVAL;
   int rc = use_device(s);
   if (rc) return rc;
   rc = srv_stop(s);
   if (rc) return rc;
-  pskv_batch b{keys, out, n};
-  return rows_get_from(s, std::vector<pskv_batch>{b}, flags, DenseView{s->opt_state, s->key_begin, s->range},
-                       "pskv_get_state", /*count_get=*/false);
+  pskv_batch b{keys, const_cast<void*>(vals), n};
+  return rows_add_to(s, std::vector<pskv_batch>{b}, flags, DenseView{arr, s->key_begin, s->range}, PSKV_ASSIGN,
+                     "pskv_put_state", "key", "optimizer state is kept for the shard's own keys only",
+                     /*count_add=*/false);
 }
 
 int pskv_apply_time(pskv_shard* s, uint64_t* launches, double* total_ms, uint64_t* elements) {

@@ -189,25 +189,40 @@ class Shard:
 
     # ------------------------------------------------------------ optimizer steps
     _OPT_KIND = {None: _lib.PSKV_OPT_NONE, "none": _lib.PSKV_OPT_NONE, "sgd": _lib.PSKV_OPT_SGD,
-                 "adagrad": _lib.PSKV_OPT_ADAGRAD}
-    _OPT_NAME = {_lib.PSKV_OPT_NONE: None, _lib.PSKV_OPT_SGD: "sgd", _lib.PSKV_OPT_ADAGRAD: "adagrad"}
+                 "adagrad": _lib.PSKV_OPT_ADAGRAD, "momentum": _lib.PSKV_OPT_MOMENTUM, "adam": _lib.PSKV_OPT_ADAM}
+    _OPT_NAME = {_lib.PSKV_OPT_NONE: None, _lib.PSKV_OPT_SGD: "sgd", _lib.PSKV_OPT_ADAGRAD: "adagrad",
+                 _lib.PSKV_OPT_MOMENTUM: "momentum", _lib.PSKV_OPT_ADAM: "adam"}
+    _OPT_SLOTS = {None: 0, "sgd": 0, "adagrad": 1, "momentum": 1, "adam": 2}
 
     def set_optimizer(self, kind, lr: float = 0.0, weight_decay: float = 0.0, eps: float = 1e-10,
-                      init_accum: float = 0.0):
-        """pskv_shard_set_optimizer: kind "sgd", "adagrad" or None.  The same kind
-        again changes the hyper-parameters of later steps only; another kind
-        resets the accumulator to init_accum."""
-        cfg = _lib.PskvOptimizer(self._OPT_KIND[kind], float(lr), float(weight_decay), float(eps),
-                                 float(init_accum))
+                      init_accum: float = 0.0, momentum: float = 0.0, nesterov: bool = False,
+                      beta1: float = 0.9, beta2: float = 0.999):
+        """pskv_shard_set_optimizer(_ex): kind "sgd", "adagrad", "momentum", "adam" or
+        None.  The same kind again changes the hyper-parameters of later steps
+        only (state and step count stay); another kind resets both."""
+        code = self._OPT_KIND[kind]
+        if code in (_lib.PSKV_OPT_MOMENTUM, _lib.PSKV_OPT_ADAM):
+            cfg = _lib.PskvOptimizerEx(ctypes.sizeof(_lib.PskvOptimizerEx), code, float(lr), float(weight_decay),
+                                       float(eps), float(init_accum), float(momentum), int(nesterov), float(beta1),
+                                       float(beta2))
+            check(lib.pskv_shard_set_optimizer_ex(self._h, ctypes.byref(cfg)))
+            return
+        cfg = _lib.PskvOptimizer(code, float(lr), float(weight_decay), float(eps), float(init_accum))
         check(lib.pskv_shard_set_optimizer(self._h, ctypes.byref(cfg)))
 
     def optimizer(self) -> dict:
         """The configuration, and `state_bytes`: what the optimizer holds in HBM
-        beyond the dense array."""
-        cfg, nbytes = _lib.PskvOptimizer(), ctypes.c_uint64()
-        check(lib.pskv_shard_get_optimizer(self._h, ctypes.byref(cfg), ctypes.byref(nbytes)))
-        return {"kind": self._OPT_NAME[cfg.kind], "lr": cfg.lr, "weight_decay": cfg.weight_decay,
-                "eps": cfg.eps, "init_accum": cfg.init_accum, "state_bytes": nbytes.value}
+        beyond the dense array.  "momentum" adds momentum and nesterov, "adam"
+        beta1 and beta2."""
+        cfg, nbytes = _lib.PskvOptimizerEx(), ctypes.c_uint64()
+        check(lib.pskv_shard_get_optimizer_ex(self._h, ctypes.byref(cfg), ctypes.byref(nbytes)))
+        d = {"kind": self._OPT_NAME[cfg.kind], "lr": cfg.lr, "weight_decay": cfg.weight_decay,
+             "eps": cfg.eps, "init_accum": cfg.init_accum, "state_bytes": nbytes.value}
+        if cfg.kind == _lib.PSKV_OPT_MOMENTUM:
+            d.update(momentum=cfg.momentum, nesterov=bool(cfg.nesterov))
+        elif cfg.kind == _lib.PSKV_OPT_ADAM:
+            d.update(beta1=cfg.beta1, beta2=cfg.beta2)
+        return d
 
     def apply(self, keys, grads):
         """One optimizer step from one batch of (key, gradient-row) pairs, shaped
@@ -226,8 +241,9 @@ class Shard:
         bs = batches if isinstance(batches, BatchSet) else self.prepare(batches)
         check(lib.pskv_apply_grouped(self._h, bs.arr, bs.n, bs.flags))
 
-    def get_state(self, keys, out=None):
-        """Adagrad's accumulator rows of `keys` (pskv_get_state), as get returns values."""
+    def get_state(self, keys, out=None, slot: int = 0):
+        """The rows of `keys` in state slot `slot` (pskv_get_state_slot; Adagrad
+        h, momentum v, Adam m and v), as get returns values."""
         if _is_torch(keys):
             import torch
 
@@ -236,7 +252,8 @@ class Shard:
                 out = torch.empty(shape, dtype=_torch_dtype(self.dtype), device=keys.device)
             self._check_dev(keys, out)
             self._check_dev_count(keys, out)
-            check(lib.pskv_get_state(self._h, keys.data_ptr(), keys.numel(), out.data_ptr(), _lib.PSKV_DEVICE))
+            check(lib.pskv_get_state_slot(self._h, int(slot), keys.data_ptr(), keys.numel(), out.data_ptr(),
+                                          _lib.PSKV_DEVICE))
             return out
         k = self._host_keys(keys)
         if out is None:
@@ -244,8 +261,52 @@ class Shard:
         elif not (isinstance(out, np.ndarray) and out.dtype == self.dtype and out.flags.c_contiguous
                   and out.size == k.size * self.width):
             raise ValueError("get_state: out must be a C-contiguous array of keys * width values")
-        check(lib.pskv_get_state(self._h, k.ctypes.data, k.size, out.ctypes.data, _lib.PSKV_HOST))
+        check(lib.pskv_get_state_slot(self._h, int(slot), k.ctypes.data, k.size, out.ctypes.data, _lib.PSKV_HOST))
         return out
+
+    def put_state(self, keys, vals, slot: int = 0):
+        """Write state rows (pskv_put_state): shaped as add's, the last occurrence
+        of a key wins with its whole row."""
+        if _is_torch(keys):
+            self._check_dev(keys, vals)
+            self._check_dev_count(keys, vals)
+            check(lib.pskv_put_state(self._h, int(slot), keys.data_ptr(), vals.data_ptr(), keys.numel(),
+                                     _lib.PSKV_DEVICE))
+            return
+        k = self._host_keys(keys)
+        v = self._host_vals(vals, k.size)
+        check(lib.pskv_put_state(self._h, int(slot), k.ctypes.data, v.ctypes.data, k.size, _lib.PSKV_HOST))
+
+    @property
+    def step(self) -> int:
+        """Optimizer steps since creation, clear or a kind change (pskv_get_step)."""
+        t = ctypes.c_uint64()
+        check(lib.pskv_get_step(self._h, ctypes.byref(t)))
+        return t.value
+
+    @step.setter
+    def step(self, t: int):
+        check(lib.pskv_set_step(self._h, int(t)))
+
+    def state_dict(self) -> dict:
+        """A checkpoint: the whole range's parameters, every state slot and the
+        step count, as host arrays."""
+        keys = np.arange(self.key_begin, self.key_end, dtype=np.int64).astype(np.uint32)
+        o = self.optimizer()
+        return {"p": self.get(keys), "slots": [self.get_state(keys, slot=i) for i in range(self._OPT_SLOTS[o["kind"]])],
+                "t": self.step, "optimizer": o}
+
+    def load_state_dict(self, d: dict):
+        """Restore state_dict()'s checkpoint into a shard of the same range,
+        width, dtype and optimizer kind."""
+        keys = np.arange(self.key_begin, self.key_end, dtype=np.int64).astype(np.uint32)
+        kind = self.optimizer()["kind"]
+        if len(d["slots"]) != self._OPT_SLOTS[kind]:
+            raise ValueError(f"load_state_dict: {len(d['slots'])} state slots for optimizer {kind!r}")
+        self.add(keys, d["p"])
+        for i, v in enumerate(d["slots"]):
+            self.put_state(keys, v, slot=i)
+        self.step = d["t"]
 
     def apply_time(self):
         """Optimizer steps timed as one operation each (pskv_apply_time)."""

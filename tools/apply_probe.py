@@ -5,7 +5,9 @@ WARMUP.  Every call is timed twice: by the library's own timers and by HIP
 events around the whole step (on the legacy default stream, which the shard's
 blocking stream orders against).
 
-  --leg apply      one Adagrad pskv_apply per call
+  --leg apply      one pskv_apply per call; --kind adagrad (default), momentum
+                   or adam selects the rule (momentum 0.9, Adam's
+                   betas 0.9 / 0.999)
                    --dups D: a call of the same size with D occurrences per
                    key (KEYS / D distinct keys, shuffled): prices the loser atomics
   --leg roundtrip  what a worker must do without optimizer steps for the same
@@ -37,9 +39,10 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LR, WD, EPS, INIT_ACCUM = 0.05, 0.0, 1e-8, 0.1
+MOMENTUM, BETA1, BETA2 = 0.9, 0.9, 0.999
 
 
-def run_width(ps, torch, leg, w, rows, nkeys, steps, warmup, dups):
+def run_width(ps, torch, leg, w, rows, nkeys, steps, warmup, dups, kind="adagrad"):
     dev = torch.device("cuda:0")
     g = torch.Generator(device=dev)
     g.manual_seed(4321 + w)
@@ -55,8 +58,12 @@ def run_width(ps, torch, leg, w, rows, nkeys, steps, warmup, dups):
     with ps.Shard(0, rows, np.float32, width=w) as sh:
         for i in range(4):  # the rows start written
             sh.add(keys[i], grads[(i + 1) % 4])
-        if leg == "apply":
+        if leg == "apply" and kind == "adagrad":
             sh.set_optimizer("adagrad", lr=LR, weight_decay=WD, eps=EPS, init_accum=INIT_ACCUM)
+        elif leg == "apply" and kind == "momentum":
+            sh.set_optimizer("momentum", lr=LR, weight_decay=WD, momentum=MOMENTUM)
+        elif leg == "apply":
+            sh.set_optimizer("adam", lr=LR, weight_decay=WD, eps=EPS, beta1=BETA1, beta2=BETA2)
         else:
             h = torch.full((rows, w), INIT_ACCUM, dtype=torch.float32, device=dev)
             p = torch.empty((keys[0].numel(), w), dtype=torch.float32, device=dev)
@@ -124,6 +131,10 @@ def merge(paths):
     legs = {}
     for r in runs:
         name = r["leg"] if r["dups"] == 1 else f"{r['leg']}_dups{r['dups']}"
+        if r.get("kind", "adagrad") != "adagrad":
+            name += "_" + r["kind"]
+        if r.get("label"):
+            name += "@" + r["label"]
         for w, x in r["widths"].items():
             legs.setdefault(name, {}).setdefault(w, []).append(x)
     for name, ws in legs.items():
@@ -134,6 +145,30 @@ def merge(paths):
             doc["summary"][name][w] = {"runs": len(xs), "event_ms": statistics.median(e), "event_ms_spread": max(e) - min(e),
                                        "library_timer_ms": statistics.median(t),
                                        "library_timer_ms_spread": max(t) - min(t)}
+    base, new = "apply@parent", "apply@new"
+    if base in legs and new in legs:
+        # the regression guard of DESIGN.md §8d: the edited kernel's Adagrad step against the parent build's
+        doc["what"] = ("tools/apply_probe.py --merge: one server-side step (pskv_apply) per kind; the Adagrad leg on a "
+                       "build of the parent commit (label parent) and on this build (label new), alternating "
+                       "(DESIGN.md 8d)")
+        doc["condition"] = ("at each width this build's Adagrad step takes no longer than the parent build's, each at the "
+                            "median of its runs' event medians; a difference inside the larger of the two spreads "
+                            "counts as equal")
+        doc["adagrad_new_over_parent"] = {}
+        doc["adagrad_guard_met"] = True
+        for w in legs[new]:
+            n, b = doc["summary"][new][w], doc["summary"][base][w]
+            slack = max(n["event_ms_spread"], b["event_ms_spread"])
+            doc["adagrad_new_over_parent"][w] = round(n["event_ms"] / b["event_ms"], 3)
+            doc["adagrad_guard_met"] = doc["adagrad_guard_met"] and n["event_ms"] <= b["event_ms"] + slack
+        doc["condition_met"] = doc["adagrad_guard_met"]
+        for k, streams in (("apply_momentum", 6), ("apply_adam", 8)):
+            for name in (k, k + "@new"):
+                if name in legs:
+                    doc[k + "_over_parent_adagrad"] = {
+                        w: round(doc["summary"][name][w]["event_ms"] / doc["summary"][base][w]["event_ms"], 3)
+                        for w in legs[name]}
+                    doc[k + "_model"] = round(streams / 6, 3)
     if "apply" in legs and "roundtrip" in legs:
         doc["apply_over_roundtrip"] = {}
         for w in legs["apply"]:
@@ -144,7 +179,7 @@ def merge(paths):
             if w in ("16", "64"):
                 slack = max(a["event_ms_spread"], r["event_ms_spread"])
                 doc["condition_met"] = doc["condition_met"] and a["event_ms"] <= r["event_ms"] + slack
-    else:
+    elif base not in legs or new not in legs:
         doc["condition_met"] = None
     return doc
 
@@ -158,6 +193,9 @@ def main():
     ap.add_argument("--rows", type=int, default=1 << 24)
     ap.add_argument("--keys", type=int, default=1 << 20)
     ap.add_argument("--dups", type=int, default=1)
+    ap.add_argument("--kind", choices=["adagrad", "momentum", "adam"], default="adagrad",
+                    help="the apply leg's optimizer")
+    ap.add_argument("--label", default="", help="kept in the run document; --merge keeps labelled runs apart")
     ap.add_argument("--widths", default="4,16,64")
     ap.add_argument("--steps", type=int, default=8)
     ap.add_argument("--warmup", type=int, default=2)
@@ -176,10 +214,10 @@ def main():
 
     import parameter_server_amd as ps
 
-    doc = {"leg": a.leg, "dups": a.dups, "commit": a.commit, "dtype": "float32", "rows": a.rows, "keys_per_call": a.keys,
+    doc = {"leg": a.leg, "kind": a.kind, "label": a.label, "dups": a.dups, "commit": a.commit, "dtype": "float32", "rows": a.rows, "keys_per_call": a.keys,
            "steps": a.steps, "warmup": a.warmup, "device": torch.cuda.get_device_name(0), "widths": {}}
     for w in [int(x) for x in a.widths.split(",")]:
-        r = run_width(ps, torch, a.leg, w, a.rows, a.keys, a.steps, a.warmup, a.dups)
+        r = run_width(ps, torch, a.leg, w, a.rows, a.keys, a.steps, a.warmup, a.dups, a.kind)
         doc["widths"][str(w)] = r
         print(f"W={w} {a.leg} dups={a.dups}: events {r['event_ms_median']:.4f} ms, library timers "
               f"{r['library_timer_ms_per_call']:.4f} ms", flush=True)
