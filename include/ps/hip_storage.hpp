@@ -79,18 +79,14 @@ class HipStorage : public AbstractStorage {
                       int mode = PSKV_ASSIGN, uint64_t overflow_slots = 0, uint32_t width = 1,
                       const pskv_optimizer* optimizer = nullptr)
       : width_(width), stepping_(optimizer != nullptr && optimizer->kind != PSKV_OPT_NONE) {
-    pskv_check(pskv_shard_create_rows(device, key_begin, key_end, PskvDtype<Val>::value, mode, width,
-                                      overflow_slots, &shard_),
-               "pskv_shard_create");
+    Create(device, key_begin, key_end, mode, overflow_slots);
     if (optimizer) pskv_check(pskv_shard_set_optimizer(shard_, optimizer), "pskv_shard_set_optimizer");
   }
   // The same with the extended configuration (momentum, Adam; every argument given).
   HipStorage(int device, uint32_t key_begin, uint64_t key_end, int mode, uint64_t overflow_slots, uint32_t width,
              const pskv_optimizer_ex* optimizer)
       : width_(width), stepping_(optimizer != nullptr && optimizer->kind != PSKV_OPT_NONE) {
-    pskv_check(pskv_shard_create_rows(device, key_begin, key_end, PskvDtype<Val>::value, mode, width,
-                                      overflow_slots, &shard_),
-               "pskv_shard_create");
+    Create(device, key_begin, key_end, mode, overflow_slots);
     if (optimizer) pskv_check(pskv_shard_set_optimizer_ex(shard_, optimizer), "pskv_shard_set_optimizer_ex");
   }
   ~HipStorage() override { pskv_shard_destroy(shard_); }
@@ -165,6 +161,13 @@ class HipStorage : public AbstractStorage {
   uint32_t width() const { return width_; }
 
  private:
+  // Both constructors' shard.
+  void Create(int device, uint32_t key_begin, uint64_t key_end, int mode, uint64_t overflow_slots) {
+    pskv_check(pskv_shard_create_rows(device, key_begin, key_end, PskvDtype<Val>::value, mode, width_,
+                                      overflow_slots, &shard_),
+               "pskv_shard_create");
+  }
+
   pskv_shard* shard_ = nullptr;
   uint32_t width_ = 1;
   bool stepping_ = false;  // an optimizer is set: Adds are optimizer steps

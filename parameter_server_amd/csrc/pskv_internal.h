@@ -263,16 +263,12 @@ hipError_t launch_row_accumulate(int dtype, const GroupArgs& ga, uint32_t nwg, c
                                  const Ovf& o, const RowShape& rs, hipStream_t st);
 
 // Optimizer steps (pskv_apply), float shards of any width
-// (1 included).  The hyper-parameters travel by value, rounded to the value
-// type once per launch, so a change is ordered by the stream.
+// (1 included).  The hyper-parameters travel by value: OptArgs<double> on the
+// host, rounded to the value type once per launch, so a change is ordered by
+// the stream.
 // Momentum: mu, nesterov.  Adam: beta1, omb1 = 1 - beta1,
 // beta2, omb2 = 1 - beta2, and the step's bias corrections a = lr / (1 -
 // beta1^t), b = 1 / sqrt(1 - beta2^t), all computed on the host in double.
-struct OptHyper {
-  double lr, wd, eps;
-  double mu, beta1, omb1, beta2, omb2, a, b;
-  int nesterov;
-};
 template <typename T>
 struct OptArgs {
   T lr, wd, eps;
@@ -289,11 +285,11 @@ hipError_t launch_row_grad_losers(int dtype, const GroupArgs& ga, uint32_t nwg, 
                                   const RowShape& rs, hipStream_t st);
 // Each winner applies the rule (kind: pskv_optimizer_kind, 1 to 4) once to its
 // key's row from its own gradient row plus the gsum row, and writes zeros back
-// to the gsum units it read non-zero.  state: slot 0 (Adagrad's h, momentum's
-// v, Adam's m); state2: slot 1 (Adam's v).
+// to the gsum units it read non-zero.  state[0]: slot 0 (Adagrad's h,
+// momentum's v, Adam's m); state[1]: slot 1 (Adam's v).
 hipError_t launch_row_apply(int dtype, int kind, const GroupArgs& ga, uint32_t nwg, const DenseView& d, void* gsum,
-                            void* state, void* state2, const unsigned long long* owner, uint32_t epoch,
-                            const RowShape& rs, const OptHyper& hy, hipStream_t st);
+                            void* const state[2], const unsigned long long* owner, uint32_t epoch,
+                            const RowShape& rs, const OptArgs<double>& hy, hipStream_t st);
 // p[0..n) = v (float or double by dtype): the accumulator's initial value.
 hipError_t launch_fill(int dtype, void* p, uint64_t n, double v, hipStream_t st);
 

@@ -182,6 +182,21 @@ static inline void check_keys(Piece& p, const uint32_t* k, size_t n, uint32_t ke
   p.outside = range ? out : n;  // pieces hold < 2^32 keys
 }
 
+// The first key of these batches outside [key_begin, key_begin + range), or
+// null: the vectorised count per batch, and the scan for the key itself only
+// in a batch that holds one.
+static inline const uint32_t* first_key_outside(const std::vector<pskv_batch>& v, uint32_t key_begin,
+                                                uint64_t range) {
+  for (const auto& b : v) {
+    Piece p{};
+    check_keys(p, b.keys, b.n, key_begin, range);
+    if (!p.outside) continue;
+    for (uint64_t i = 0; i < b.n; ++i)
+      if ((uint64_t)(uint32_t)(b.keys[i] - key_begin) >= range) return b.keys + i;
+  }
+  return nullptr;
+}
+
 static inline void copy_piece(Piece& p, uint32_t key_begin, uint64_t range) {
   if (p.key_batch < 0) {
     std::memcpy(p.dst, p.src, p.bytes);

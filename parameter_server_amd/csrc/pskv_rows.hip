@@ -56,6 +56,11 @@ __device__ __forceinline__ uint64_t row_elem_prefix(const GroupArgs& ga, int j) 
   return e;
 }
 
+// The tag K4a stamped for an element: epoch<<32 | (group-wide index of the element).
+__device__ __forceinline__ unsigned long long row_tag(uint32_t epoch, uint64_t index) {
+  return ((unsigned long long)epoch << 32) | index;
+}
+
 template <typename UT>
 __device__ __forceinline__ UT zero_unit() {
   return UT(0);
@@ -152,9 +157,7 @@ __global__ __launch_bounds__(kBlock) void k_row_commit(GroupArgs ga, DenseView d
       bool win[kRowsInFlight];
 #pragma unroll
       for (int r = 0; r < kRowsInFlight; ++r) {
-        // the tag K4a stamped for this element: epoch<<32 | (group index of the element)
-        const unsigned long long tag =
-            ((unsigned long long)epoch << 32) | (gbase + r0 + (uint32_t)r * G);
+        const unsigned long long tag = row_tag(epoch, gbase + r0 + (uint32_t)r * G);
         win[r] = s.in[r] && owner[s.off[r]] == tag;
         if (s.live[r] && !s.in[r] && lane == 0) atomicOr(err, kErrRowOutOfRange);
       }
@@ -275,8 +278,7 @@ __global__ __launch_bounds__(kBlock) void k_row_grad_losers(GroupArgs ga, DenseV
       bool any = false;
 #pragma unroll
       for (int r = 0; r < kRowsInFlight; ++r) {
-        const unsigned long long tag =
-            ((unsigned long long)epoch << 32) | (gbase + r0 + (uint32_t)r * G);
+        const unsigned long long tag = row_tag(epoch, gbase + r0 + (uint32_t)r * G);
         lose[r] = s.in[r] && owner[s.off[r]] != tag;
         any |= lose[r];
         if (s.live[r] && !s.in[r] && lane == 0) atomicOr(err, kErrRowOutOfRange);
@@ -324,8 +326,7 @@ __global__ __launch_bounds__(kBlock) void k_row_apply(GroupArgs ga, DenseView d,
       bool any = false;
 #pragma unroll
       for (int r = 0; r < kRowsInFlight; ++r) {
-        const unsigned long long tag =
-            ((unsigned long long)epoch << 32) | (gbase + r0 + (uint32_t)r * G);
+        const unsigned long long tag = row_tag(epoch, gbase + r0 + (uint32_t)r * G);
         win[r] = s.in[r] && owner[s.off[r]] == tag;
         any |= win[r];
       }
@@ -384,15 +385,40 @@ __global__ __launch_bounds__(kBlock) void k_fill(T* __restrict__ p, uint64_t n, 
 
 uint32_t row_grid(uint32_t nwg) { return nwg < 4096u ? nwg : 4096u; }
 
+// f(T()) with T the shard's float type (dtype: 1 float, 2 double), then the
+// launch's error; any other dtype is refused.
+template <typename F>
+hipError_t with_float_type(int dtype, F&& f) {
+  if (dtype != 1 && dtype != 2) return hipErrorInvalidValue;
+  dtype == 1 ? f(float()) : f(double());
+  return hipGetLastError();
+}
+
+// f(UT()) with UT the unit of a copy kernel: 16 bytes, or one element of vb bytes.
+template <typename F>
+hipError_t with_unit_type(const RowShape& rs, int vb, F&& f) {
+  if (rs.unit_bytes == 16)
+    f(u32x4());
+  else if (vb == 4)
+    f(uint32_t());
+  else
+    f((unsigned long long)0);
+  return hipGetLastError();
+}
+
+template <typename T>
+OptArgs<T> round_opt_args(const OptArgs<double>& h) {
+  return OptArgs<T>{(T)h.lr,   (T)h.wd,    (T)h.eps,  (T)h.mu, (T)h.beta1,
+                    (T)h.omb1, (T)h.beta2, (T)h.omb2, (T)h.a,  (T)h.b,    h.nesterov};
+}
+
 template <typename T, int V>
-void launch_row_apply_kind(int kind, uint32_t grid, const GroupArgs& ga, const DenseView& d, void* gsum, void* state,
-                           void* state2, const unsigned long long* owner, uint32_t epoch, const RowShape& rs,
-                           const OptHyper& hy, hipStream_t st) {
-  const OptArgs<T> o{(T)hy.lr,   (T)hy.wd,    (T)hy.eps,  (T)hy.mu, (T)hy.beta1,
-                     (T)hy.omb1, (T)hy.beta2, (T)hy.omb2, (T)hy.a,  (T)hy.b,    hy.nesterov};
+void launch_row_apply_kind(int kind, uint32_t grid, const GroupArgs& ga, const DenseView& d, void* gsum,
+                           void* const state[2], const unsigned long long* owner, uint32_t epoch, const RowShape& rs,
+                           const OptArgs<T>& o, hipStream_t st) {
   T* g = static_cast<T*>(gsum);
-  T* s1 = static_cast<T*>(state);
-  T* s2 = static_cast<T*>(state2);
+  T* s1 = static_cast<T*>(state[0]);
+  T* s2 = static_cast<T*>(state[1]);
   if (kind == 4)
     k_row_apply<T, 4, V><<<grid, kBlock, 0, st>>>(ga, d, g, s1, s2, owner, epoch, rs, o);
   else if (kind == 3)
@@ -422,23 +448,13 @@ hipError_t launch_row_gather(int vb, bool nt, const GroupArgs& ga, uint32_t nwg,
                              const RowShape& rs, hipStream_t st) {
   if (nwg == 0) return hipSuccess;
   const uint32_t grid = row_grid(nwg);
-  if (rs.unit_bytes == 16) {
+  return with_unit_type(rs, vb, [&](auto u) {
+    using UT = decltype(u);
     if (nt)
-      k_row_gather<u32x4, true><<<grid, kBlock, 0, st>>>(ga, d, rs);
+      k_row_gather<UT, true><<<grid, kBlock, 0, st>>>(ga, d, rs);
     else
-      k_row_gather<u32x4, false><<<grid, kBlock, 0, st>>>(ga, d, rs);
-  } else if (vb == 4) {
-    if (nt)
-      k_row_gather<uint32_t, true><<<grid, kBlock, 0, st>>>(ga, d, rs);
-    else
-      k_row_gather<uint32_t, false><<<grid, kBlock, 0, st>>>(ga, d, rs);
-  } else {
-    if (nt)
-      k_row_gather<unsigned long long, true><<<grid, kBlock, 0, st>>>(ga, d, rs);
-    else
-      k_row_gather<unsigned long long, false><<<grid, kBlock, 0, st>>>(ga, d, rs);
-  }
-  return hipGetLastError();
+      k_row_gather<UT, false><<<grid, kBlock, 0, st>>>(ga, d, rs);
+  });
 }
 
 hipError_t launch_row_commit(int vb, const GroupArgs& ga, uint32_t nwg, const DenseView& d,
@@ -447,13 +463,9 @@ hipError_t launch_row_commit(int vb, const GroupArgs& ga, uint32_t nwg, const De
   if (nwg == 0) return hipSuccess;
   const uint32_t grid = row_grid(nwg);
   uint32_t* err = &o.c->stat[1];
-  if (rs.unit_bytes == 16)
-    k_row_commit<u32x4><<<grid, kBlock, 0, st>>>(ga, d, owner, err, epoch, rs);
-  else if (vb == 4)
-    k_row_commit<uint32_t><<<grid, kBlock, 0, st>>>(ga, d, owner, err, epoch, rs);
-  else
-    k_row_commit<unsigned long long><<<grid, kBlock, 0, st>>>(ga, d, owner, err, epoch, rs);
-  return hipGetLastError();
+  return with_unit_type(rs, vb, [&](auto u) {
+    k_row_commit<decltype(u)><<<grid, kBlock, 0, st>>>(ga, d, owner, err, epoch, rs);
+  });
 }
 
 hipError_t launch_row_accumulate(int dtype, const GroupArgs& ga, uint32_t nwg, const DenseView& d,
@@ -474,48 +486,38 @@ hipError_t launch_row_grad_losers(int dtype, const GroupArgs& ga, uint32_t nwg, 
                                   const unsigned long long* owner, const Ovf& o, uint32_t epoch,
                                   const RowShape& rs, hipStream_t st) {
   if (nwg == 0) return hipSuccess;
-  if (dtype != 1 && dtype != 2) return hipErrorInvalidValue;
   const uint32_t grid = row_grid(nwg);
   uint32_t* err = &o.c->stat[1];
-  if (dtype == 1)
-    k_row_grad_losers<float><<<grid, kBlock, 0, st>>>(ga, d, static_cast<float*>(gsum), owner, err, epoch, rs);
-  else
-    k_row_grad_losers<double><<<grid, kBlock, 0, st>>>(ga, d, static_cast<double*>(gsum), owner, err, epoch, rs);
-  return hipGetLastError();
+  return with_float_type(dtype, [&](auto z) {
+    using T = decltype(z);
+    k_row_grad_losers<T><<<grid, kBlock, 0, st>>>(ga, d, static_cast<T*>(gsum), owner, err, epoch, rs);
+  });
 }
 
 hipError_t launch_row_apply(int dtype, int kind, const GroupArgs& ga, uint32_t nwg, const DenseView& d, void* gsum,
-                            void* state, void* state2, const unsigned long long* owner, uint32_t epoch,
-                            const RowShape& rs, const OptHyper& hy, hipStream_t st) {
+                            void* const state[2], const unsigned long long* owner, uint32_t epoch,
+                            const RowShape& rs, const OptArgs<double>& hy, hipStream_t st) {
   if (nwg == 0) return hipSuccess;
-  if ((dtype != 1 && dtype != 2) || kind < 1 || kind > 4 || (kind >= 2 && !state) || (kind == 4 && !state2))
-    return hipErrorInvalidValue;
+  if (kind < 1 || kind > 4 || (kind >= 2 && !state[0]) || (kind == 4 && !state[1])) return hipErrorInvalidValue;
   const uint32_t grid = row_grid(nwg);
-  const bool u16 = rs.unit_bytes == 16;
-  if (dtype == 1) {
-    if (u16)
-      launch_row_apply_kind<float, 4>(kind, grid, ga, d, gsum, state, state2, owner, epoch, rs, hy, st);
+  return with_float_type(dtype, [&](auto z) {
+    using T = decltype(z);
+    const OptArgs<T> o = round_opt_args<T>(hy);
+    if (rs.unit_bytes == 16)
+      launch_row_apply_kind<T, 16 / sizeof(T)>(kind, grid, ga, d, gsum, state, owner, epoch, rs, o, st);
     else
-      launch_row_apply_kind<float, 1>(kind, grid, ga, d, gsum, state, state2, owner, epoch, rs, hy, st);
-  } else {
-    if (u16)
-      launch_row_apply_kind<double, 2>(kind, grid, ga, d, gsum, state, state2, owner, epoch, rs, hy, st);
-    else
-      launch_row_apply_kind<double, 1>(kind, grid, ga, d, gsum, state, state2, owner, epoch, rs, hy, st);
-  }
-  return hipGetLastError();
+      launch_row_apply_kind<T, 1>(kind, grid, ga, d, gsum, state, owner, epoch, rs, o, st);
+  });
 }
 
 hipError_t launch_fill(int dtype, void* p, uint64_t n, double v, hipStream_t st) {
   if (n == 0) return hipSuccess;
-  if (dtype != 1 && dtype != 2) return hipErrorInvalidValue;
   const uint64_t nwg = (n + kBlock - 1) / kBlock;
   const uint32_t grid = (uint32_t)(nwg < 65536u ? nwg : 65536u);
-  if (dtype == 1)
-    k_fill<float><<<grid, kBlock, 0, st>>>(static_cast<float*>(p), n, (float)v);
-  else
-    k_fill<double><<<grid, kBlock, 0, st>>>(static_cast<double*>(p), n, v);
-  return hipGetLastError();
+  return with_float_type(dtype, [&](auto z) {
+    using T = decltype(z);
+    k_fill<T><<<grid, kBlock, 0, st>>>(static_cast<T*>(p), n, (T)v);
+  });
 }
 
 }  // namespace pskv

@@ -37,6 +37,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <initializer_list>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -367,8 +368,7 @@ struct pskv_shard {
   // optimizer is set.  opt_step: steps since creation, clear or a kind change.
   pskv_optimizer_ex opt{};
   void* opt_gsum = nullptr;
-  void* opt_state = nullptr;   // slot 0
-  void* opt_state2 = nullptr;  // slot 1
+  void* opt_slot[2] = {nullptr, nullptr};  // the first opt_slots(opt.kind) are allocated
   uint64_t opt_step = 0;
 
   DenseView dview() const { return DenseView{dense, key_begin, range}; }
@@ -1585,21 +1585,63 @@ int inline_get(pskv_shard* s, const std::vector<pskv_batch>& v, uint64_t total) 
 // is queued, the kernels drop them and set kErrRowOutOfRange.
 size_t row_bytes(const pskv_shard* s) { return (size_t)s->width * (size_t)s->vb; }
 
-int rows_pieces(pskv_shard* s, const std::vector<pskv_batch>& in, const char* what, std::vector<pskv_batch>* v) {
+// unit16 of a launch (row_shape): the row size is a multiple of 16 bytes, and
+// the arrays the launch touches and every batch's rows are 16-byte aligned.
+bool rows_unit16(const pskv_shard* s, std::initializer_list<const void*> arrays, const std::vector<pskv_batch>& v) {
+  bool ok = row_bytes(s) % 16 == 0;
+  for (const void* p : arrays) ok = ok && aligned16(p);
+  for (const auto& b : v) ok = ok && aligned16(b.vals);
+  return ok;
+}
+
+// The front of every row-shaped call: a row Add or Get, an optimizer step, a
+// read or write of optimizer state.
+struct RowFront {
+  const char* what;      // the call's name in messages
+  uint64_t* calls;       // n_add / n_get, or null: counted once the arguments hold
+  bool stop_server;      // end a width-1 shard's request server before stream work
+  const char* refusal;   // a host call refuses an out-of-range key (null: it does not):
+  const char* why;       //   what stands in front of and behind the key
+  bool with_values;      // a host call stages its rows behind its keys (an Add's)
+};
+struct RowCall {
+  std::vector<pskv_batch> v;   // the call's pieces, where the caller has them (empty: nothing to do)
+  std::vector<pskv_batch> dv;  // a host call's pieces in the device staging
+  StageLayout lay;             // and where each lies there (pinned staging: the same offsets)
+  bool host = false;
+  const std::vector<pskv_batch>& views() const { return host ? dv : v; }  // what the kernels read
+};
+
+// A host call's keys are checked before anything is queued (nothing is
+// applied); its pieces are then on their way to the device staging, and
+// `hold`, the caller's, is armed.
+int rows_front(pskv_shard* s, const std::vector<pskv_batch>& in, int flags, const RowFront& f, HstageHold& hold,
+               RowCall* c) {
   for (auto& b : in) {
     if (b.n == 0) continue;
-    if (!b.keys || !b.vals) return fail(PSKV_EINVAL, std::string(what) + ": null keys/vals with n > 0");
-    push_pieces(*v, b, row_bytes(s));
+    if (!b.keys || !b.vals) return fail(PSKV_EINVAL, std::string(f.what) + ": null keys/vals with n > 0");
+    push_pieces(c->v, b, row_bytes(s));
   }
-  return PSKV_OK;
+  if (f.calls) ++*f.calls;
+  if (c->v.empty()) return PSKV_OK;
+  int rc = use_device(s);
+  if (rc) return rc;
+  if (f.stop_server && (rc = srv_stop(s))) return rc;
+  if (flags & PSKV_DEVICE) return PSKV_OK;
+  if (f.refusal)
+    if (const uint32_t* k = first_key_outside(c->v, s->key_begin, s->range))
+      return fail(PSKV_EINVAL, std::string(f.what) + ": " + f.refusal + " " + std::to_string(*k) +
+                                   " is outside [key_begin, key_end); " + f.why + " (nothing was applied)");
+  c->host = true;
+  c->lay = stage_layout(c->v, row_bytes(s), StageOrder::kKeysFirst);
+  return stage_keys_first(s, c->v, c->lay, row_bytes(s), f.with_values, hold, &c->dv);
 }
 
 // `d`: the array written: the dense array in the shard's mode, or
 // (pskv_put_state) one of the optimizer's state arrays, which have the same
 // shape, always as an assign.
 int rows_add_device(pskv_shard* s, const std::vector<pskv_batch>& v, const DenseView& d, int mode) {
-  bool vec = row_bytes(s) % 16 == 0 && aligned16(d.param);
-  for (auto& b : v) vec = vec && aligned16(b.vals);
+  const bool vec = rows_unit16(s, {d.param}, v);
   for (const Span& sp : split_groups(v)) {
     const LaunchGroup g = make_group(v, sp.first, sp.second, kGeneralChunk);
     if (mode == PSKV_ACCUMULATE) {
@@ -1623,47 +1665,25 @@ int rows_add_device(pskv_shard* s, const std::vector<pskv_batch>& v, const Dense
   return PSKV_OK;
 }
 
-// `what`: the call's name in messages; `refusal`, `why`: what stands in front
-// of and behind an out-of-range key.
+// A row shard has no request server, so neither this nor rows_get_from stops one.
 int rows_add_to(pskv_shard* s, const std::vector<pskv_batch>& in, int flags, const DenseView& d, int mode,
-                const char* what, const char* refusal, const char* why, bool count_add) {
-  std::vector<pskv_batch> v;
-  if (int rc = rows_pieces(s, in, what, &v)) return rc;
-  if (count_add) s->n_add++;
-  if (v.empty()) return PSKV_OK;
-  int rc = use_device(s);
-  if (rc) return rc;
-  if (flags & PSKV_DEVICE) return rows_add_device(s, v, d, mode);
-  // the keys are checked before anything is queued: nothing is applied
-  for (const auto& b : v) {
-    Piece p{};
-    check_keys(p, b.keys, b.n, s->key_begin, s->range);
-    if (!p.outside) continue;
-    for (uint64_t i = 0; i < b.n; ++i)
-      if ((uint64_t)(uint32_t)(b.keys[i] - s->key_begin) >= s->range)
-        return fail(PSKV_EINVAL, std::string(what) + ": " + refusal + " " + std::to_string(b.keys[i]) +
-                                     " is outside [key_begin, key_end); " + why +
-                                     " (nothing was applied)");
-  }
-  // the call returns before its DMA: the hold stays armed
-  HstageHold hold(s);
-  std::vector<pskv_batch> dv;
-  rc = stage_keys_first(s, v, stage_layout(v, row_bytes(s), StageOrder::kKeysFirst), row_bytes(s),
-                        /*with_values=*/true, hold, &dv);
-  return rc ? rc : rows_add_device(s, dv, d, mode);
+                const RowFront& f) {
+  HstageHold hold(s);  // the call returns before its DMA: the hold stays armed
+  RowCall c;
+  if (int rc = rows_front(s, in, flags, f, hold, &c)) return rc;
+  return c.v.empty() ? PSKV_OK : rows_add_device(s, c.views(), d, mode);
 }
 
 int rows_add(pskv_shard* s, const std::vector<pskv_batch>& in, int flags) {
-  return rows_add_to(s, in, flags, s->dview(), s->mode, "pskv_add", "row shard: key",
-                     "a row shard stores no out-of-range keys", /*count_add=*/true);
+  return rows_add_to(s, in, flags, s->dview(), s->mode,
+                     RowFront{"pskv_add", &s->n_add, false, "row shard: key", "a row shard stores no out-of-range keys",
+                              /*with_values=*/true});
 }
 
 // `d`: the array gathered from: the dense array, or (pskv_get_state) the
 // optimizer's accumulator, which has the same shape.
 int rows_gather(pskv_shard* s, const std::vector<pskv_batch>& dv, const DenseView& d) {
-  bool vec = row_bytes(s) % 16 == 0 && aligned16(d.param);
-  for (auto& b : dv) vec = vec && aligned16(b.vals);
-  const RowShape rs = row_shape(s->width, s->vb, vec);
+  const RowShape rs = row_shape(s->width, s->vb, rows_unit16(s, {d.param}, dv));
   for (const Span& sp : split_groups(dv)) {
     const LaunchGroup g = make_group(dv, sp.first, sp.second, kGeneralChunk);
     LaunchTimer t(s, PSKV_K_ROW_GATHER, g.elems);
@@ -1674,36 +1694,28 @@ int rows_gather(pskv_shard* s, const std::vector<pskv_batch>& dv, const DenseVie
 }
 
 int rows_get_from(pskv_shard* s, const std::vector<pskv_batch>& in, int flags, const DenseView& src,
-                  const char* what, bool count_get) {
-  std::vector<pskv_batch> v;
-  if (int rc = rows_pieces(s, in, what, &v)) return rc;
-  if (count_get) s->n_get++;
-  if (v.empty()) return PSKV_OK;
-  int rc = use_device(s);
-  if (rc) return rc;
-  if (flags & PSKV_DEVICE) return rows_gather(s, v, src);
+                  const char* what, uint64_t* calls) {
   HstageHold hold(s);
-  const StageLayout lay = stage_layout(v, row_bytes(s), StageOrder::kKeysFirst);
-  std::vector<pskv_batch> dv;
-  rc = stage_keys_first(s, v, lay, row_bytes(s), /*with_values=*/false, hold, &dv);
-  if (!rc) rc = rows_gather(s, dv, src);
-  if (rc) return rc;
+  RowCall c;
+  int rc = rows_front(s, in, flags, RowFront{what, calls, false, nullptr, nullptr, /*with_values=*/false}, hold, &c);
+  if (rc || c.v.empty()) return rc;
+  if ((rc = rows_gather(s, c.views(), src)) || !c.host) return rc;
   // rows: device staging -> pinned staging -> the caller's buffers
   char* h = static_cast<char*>(s->hstage);
   char* d = static_cast<char*>(s->dstage);
-  PSKV_HIP(hipMemcpyAsync(h + lay.key_bytes, d + lay.key_bytes, lay.total - lay.key_bytes, hipMemcpyDeviceToHost,
-                          s->stream));
+  PSKV_HIP(hipMemcpyAsync(h + c.lay.key_bytes, d + c.lay.key_bytes, c.lay.total - c.lay.key_bytes,
+                          hipMemcpyDeviceToHost, s->stream));
   if (int rc2 = wait_stream(s, s->stream, "shard stream (row Get to host)")) return rc2;
   hold.dismiss();
   std::vector<Piece> pieces;
-  for (size_t i = 0; i < v.size(); ++i)
-    add_pieces(pieces, h + lay.at[i].vals, static_cast<char*>(v[i].vals), v[i].n * row_bytes(s), -1);
+  for (size_t i = 0; i < c.v.size(); ++i)
+    add_pieces(pieces, h + c.lay.at[i].vals, static_cast<char*>(c.v[i].vals), c.v[i].n * row_bytes(s), -1);
   run_copies(s, pieces, 0, pieces.size());
   return PSKV_OK;
 }
 
 int rows_get(pskv_shard* s, const std::vector<pskv_batch>& in, int flags) {
-  return rows_get_from(s, in, flags, s->dview(), "pskv_get", /*count_get=*/true);
+  return rows_get_from(s, in, flags, s->dview(), "pskv_get", &s->n_get);
 }
 
 // -------------------------------------------------------- optimizer steps
@@ -1726,26 +1738,44 @@ int opt_slots(int kind) {
   return kind == PSKV_OPT_ADAM ? 2 : (kind == PSKV_OPT_ADAGRAD || kind == PSKV_OPT_MOMENTUM) ? 1 : 0;
 }
 
+// The hyper-parameters of step `step` as a launch takes them, in double; a
+// field the kind does not use is 0.
+OptArgs<double> opt_args(const pskv_optimizer_ex& c, uint64_t step) {
+  OptArgs<double> o{};
+  o.lr = c.lr;
+  o.wd = c.weight_decay;
+  o.eps = c.eps;
+  if (c.kind == PSKV_OPT_MOMENTUM) {
+    o.mu = c.momentum;
+    o.nesterov = c.nesterov;
+  } else if (c.kind == PSKV_OPT_ADAM) {
+    o.beta1 = c.beta1;
+    o.beta2 = c.beta2;
+    o.omb1 = 1.0 - c.beta1;
+    o.omb2 = 1.0 - c.beta2;
+    o.a = c.lr / (1.0 - std::pow(c.beta1, (double)step));
+    o.b = 1.0 / std::sqrt(1.0 - std::pow(c.beta2, (double)step));
+  }
+  return o;
+}
+
 // The state back to its start values (Adagrad's h: init_accum; every other
 // slot: 0), the gradient scratch to zero (stream-ordered), the step count to 0.
 int opt_reset_state(pskv_shard* s) {
   s->opt_step = 0;
   if (s->opt_gsum) PSKV_HIP(hipMemsetAsync(s->opt_gsum, 0, opt_array_bytes(s), s->stream));
-  if (s->opt_state) {
+  for (int i = 0; i < opt_slots(s->opt.kind); ++i) {
     if (s->opt.kind == PSKV_OPT_ADAGRAD)
-      PSKV_HIP(launch_fill(s->dtype, s->opt_state, s->range * (uint64_t)s->width, s->opt.init_accum, s->stream));
+      PSKV_HIP(launch_fill(s->dtype, s->opt_slot[i], s->range * (uint64_t)s->width, s->opt.init_accum, s->stream));
     else
-      PSKV_HIP(hipMemsetAsync(s->opt_state, 0, opt_array_bytes(s), s->stream));
+      PSKV_HIP(hipMemsetAsync(s->opt_slot[i], 0, opt_array_bytes(s), s->stream));
   }
-  if (s->opt_state2) PSKV_HIP(hipMemsetAsync(s->opt_state2, 0, opt_array_bytes(s), s->stream));
   return PSKV_OK;
 }
 
 int apply_device(pskv_shard* s, const std::vector<pskv_batch>& v) {
   if (int rc = ensure_owner(s)) return rc;
-  bool vec = row_bytes(s) % 16 == 0 && aligned16(s->dense) && aligned16(s->opt_gsum) && aligned16(s->opt_state) &&
-             aligned16(s->opt_state2);
-  for (auto& b : v) vec = vec && aligned16(b.vals);
+  const bool vec = rows_unit16(s, {s->dense, s->opt_gsum, s->opt_slot[0], s->opt_slot[1]}, v);
   const std::vector<Span> spans = split_groups(v);
   std::vector<LaunchGroup> groups;
   std::vector<uint32_t> epochs;
@@ -1759,22 +1789,7 @@ int apply_device(pskv_shard* s, const std::vector<pskv_batch>& v) {
     elems += groups.back().elems;
   }
   // one step number for the whole call, whatever its launch groups
-  const uint64_t step = ++s->opt_step;
-  OptHyper hy{};
-  hy.lr = s->opt.lr;
-  hy.wd = s->opt.weight_decay;
-  hy.eps = s->opt.eps;
-  if (s->opt.kind == PSKV_OPT_MOMENTUM) {
-    hy.mu = s->opt.momentum;
-    hy.nesterov = s->opt.nesterov;
-  } else if (s->opt.kind == PSKV_OPT_ADAM) {
-    hy.beta1 = s->opt.beta1;
-    hy.beta2 = s->opt.beta2;
-    hy.omb1 = 1.0 - s->opt.beta1;
-    hy.omb2 = 1.0 - s->opt.beta2;
-    hy.a = s->opt.lr / (1.0 - std::pow(s->opt.beta1, (double)step));
-    hy.b = 1.0 / std::sqrt(1.0 - std::pow(s->opt.beta2, (double)step));
-  }
+  const OptArgs<double> hy = opt_args(s->opt, ++s->opt_step);
   const RowShape rs1 = row_shape(s->width, s->vb, false);
   const RowShape rsv = row_shape(s->width, s->vb, vec);
   LaunchTimer t(s, kTimeApply, elems);
@@ -1787,7 +1802,7 @@ int apply_device(pskv_shard* s, const std::vector<pskv_batch>& v) {
                                     epochs[i], rs1, s->stream));
   for (size_t i = 0; i < groups.size(); ++i)
     PSKV_HIP(launch_row_apply(s->dtype, s->opt.kind, groups[i].ga, groups[i].nwg, s->dview(), s->opt_gsum,
-                              s->opt_state, s->opt_state2, s->owner, epochs[i], rsv, hy, s->stream));
+                              s->opt_slot, s->owner, epochs[i], rsv, hy, s->stream));
   t.done();
   s->n_general += 3 * groups.size();
   return PSKV_OK;
@@ -1796,72 +1811,46 @@ int apply_device(pskv_shard* s, const std::vector<pskv_batch>& v) {
 int apply_impl(pskv_shard* s, const std::vector<pskv_batch>& in, int flags) {
   if (s->opt.kind == PSKV_OPT_NONE)
     return fail(PSKV_EINVAL, "pskv_apply: the shard has no optimizer (pskv_shard_set_optimizer)");
-  std::vector<pskv_batch> v;
-  if (int rc = rows_pieces(s, in, "pskv_apply", &v)) return rc;
-  if (v.empty()) return PSKV_OK;
-  int rc = use_device(s);
-  if (rc) return rc;
   // a width-1 shard's resident request server runs alone on the shard: as
-  // every stream path of add_impl / get_impl, end it first (K8 launches are
-  // ordinary work of the shard's stream and need nothing)
-  rc = srv_stop(s);
-  if (rc) return rc;
-  if (flags & PSKV_DEVICE) return apply_device(s, v);
-  // the keys are checked before anything is queued: nothing is applied
-  for (const auto& b : v) {
-    Piece p{};
-    check_keys(p, b.keys, b.n, s->key_begin, s->range);
-    if (!p.outside) continue;
-    for (uint64_t i = 0; i < b.n; ++i)
-      if ((uint64_t)(uint32_t)(b.keys[i] - s->key_begin) >= s->range)
-        return fail(PSKV_EINVAL, "pskv_apply: key " + std::to_string(b.keys[i]) +
-                                     " is outside [key_begin, key_end); an optimizer step takes no out-of-range "
-                                     "keys (nothing was applied)");
-  }
-  // the call returns before its DMA: the hold stays armed
-  HstageHold hold(s);
-  std::vector<pskv_batch> dv;
-  rc = stage_keys_first(s, v, stage_layout(v, row_bytes(s), StageOrder::kKeysFirst), row_bytes(s),
-                        /*with_values=*/true, hold, &dv);
-  return rc ? rc : apply_device(s, dv);
+  // every stream path of add_impl / get_impl, the front ends it first (K8
+  // launches are ordinary work of the shard's stream and need nothing)
+  HstageHold hold(s);  // the call returns before its DMA: the hold stays armed
+  RowCall c;
+  if (int rc = rows_front(s, in, flags,
+                          RowFront{"pskv_apply", nullptr, /*stop_server=*/true, "key",
+                                   "an optimizer step takes no out-of-range keys", /*with_values=*/true},
+                          hold, &c))
+    return rc;
+  return c.v.empty() ? PSKV_OK : apply_device(s, c.views());
 }
 
-// What is wrong with a configuration, or null (checked before any handle).
-const char* opt_config_error(const pskv_optimizer* c) {
-  if (!c) return "null configuration";
-  if (c->kind != PSKV_OPT_NONE && c->kind != PSKV_OPT_SGD && c->kind != PSKV_OPT_ADAGRAD)
-    return "kind must be PSKV_OPT_NONE, PSKV_OPT_SGD or PSKV_OPT_ADAGRAD";
-  if (c->kind == PSKV_OPT_NONE) return nullptr;
-  if (!std::isfinite(c->lr) || !(c->lr > 0)) return "lr must be finite and > 0";
-  if (!std::isfinite(c->weight_decay) || !(c->weight_decay >= 0)) return "weight_decay must be finite and >= 0";
-  if (c->kind == PSKV_OPT_ADAGRAD) {
-    if (!std::isfinite(c->eps) || !(c->eps > 0)) return "eps must be finite and > 0";
-    if (!std::isfinite(c->init_accum) || !(c->init_accum >= 0)) return "init_accum must be finite and >= 0";
+// What is wrong with a configuration, or null (checked before any handle;
+// fields a kind does not use are ignored).  legacy: the configuration was
+// widened from a pskv_optimizer, which has no size and only the first kinds.
+const char* opt_config_error(const pskv_optimizer_ex& c, bool legacy) {
+  if (legacy) {
+    if (c.kind != PSKV_OPT_NONE && c.kind != PSKV_OPT_SGD && c.kind != PSKV_OPT_ADAGRAD)
+      return "kind must be PSKV_OPT_NONE, PSKV_OPT_SGD or PSKV_OPT_ADAGRAD";
+  } else {
+    if (c.size != sizeof(pskv_optimizer_ex)) return "size must be sizeof(pskv_optimizer_ex)";
+    if (c.kind < PSKV_OPT_NONE || c.kind > PSKV_OPT_ADAM)
+      return "kind must be PSKV_OPT_NONE, PSKV_OPT_SGD, PSKV_OPT_ADAGRAD, PSKV_OPT_MOMENTUM or PSKV_OPT_ADAM";
   }
-  return nullptr;
-}
-
-// The same for the extended configuration (fields a kind does not use are ignored).
-const char* opt_config_error_ex(const pskv_optimizer_ex* c) {
-  if (!c) return "null configuration";
-  if (c->size != sizeof(pskv_optimizer_ex)) return "size must be sizeof(pskv_optimizer_ex)";
-  if (c->kind < PSKV_OPT_NONE || c->kind > PSKV_OPT_ADAM)
-    return "kind must be PSKV_OPT_NONE, PSKV_OPT_SGD, PSKV_OPT_ADAGRAD, PSKV_OPT_MOMENTUM or PSKV_OPT_ADAM";
-  if (c->kind == PSKV_OPT_NONE) return nullptr;
-  if (!std::isfinite(c->lr) || !(c->lr > 0)) return "lr must be finite and > 0";
-  if (!std::isfinite(c->weight_decay) || !(c->weight_decay >= 0)) return "weight_decay must be finite and >= 0";
-  if (c->kind == PSKV_OPT_ADAGRAD || c->kind == PSKV_OPT_ADAM)
-    if (!std::isfinite(c->eps) || !(c->eps > 0)) return "eps must be finite and > 0";
-  if (c->kind == PSKV_OPT_ADAGRAD)
-    if (!std::isfinite(c->init_accum) || !(c->init_accum >= 0)) return "init_accum must be finite and >= 0";
-  if (c->kind == PSKV_OPT_MOMENTUM) {
-    if (!std::isfinite(c->momentum) || !(c->momentum >= 0) || !(c->momentum < 1))
+  if (c.kind == PSKV_OPT_NONE) return nullptr;
+  if (!std::isfinite(c.lr) || !(c.lr > 0)) return "lr must be finite and > 0";
+  if (!std::isfinite(c.weight_decay) || !(c.weight_decay >= 0)) return "weight_decay must be finite and >= 0";
+  if (c.kind == PSKV_OPT_ADAGRAD || c.kind == PSKV_OPT_ADAM)
+    if (!std::isfinite(c.eps) || !(c.eps > 0)) return "eps must be finite and > 0";
+  if (c.kind == PSKV_OPT_ADAGRAD)
+    if (!std::isfinite(c.init_accum) || !(c.init_accum >= 0)) return "init_accum must be finite and >= 0";
+  if (c.kind == PSKV_OPT_MOMENTUM) {
+    if (!std::isfinite(c.momentum) || !(c.momentum >= 0) || !(c.momentum < 1))
       return "momentum must be finite and in [0, 1)";
-    if (c->nesterov != 0 && c->nesterov != 1) return "nesterov must be 0 or 1";
+    if (c.nesterov != 0 && c.nesterov != 1) return "nesterov must be 0 or 1";
   }
-  if (c->kind == PSKV_OPT_ADAM) {
-    if (!std::isfinite(c->beta1) || !(c->beta1 >= 0) || !(c->beta1 < 1)) return "beta1 must be finite and in [0, 1)";
-    if (!std::isfinite(c->beta2) || !(c->beta2 >= 0) || !(c->beta2 < 1)) return "beta2 must be finite and in [0, 1)";
+  if (c.kind == PSKV_OPT_ADAM) {
+    if (!std::isfinite(c.beta1) || !(c.beta1 >= 0) || !(c.beta1 < 1)) return "beta1 must be finite and in [0, 1)";
+    if (!std::isfinite(c.beta2) || !(c.beta2 >= 0) || !(c.beta2 < 1)) return "beta2 must be finite and in [0, 1)";
   }
   return nullptr;
 }
@@ -2292,8 +2281,10 @@ int apply_env_options(pskv_shard* s) {
   return PSKV_OK;
 }
 
-// Both setters end here, with a validated configuration.
-int set_optimizer_impl(pskv_shard* s, const pskv_optimizer_ex& cfg, const std::string& who) {
+// Both setters end here (legacy: from pskv_shard_set_optimizer, widened).
+int set_optimizer_impl(pskv_shard* s, const pskv_optimizer_ex& cfg, bool legacy, const std::string& who) {
+  // the configuration first: a bad field is reported whatever the handle
+  if (const char* what = opt_config_error(cfg, legacy)) return fail(PSKV_EINVAL, who + ": " + what);
   if (!s) return fail(PSKV_EINVAL, who + ": null shard");
   if (cfg.kind != PSKV_OPT_NONE && s->dtype != PSKV_F32 && s->dtype != PSKV_F64)
     return fail(PSKV_EINVAL, who + ": optimizers need a float shard (PSKV_F32, PSKV_F64)");
@@ -2331,22 +2322,20 @@ int set_optimizer_impl(pskv_shard* s, const pskv_optimizer_ex& cfg, const std::s
     }
   }
   // queued steps may still use the arrays that go
-  if (s->opt_state || (cfg.kind == PSKV_OPT_NONE && s->opt_gsum)) {
+  if (s->opt_slot[0] || (cfg.kind == PSKV_OPT_NONE && s->opt_gsum)) {
     if ((rc = srv_stop(s)) || (rc = wait_stream(s, s->stream, "shard stream (optimizer change)"))) {
       give_back();
       return rc;
     }
-    if (s->opt_state) (void)hipFree(s->opt_state);
-    if (s->opt_state2) (void)hipFree(s->opt_state2);
-    s->opt_state = s->opt_state2 = nullptr;
+    for (void* p : s->opt_slot)
+      if (p) (void)hipFree(p);
     if (cfg.kind == PSKV_OPT_NONE) {
       (void)hipFree(s->opt_gsum);
       gsum = nullptr;
     }
   }
   s->opt_gsum = gsum;
-  s->opt_state = state[0];
-  s->opt_state2 = state[1];
+  for (int i = 0; i < 2; ++i) s->opt_slot[i] = state[i];
   s->opt = cfg;
   return opt_reset_state(s);
 }
@@ -2364,18 +2353,7 @@ void* opt_slot_array(pskv_shard* s, int slot, const char* who) {
                                 " (slots: SGD 0, Adagrad 1, momentum 1, Adam 2)");
     return nullptr;
   }
-  return slot == 0 ? s->opt_state : s->opt_state2;
-}
-
-// A Get on the state array `arr` (pskv_get_state, pskv_get_state_slot).
-int state_get(pskv_shard* s, void* arr, const uint32_t* keys, uint64_t n, void* out, int flags, const char* who) {
-  int rc = use_device(s);
-  if (rc) return rc;
-  rc = srv_stop(s);
-  if (rc) return rc;
-  pskv_batch b{keys, out, n};
-  return rows_get_from(s, std::vector<pskv_batch>{b}, flags, DenseView{arr, s->key_begin, s->range}, who,
-                       /*count_get=*/false);
+  return s->opt_slot[slot];
 }
 
 }  // namespace
@@ -2536,8 +2514,8 @@ int pskv_shard_destroy(pskv_shard* s) {
   if (s->dense) (void)hipFree(s->dense);
   if (s->owner) (void)hipFree(s->owner);
   if (s->opt_gsum) (void)hipFree(s->opt_gsum);
-  if (s->opt_state) (void)hipFree(s->opt_state);
-  if (s->opt_state2) (void)hipFree(s->opt_state2);
+  for (void* p : s->opt_slot)
+    if (p) (void)hipFree(p);
   if (s->flag) (void)hipFree(s->flag);
   for (const auto& t : s->tables) {  // (the service no longer touches the list)
     (void)hipFree(t.keys);
@@ -2603,9 +2581,7 @@ int pskv_get_grouped(pskv_shard* s, const pskv_batch* batches, uint64_t nb, int 
 }
 
 int pskv_shard_set_optimizer(pskv_shard* s, const pskv_optimizer* cfg) {
-  // the configuration first: a bad field is reported whatever the handle
-  if (const char* what = opt_config_error(cfg))
-    return fail(PSKV_EINVAL, std::string("pskv_shard_set_optimizer: ") + what);
+  if (!cfg) return fail(PSKV_EINVAL, "pskv_shard_set_optimizer: null configuration");
   pskv_optimizer_ex x{};
   x.size = sizeof(x);
   x.kind = cfg->kind;
@@ -2613,13 +2589,12 @@ int pskv_shard_set_optimizer(pskv_shard* s, const pskv_optimizer* cfg) {
   x.weight_decay = cfg->weight_decay;
   x.eps = cfg->eps;
   x.init_accum = cfg->init_accum;
-  return set_optimizer_impl(s, x, "pskv_shard_set_optimizer");
+  return set_optimizer_impl(s, x, /*legacy=*/true, "pskv_shard_set_optimizer");
 }
 
 int pskv_shard_set_optimizer_ex(pskv_shard* s, const pskv_optimizer_ex* cfg) {
-  if (const char* what = opt_config_error_ex(cfg))
-    return fail(PSKV_EINVAL, std::string("pskv_shard_set_optimizer_ex: ") + what);
-  return set_optimizer_impl(s, *cfg, "pskv_shard_set_optimizer_ex");
+  if (!cfg) return fail(PSKV_EINVAL, "pskv_shard_set_optimizer_ex: null configuration");
+  return set_optimizer_impl(s, *cfg, /*legacy=*/false, "pskv_shard_set_optimizer_ex");
 }
 
 int pskv_shard_get_optimizer(pskv_shard* s, pskv_optimizer* out, uint64_t* state_bytes) {
@@ -2672,36 +2647,39 @@ int pskv_apply_grouped(pskv_shard* s, const pskv_batch* batches, uint64_t nb, in
   return apply_impl(s, std::vector<pskv_batch>(batches, batches + nb), flags);
 }
 
-int pskv_get_state(pskv_shard* s, const uint32_t* keys, uint64_t n, void* out, int flags) {
-  if (!s) return fail(PSKV_EINVAL, "pskv_get_state: null shard");
-  if (bad_flags(flags)) return fail(PSKV_EINVAL, "pskv_get_state: unknown flags");
-  if (s->opt.kind != PSKV_OPT_ADAGRAD || !s->opt_state)
-    return fail(PSKV_EINVAL, "pskv_get_state: the shard's optimizer is not PSKV_OPT_ADAGRAD (the other kinds' state: "
-                             "pskv_get_state_slot)");
-  return state_get(s, s->opt_state, keys, n, out, flags, "pskv_get_state");
-}
-
-int pskv_get_state_slot(pskv_shard* s, int slot, const uint32_t* keys, uint64_t n, void* out, int flags) {
-  if (!s) return fail(PSKV_EINVAL, "pskv_get_state_slot: null shard");
-  if (bad_flags(flags)) return fail(PSKV_EINVAL, "pskv_get_state_slot: unknown flags");
-  void* arr = opt_slot_array(s, slot, "pskv_get_state_slot");
-  if (!arr) return PSKV_EINVAL;
-  return state_get(s, arr, keys, n, out, flags, "pskv_get_state_slot");
-}
-
-int pskv_put_state(pskv_shard* s, int slot, const uint32_t* keys, const void* vals, uint64_t n, int flags) {
-  if (!s) return fail(PSKV_EINVAL, "pskv_put_state: null shard");
-  if (bad_flags(flags)) return fail(PSKV_EINVAL, "pskv_put_state: unknown flags");
-  void* arr = opt_slot_array(s, slot, "pskv_put_state");
+// The three state entry points: a row Get from, or (put) a row assign Add
+// to, the array of `slot`.  adagrad_only: pskv_get_state's guard.
+static int state_call(pskv_shard* s, const std::string& who, bool adagrad_only, int slot, const uint32_t* keys,
+                      void* vals, uint64_t n, int flags, bool put) {
+  if (!s) return fail(PSKV_EINVAL, who + ": null shard");
+  if (bad_flags(flags)) return fail(PSKV_EINVAL, who + ": unknown flags");
+  if (adagrad_only && (s->opt.kind != PSKV_OPT_ADAGRAD || !s->opt_slot[0]))
+    return fail(PSKV_EINVAL, who + ": the shard's optimizer is not PSKV_OPT_ADAGRAD (the other kinds' state: "
+                                   "pskv_get_state_slot)");
+  void* arr = opt_slot_array(s, slot, who.c_str());
   if (!arr) return PSKV_EINVAL;
   int rc = use_device(s);
   if (rc) return rc;
   rc = srv_stop(s);
   if (rc) return rc;
-  pskv_batch b{keys, const_cast<void*>(vals), n};
-  return rows_add_to(s, std::vector<pskv_batch>{b}, flags, DenseView{arr, s->key_begin, s->range}, PSKV_ASSIGN,
-                     "pskv_put_state", "key", "optimizer state is kept for the shard's own keys only",
-                     /*count_add=*/false);
+  const std::vector<pskv_batch> in{pskv_batch{keys, vals, n}};
+  const DenseView d{arr, s->key_begin, s->range};
+  if (!put) return rows_get_from(s, in, flags, d, who.c_str(), nullptr);
+  return rows_add_to(s, in, flags, d, PSKV_ASSIGN,
+                     RowFront{who.c_str(), nullptr, false, "key",
+                              "optimizer state is kept for the shard's own keys only", /*with_values=*/true});
+}
+
+int pskv_get_state(pskv_shard* s, const uint32_t* keys, uint64_t n, void* out, int flags) {
+  return state_call(s, "pskv_get_state", /*adagrad_only=*/true, 0, keys, out, n, flags, /*put=*/false);
+}
+
+int pskv_get_state_slot(pskv_shard* s, int slot, const uint32_t* keys, uint64_t n, void* out, int flags) {
+  return state_call(s, "pskv_get_state_slot", false, slot, keys, out, n, flags, /*put=*/false);
+}
+
+int pskv_put_state(pskv_shard* s, int slot, const uint32_t* keys, const void* vals, uint64_t n, int flags) {
+  return state_call(s, "pskv_put_state", false, slot, keys, const_cast<void*>(vals), n, flags, /*put=*/true);
 }
 
 int pskv_apply_time(pskv_shard* s, uint64_t* launches, double* total_ms, uint64_t* elements) {

@@ -421,12 +421,44 @@ static void test_bucket_rule() {
   EXPECT(n.bm.nbd == 100 && n.bm.nlog == -1 && n.bm.magic == (uint32_t)(((1ull << 32) + 99) / 100));
 }
 
+// first_key_outside: the key a host row call names when it refuses its input.
+static void test_first_key_outside() {
+  auto first = [](const std::vector<std::vector<uint32_t>>& keys, uint32_t key_begin, uint64_t range) -> long {
+    std::vector<pskv_batch> v;
+    for (const auto& k : keys) v.push_back(pskv_batch{k.data(), nullptr, k.size()});
+    const uint32_t* at = first_key_outside(v, key_begin, range);
+    if (!at) return -1;
+    // the pointer lies in one of the batches: report (batch << 16) | index
+    for (size_t b = 0; b < keys.size(); ++b)
+      if (!keys[b].empty() && at >= keys[b].data() && at < keys[b].data() + keys[b].size())
+        return (long)((b << 16) | (size_t)(at - keys[b].data()));
+    return -2;
+  };
+  EXPECT(first({}, 0, 10) == -1);
+  EXPECT(first({{0u, 9u, 5u}, {3u}}, 0, 10) == -1);                           // no such key
+  EXPECT(first({{10u, 19u}, {12u}}, 10, 10) == -1);
+  EXPECT(first({{1u, 2u}, {3u, 10u, 4u, 11u}, {12u}}, 0, 10) == ((1 << 16) | 1));  // the first of several
+  EXPECT(first({{9u, 20u, 21u}}, 10, 10) == 0);                               // a key equal to key_begin - 1
+  EXPECT(first({{10u, 20u}}, 10, 10) == 1);                                   // a key equal to key_end
+  EXPECT(first({{5u, 0x80000000u, 0xFFFFFFFFu}}, 0, 1ull << 31) == 1);        // a key >= 2^31
+  EXPECT(first({{5u, 0x80000000u, 0xFFFFFFFFu}}, 0, (1ull << 31) + 1) == 2);
+  EXPECT(first({{0u, 0x80000000u, 0xFFFFFFFFu}}, 0, 1ull << 32) == -1);       // range = 2^32: every key inside
+  // a wrapped range whose key_begin > 0: 0xFFFFFFF0 .. 2^32 - 1, 0 .. 15
+  EXPECT(first({{0xFFFFFFF0u, 0xFFFFFFFFu, 0u, 15u}}, 0xFFFFFFF0u, 32) == -1);
+  EXPECT(first({{0xFFFFFFF0u, 0u, 15u, 16u, 0xFFFFFFEFu}}, 0xFFFFFFF0u, 32) == 3);
+  EXPECT(first({{0xFFFFFFFFu}, {0xFFFFFFEFu}}, 0xFFFFFFF0u, 32) == (1 << 16));
+  EXPECT(first({{1u}, {}, {2u, 77u}}, 0, 10) == ((2 << 16) | 1));             // an empty batch between two others
+  EXPECT(first({{}, {77u}, {}}, 0, 10) == (1 << 16));
+  EXPECT(first({{3u, 4u}}, 3, 0) == 0);                                       // an empty range owns nothing
+}
+
 int main() {
   test_push_pieces();
   test_split_groups();
   test_layout();
   test_windows();
   test_key_check();
+  test_first_key_outside();
   test_bucket_rule();
   std::printf("host_plan_test: %d passed, %d failed\n", passed, failed);
   return failed ? 1 : 0;

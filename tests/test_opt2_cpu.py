@@ -1,6 +1,6 @@
 """CPU tests of momentum and Adam steps: the new exports and constants, the
 argument checks that need no device, the np.longdouble oracle of
-tests/opt2_util.py pinned against a per-key loop and (Adam) against
+tests/opt_util.py pinned against a per-key loop and (Adam) against
 torch.optim.SparseAdam, the two conditions that bind the tolerances on the GPU
 bound tests' own inputs, and the exactness of the dyadic momentum cases.  No
 kernel is launched here."""
@@ -11,7 +11,6 @@ import os
 import numpy as np
 import pytest
 
-import opt2_util as o2
 import opt_util as ou
 from rows_util import LAYOUTS
 
@@ -140,13 +139,13 @@ def test_the_old_setter_still_refuses_the_new_kinds():
 def test_oracle_matches_a_per_key_loop(kind, nesterov):
     rng = np.random.default_rng(12)
     w, rows, t = 3, 20, 3
-    hp = o2.hyper(kind, wd=0.01, nesterov=nesterov)
+    hp = ou.hyper(kind, wd=0.01, nesterov=nesterov)
     idx = rng.integers(0, rows - 2, size=50)  # the last two rows are never touched
     assert np.unique(idx).size < idx.size
     grads = rng.standard_normal((50, w)) * 3
     p = rng.standard_normal((rows, w))
-    slots = [np.abs(rng.standard_normal((rows, w))) for _ in range(o2.SLOTS[kind])]
-    ref = o2.step_ref(p, slots, idx, grads, hp, t)
+    slots = [np.abs(rng.standard_normal((rows, w))) for _ in range(ou.SLOTS[kind])]
+    ref = ou.step_ref(p, slots, idx, grads, hp, t)
     for k in range(rows):
         occ = [i for i in range(50) if idx[i] == k]
         assert ref["m"][k] == len(occ)
@@ -174,13 +173,13 @@ def test_oracle_matches_a_per_key_loop(kind, nesterov):
     # the checker accepts the oracle's own result rounded to the value type, and objects to a moved untouched key
     for dt in (np.float32, np.float64):
         p_t, s_t, g_t = p.astype(dt), [s.astype(dt) for s in slots], grads.astype(dt)
-        r = o2.step_ref(p_t, s_t, idx, g_t, hp, t)
+        r = ou.step_ref(p_t, s_t, idx, g_t, hp, t)
         got_p, got_s = r["p"].astype(dt), [s.astype(dt) for s in r["slots"]]
-        o2.check_step(p_t, s_t, idx, g_t, got_p, got_s, dt, hp, t)
+        ou.check_step(p_t, s_t, idx, g_t, got_p, got_s, dt, hp, t)
         for which in range(1 + len(got_s)):
             moved = [got_p.copy()] + [s.copy() for s in got_s]
             moved[which][rows - 1, 0] += 1
-            assert o2.step_errors(p_t, s_t, idx, g_t, moved[0], moved[1:], dt, hp, t)
+            assert ou.step_errors(p_t, s_t, idx, g_t, moved[0], moved[1:], dt, hp, t)
 
 
 @pytest.mark.parametrize("coalesce", [False, True], ids=["distinct", "coalesced_duplicates"])
@@ -195,11 +194,11 @@ def test_adam_oracle_matches_torch_sparse_adam(coalesce):
 
     rng = np.random.default_rng(21 + coalesce)
     rows, w = 12, 3
-    hp = o2.hyper("adam", lr=0.05, eps=1e-8, beta1=0.9, beta2=0.999)
+    hp = ou.hyper("adam", lr=0.05, eps=1e-8, beta1=0.9, beta2=0.999)
     p0 = rng.standard_normal((rows, w))
     param = torch.nn.Parameter(torch.tensor(p0, dtype=torch.float64))
     opt = torch.optim.SparseAdam([param], lr=hp["lr"], betas=(hp["beta1"], hp["beta2"]), eps=hp["eps"])
-    p, slots = p0.copy(), o2.zero_slots("adam", p0.shape, np.float64)
+    p, slots = p0.copy(), ou.zero_slots("adam", p0.shape, np.float64)
     for t in (1, 2, 3):
         if coalesce:
             idx = rng.integers(0, rows - 3, size=9)  # duplicates: the sparse gradient sums them
@@ -210,7 +209,7 @@ def test_adam_oracle_matches_torch_sparse_adam(coalesce):
         param.grad = torch.sparse_coo_tensor(torch.tensor(idx[None, :]), torch.tensor(grads), (rows, w)).coalesce()
         before = param.detach().numpy().copy()
         opt.step()
-        ref = o2.step_ref(p, slots, idx, grads, dict(hp, eps=hp["eps"] * float(o2.bias_corrections(hp, t)[1])), t)
+        ref = ou.step_ref(p, slots, idx, grads, dict(hp, eps=hp["eps"] * float(ou.bias_corrections(hp, t)[1])), t)
         untouched = np.setdiff1d(np.arange(rows), idx)
         assert np.array_equal(ref["p"][untouched], p[untouched])
         assert all(np.array_equal(sn[untouched], s[untouched]) for sn, s in zip(ref["slots"], slots))
@@ -226,12 +225,12 @@ def test_adam_oracle_matches_torch_sparse_adam(coalesce):
 def _walk(case, dt):
     """The bound case's three steps along the oracle: (t, p, slots, idx, grads, ref) per step."""
     kb, _ = LAYOUTS[case[0]]
-    hp = o2.case_hyper(case)
-    p0, calls = o2.bound_steps(case, dt)
-    p, slots = p0.copy(), o2.zero_slots(hp["kind"], p0.shape, dt)
+    hp = ou.case_hyper(case)
+    p0, calls = ou.bound_steps2(case, dt)
+    p, slots = p0.copy(), ou.zero_slots(hp["kind"], p0.shape, dt)
     for t, (keys, grads) in enumerate(calls, 1):
         idx = keys.astype(np.int64) - kb
-        pre = o2.prepare(p, slots, idx, grads, dt, hp, t)
+        pre = ou.prepare(p, slots, idx, grads, dt, hp, t)
         ref = pre[0]
         yield t, p, slots, idx, grads, pre, hp
         p, slots = ref["p"].astype(dt), [s.astype(dt) for s in ref["slots"]]
@@ -243,12 +242,12 @@ def test_an_emulation_of_the_kernel_order_passes_the_checker(dt):
     float32 / float64 numpy arithmetic -- the losers' rows added one by one in
     call order and in a random order, then the rule -- is inside the tolerances."""
     dt = np.dtype(dt)
-    for case in o2.bound_cases():
+    for case in ou.bound_cases2():
         rng = np.random.default_rng(ou.case_seed("perm", case))
         for t, p, slots, idx, grads, pre, hp in _walk(case, dt):
             for order in (None, rng):
-                got_p, got_s = o2.emulate(p, slots, idx, grads, dt, hp, t, order)
-                o2.check_step(p, slots, idx, grads, got_p, got_s, dt, hp, t, pre=pre, msg=f"{case} t {t}")
+                got_p, got_s = ou.emulate(p, slots, idx, grads, dt, hp, t, order)
+                ou.check_step(p, slots, idx, grads, got_p, got_s, dt, hp, t, pre=pre, msg=f"{case} t {t}")
 
 
 def _sequential(ref, p, slots, idx, grads, rows, hp, t):
@@ -257,7 +256,7 @@ def _sequential(ref, p, slots, idx, grads, rows, hp, t):
     for k in rows:
         pk, sk = p[k:k + 1].astype(ou.F), [s[k:k + 1].astype(ou.F) for s in slots]
         for i in np.flatnonzero(idx == k):
-            r = o2.step_ref(pk, sk, [0], grads[i:i + 1], hp, t)
+            r = ou.step_ref(pk, sk, [0], grads[i:i + 1], hp, t)
             pk, sk = r["p"], r["slots"]
         pn[k] = pk[0]
         for s, x in zip(sn, sk):
@@ -273,24 +272,24 @@ def test_the_checker_rejects_wrong_semantics_on_the_gpu_tests_inputs(dt):
     dt = np.dtype(dt)
     seen = 0
     carried_by = set()
-    for case in o2.bound_cases():
+    for case in ou.bound_cases2():
         for t, p, slots, idx, grads, pre, hp in _walk(case, dt):
             ref = pre[0]
-            o2.check_step(p, slots, idx, grads, ref["p"].astype(dt), [s.astype(dt) for s in ref["slots"]], dt, hp, t,
+            ou.check_step(p, slots, idx, grads, ref["p"].astype(dt), [s.astype(dt) for s in ref["slots"]], dt, hp, t,
                           pre=pre, msg=str(case))
             dup = np.flatnonzero(ref["m"] > 1)
             if not dup.size:
                 continue
             seen += 1
             sp, ss = _sequential(ref, p, slots, idx, grads, dup[:4], hp, t)
-            bad = o2.step_errors(p, slots, idx, grads, sp.astype(dt), [s.astype(dt) for s in ss], dt, hp, t, pre=pre)
+            bad = ou.step_errors(p, slots, idx, grads, sp.astype(dt), [s.astype(dt) for s in ss], dt, hp, t, pre=pre)
             assert bad, f"sequential steps accepted: {case} t {t}"
             carried_by |= {name for name, _ in bad}
             first = int(np.flatnonzero(idx == dup[0])[0])  # a loser: not the key's last occurrence
             keep = np.ones(idx.size, dtype=bool)
             keep[first] = False
-            dr = o2.step_ref(p, slots, idx[keep], grads[keep], hp, t)
-            bad = o2.step_errors(p, slots, idx, grads, dr["p"].astype(dt), [s.astype(dt) for s in dr["slots"]], dt,
+            dr = ou.step_ref(p, slots, idx[keep], grads[keep], hp, t)
+            bad = ou.step_errors(p, slots, idx, grads, dr["p"].astype(dt), [s.astype(dt) for s in dr["slots"]], dt,
                                  hp, t, pre=pre)
             assert bad, f"a dropped loser accepted: {case} t {t}"
             carried_by |= {name for name, _ in bad}
@@ -312,18 +311,18 @@ def test_dyadic_momentum_cases_are_exact_in_float32(nesterov):
     v, the Nesterov sum, lr times it, the new p -- is representable in float32,
     so float32 and float64 arithmetic have nothing to round, with or without
     FMA contraction."""
-    hp = o2.dyadic_hyper(nesterov)
+    hp = ou.dyadic_hyper(nesterov)
     mu, lr = ou.F(hp["mu"]), ou.F(hp["lr"])
     for n, w, pat in [(4100, 1, "all_equal"), (4100, 3, "dups_in_chunk"), (2049, 4, "dups_across_chunks"),
                       (2049, 16, "distinct"), (1, 33, "range_ends"), (4100, 64, "all_equal")]:
         kb, _ = LAYOUTS[0]
-        p0, calls = o2.dyadic_steps(n, w, pat, 0, np.float32)
+        p0, calls = ou.dyadic_steps2(n, w, pat, 0, np.float32)
         assert len(calls) == 3
         p, v = p0.astype(ou.F), np.zeros(p0.shape, dtype=ou.F)
         for keys, grads in calls:
             idx = keys.astype(np.int64) - kb
             assert np.array_equal(grads * 16, np.round(grads * 16)) and np.abs(grads).max() <= 8
-            ref = o2.step_ref(p, [v], idx, grads, hp)
+            ref = ou.step_ref(p, [v], idx, grads, hp)
             # every partial sum is a multiple of 2^-4 below 2^24 * 2^-4: exact in any order
             assert ref["G"].max() * 16 < 2**24
             d, vn = ref["d"], ref["slots"][0]

@@ -2,7 +2,7 @@
 step counter, of state slot access (pskv_get_state_slot, pskv_put_state) and of
 checkpoints (Shard.state_dict / load_state_dict).
 
-Two bars (tests/opt2_util.py), as tests/test_opt_gpu.py:
+Two bars (tests/opt_util.py), as tests/test_opt_gpu.py:
   * dyadic momentum inputs, whose every intermediate is exact in float32
     (tests/test_opt2_cpu.py proves it): p and v compared bit for bit;
   * random inputs, momentum (Nesterov on and off) and Adam, weight decay 0 and
@@ -16,7 +16,6 @@ import subprocess
 import numpy as np
 import pytest
 
-import opt2_util as o2
 import opt_util as ou
 from rows_util import LAYOUTS, bits
 from test_gpu_parity import tdev
@@ -32,7 +31,7 @@ PATTERNS = ["distinct", "all_equal", "dups_in_chunk", "dups_across_chunks", "ran
 
 def read_slots(sh, kind):
     keys = all_keys(sh.key_begin, sh.key_end)
-    return [rows_of(sh, sh.get_state(keys, slot=i)) for i in range(o2.SLOTS[kind])]
+    return [rows_of(sh, sh.get_state(keys, slot=i)) for i in range(ou.SLOTS[kind])]
 
 
 # ------------------------------------------------ dyadic momentum, bit-exact
@@ -56,18 +55,18 @@ def test_momentum_dyadic_is_bit_exact(cuda, dt, li, n, pat, w, nesterov):
 
     dt = np.dtype(dt)
     kb, ke = LAYOUTS[li]
-    p0, calls = o2.dyadic_steps(n, w, pat, li, dt)
-    hp = o2.dyadic_hyper(nesterov)
+    p0, calls = ou.dyadic_steps2(n, w, pat, li, dt)
+    hp = ou.dyadic_hyper(nesterov)
     keys_all = all_keys(kb, ke)
     with ps.Shard(kb, ke, dt, width=w) as sh:
-        sh.set_optimizer("momentum", **o2.set_optimizer_kwargs(hp))
+        sh.set_optimizer("momentum", **ou.set_optimizer_kwargs(hp))
         for path in PATHS:
             sh.clear()
             sh.add(keys_all, p0)
             p, v = p0, np.zeros(p0.shape, dtype=dt)
             for step, (keys, grads) in enumerate(calls):
                 do_apply(sh, keys, grads, path, cuda)
-                ref = o2.step_ref(p, [v], keys.astype(np.int64) - kb, grads, hp)
+                ref = ou.step_ref(p, [v], keys.astype(np.int64) - kb, grads, hp)
                 p, v = ref["p"].astype(dt), ref["slots"][0].astype(dt)
                 assert_bits(read_p(sh), p, f"p {path} step {step}")
                 assert_bits(read_slots(sh, "momentum")[0], v, f"v {path} step {step}")
@@ -78,7 +77,7 @@ def test_momentum_dyadic_is_bit_exact(cuda, dt, li, n, pat, w, nesterov):
 # ------------------------------------------------ momentum and Adam: bounds
 def _bound_params():
     out = []
-    for i, case in enumerate(o2.bound_cases()):
+    for i, case in enumerate(ou.bound_cases2()):
         for dt in (np.float32, np.float64):
             path = PATHS[i % len(PATHS)]
             out.append(pytest.param(case, dt, path, id=f"{'-'.join(map(str, case))}-{np.dtype(dt).name}-{path}"))
@@ -92,10 +91,10 @@ def test_steps_meet_the_one_step_bound(cuda, case, dt, path):
     li, n, w, pat, kind, _, _ = case
     dt = np.dtype(dt)
     kb, ke = LAYOUTS[li]
-    hp = o2.case_hyper(case)
-    p0, calls = o2.bound_steps(case, dt)
+    hp = ou.case_hyper(case)
+    p0, calls = ou.bound_steps2(case, dt)
     with ps.Shard(kb, ke, dt, width=w) as sh:
-        sh.set_optimizer(kind, **o2.set_optimizer_kwargs(hp))
+        sh.set_optimizer(kind, **ou.set_optimizer_kwargs(hp))
         sh.add(all_keys(kb, ke), p0)
         for s in read_slots(sh, kind):
             assert not s.any(), "initial state"
@@ -103,7 +102,7 @@ def test_steps_meet_the_one_step_bound(cuda, case, dt, path):
             p, slots = read_p(sh), read_slots(sh, kind)
             do_apply(sh, keys, grads, path, cuda)
             assert sh.step == t
-            o2.check_step(p, slots, keys.astype(np.int64) - kb, grads, read_p(sh), read_slots(sh, kind), dt, hp, t,
+            ou.check_step(p, slots, keys.astype(np.int64) - kb, grads, read_p(sh), read_slots(sh, kind), dt, hp, t,
                           msg=f"{path} step {t}")
         sh.sync()
 
@@ -126,13 +125,13 @@ def test_65_batches_are_one_momentum_step(cuda, w, device):
     kb, ke = 100, 140
     rng = np.random.default_rng(650 + w)
     p0 = ou.dyadic_params(rng, ke - kb, w, np.float32)
-    hp = o2.dyadic_hyper(True)
+    hp = ou.dyadic_hyper(True)
     batches, cat_k, cat_g = _tiny_batches(rng, kb, w)
-    ref = o2.step_ref(p0, [np.zeros_like(p0)], cat_k.astype(np.int64) - kb, cat_g, hp)
+    ref = ou.step_ref(p0, [np.zeros_like(p0)], cat_k.astype(np.int64) - kb, cat_g, hp)
     got = []
     for grouped in (True, False):
         with ps.Shard(kb, ke, np.float32, width=w) as sh:
-            sh.set_optimizer("momentum", **o2.set_optimizer_kwargs(hp))
+            sh.set_optimizer("momentum", **ou.set_optimizer_kwargs(hp))
             sh.add(all_keys(kb, ke), p0)
             if grouped:
                 sh.apply_grouped([(tdev(k, cuda), tdev(g, cuda)) for k, g in batches] if device else batches)
@@ -159,18 +158,18 @@ def test_65_batches_are_one_adam_step(cuda, device):
     dt = np.dtype(np.float32)
     rng = np.random.default_rng(651)
     p0 = rng.standard_normal((ke - kb, w)).astype(dt)
-    hp = o2.hyper("adam", wd=0.01)
+    hp = ou.hyper("adam", wd=0.01)
     batches, cat_k, cat_g = _tiny_batches(rng, kb, w)
     for grouped in (True, False):
         with ps.Shard(kb, ke, dt, width=w) as sh:
-            sh.set_optimizer("adam", **o2.set_optimizer_kwargs(hp))
+            sh.set_optimizer("adam", **ou.set_optimizer_kwargs(hp))
             sh.add(all_keys(kb, ke), p0)
             if grouped:
                 sh.apply_grouped([(tdev(k, cuda), tdev(g, cuda)) for k, g in batches] if device else batches)
             else:
                 sh.apply(tdev(cat_k, cuda), tdev(cat_g, cuda)) if device else sh.apply(cat_k, cat_g)
             assert sh.step == 1
-            o2.check_step(p0, o2.zero_slots("adam", p0.shape, dt), cat_k.astype(np.int64) - kb, cat_g, read_p(sh),
+            ou.check_step(p0, ou.zero_slots("adam", p0.shape, dt), cat_k.astype(np.int64) - kb, cat_g, read_p(sh),
                           read_slots(sh, "adam"), dt, hp, 1, msg=f"grouped {grouped}")
             sh.sync()
 
@@ -189,10 +188,10 @@ def test_step_counter(cuda):
     bad = keys.copy()
     bad[77], bad[300] = 3007, 12  # outside on both sides
     inside = (bad >= kb) & (bad < ke)
-    hp = o2.hyper("adam")
+    hp = ou.hyper("adam")
     with ps.Shard(kb, ke, dt, width=w) as sh:
         assert sh.step == 0
-        sh.set_optimizer("adam", **o2.set_optimizer_kwargs(hp))
+        sh.set_optimizer("adam", **ou.set_optimizer_kwargs(hp))
         sh.add(all_keys(kb, ke), p0)
         assert sh.step == 0  # an Add is no step
         sh.apply(keys, grads)
@@ -214,14 +213,14 @@ def test_step_counter(cuda):
         # a device call with out-of-range keys: the in-range keys step (t = 3), the next sync reports
         sh.apply(tdev(bad, cuda), tdev(grads, cuda))
         assert sh.step == 3
-        o2.check_step(p, slots, bad[inside].astype(np.int64) - kb, grads[inside], read_p(sh), read_slots(sh, "adam"),
+        ou.check_step(p, slots, bad[inside].astype(np.int64) - kb, grads[inside], read_p(sh), read_slots(sh, "adam"),
                       dt, hp, 3, msg="device apply with out-of-range keys")
         with pytest.raises(_lib.PskvError) as e:
             sh.sync()
         assert e.value.code == _lib.PSKV_ESTATE and "out-of-range" in str(e.value)
         # the same kind with a new lr keeps t and the state
         slots = read_slots(sh, "adam")
-        sh.set_optimizer("adam", **dict(o2.set_optimizer_kwargs(hp), lr=0.01))
+        sh.set_optimizer("adam", **dict(ou.set_optimizer_kwargs(hp), lr=0.01))
         assert sh.step == 3 and sh.optimizer()["lr"] == 0.01
         for a, b, nm in zip(read_slots(sh, "adam"), slots, "mv"):
             assert_bits(a, b, f"a new lr changed {nm}")
@@ -231,10 +230,10 @@ def test_step_counter(cuda):
         assert sh.step == 0 and not read_p(sh).any()
         for s in read_slots(sh, "adam"):
             assert not s.any()
-        hp2 = o2.hyper("adam", lr=0.01)
+        hp2 = ou.hyper("adam", lr=0.01)
         sh.apply(keys, grads)
         assert sh.step == 1
-        o2.check_step(np.zeros_like(p0), o2.zero_slots("adam", p0.shape, dt), keys.astype(np.int64) - kb, grads,
+        ou.check_step(np.zeros_like(p0), ou.zero_slots("adam", p0.shape, dt), keys.astype(np.int64) - kb, grads,
                       read_p(sh), read_slots(sh, "adam"), dt, hp2, 1, msg="the step after clear")
         # a kind change resets t and the state
         sh.set_optimizer("momentum", lr=0.05, momentum=0.9)
@@ -470,8 +469,8 @@ def test_hip_storage_with_a_momentum_optimizer(cuda):
     from parameter_server_amd.storage import Flag, HipStorage, Message, typed
 
     w = 4
-    hp = o2.dyadic_hyper(False)
-    opt = dict(kind="momentum", **o2.set_optimizer_kwargs(hp))
+    hp = ou.dyadic_hyper(False)
+    opt = dict(kind="momentum", **ou.set_optimizer_kwargs(hp))
     keys = np.array([5, 9, 5], dtype=np.uint32)
     g1 = np.arange(12, dtype=np.float32).reshape(3, w) / 4
     g2 = g1[::-1].copy() + 1
@@ -490,9 +489,9 @@ def test_hip_storage_with_a_momentum_optimizer(cuda):
 
     idx = np.array([0, 1, 0])  # rows of keys 5, 9 (7 is row 2)
     zero = np.zeros((3, w))
-    r1 = o2.step_ref(zero, [zero], idx, g1, hp)
-    two = o2.step_ref(r1["p"], r1["slots"], idx, g2, hp)["p"]
-    one = o2.step_ref(zero, [zero], np.concatenate([idx, idx]), np.concatenate([g1, g2]), hp)["p"]
+    r1 = ou.step_ref(zero, [zero], idx, g1, hp)
+    two = ou.step_ref(r1["p"], r1["slots"], idx, g2, hp)["p"]
+    one = ou.step_ref(zero, [zero], np.concatenate([idx, idx]), np.concatenate([g1, g2]), hp)["p"]
     assert not np.array_equal(one, two)
     st = HipStorage(np.float32, 0, 100, width=w, optimizer=opt)
     try:

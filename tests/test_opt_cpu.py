@@ -138,10 +138,10 @@ def test_oracle_matches_a_per_key_loop(kind):
     for dt in (np.float32, np.float64):
         p_t, h_t = p.astype(dt), h.astype(dt)
         r = ou.step64(p_t, h_t, idx, grads.astype(dt), kind, lr, wd, eps)
-        ou.check_step(p_t, h_t, idx, grads.astype(dt), r["p"].astype(dt), r["h"].astype(dt), dt, kind, lr, wd, eps)
+        ou.check_step64(p_t, h_t, idx, grads.astype(dt), r["p"].astype(dt), r["h"].astype(dt), dt, kind, lr, wd, eps)
         moved = r["p"].astype(dt)
         moved[rows - 1, 0] += 1  # an untouched key changed: the checker must object
-        assert ou.step_errors(p_t, h_t, idx, grads.astype(dt), moved, r["h"].astype(dt), dt, kind, lr, wd, eps)
+        assert ou.step_errors64(p_t, h_t, idx, grads.astype(dt), moved, r["h"].astype(dt), dt, kind, lr, wd, eps)
 
 
 def _sequential(ref, p, h, idx, grads, rows, kind, lr, wd, eps):
@@ -175,19 +175,19 @@ def test_the_checker_rejects_wrong_semantics_on_the_gpu_tests_inputs(dt):
             idx = keys.astype(np.int64) - kb
             ref = ou.step64(p, h, idx, grads, kind, lr, wd, eps)
             good_p, good_h = ref["p"].astype(dt), ref["h"].astype(dt)
-            ou.check_step(p, h, idx, grads, good_p, good_h, dt, kind, lr, wd, eps, msg=str(case))
+            ou.check_step64(p, h, idx, grads, good_p, good_h, dt, kind, lr, wd, eps, msg=str(case))
             dup = np.flatnonzero(ref["m"] > 1)
             if dup.size:
                 seen += 1
                 # (for SGD without weight decay m steps ARE one step on the sum; no such case is listed)
                 sp, sh = _sequential(ref, p, h, idx, grads, dup[:4], kind, lr, wd, eps)
-                assert ou.step_errors(p, h, idx, grads, sp.astype(dt), sh.astype(dt), dt, kind, lr, wd, eps), \
+                assert ou.step_errors64(p, h, idx, grads, sp.astype(dt), sh.astype(dt), dt, kind, lr, wd, eps), \
                     f"sequential steps accepted: {case}"
                 first = int(np.flatnonzero(idx == dup[0])[0])  # a loser: not the key's last occurrence
                 keep = np.ones(idx.size, dtype=bool)
                 keep[first] = False
                 dr = ou.step64(p, h, idx[keep], grads[keep], kind, lr, wd, eps)
-                assert ou.step_errors(p, h, idx, grads, dr["p"].astype(dt), dr["h"].astype(dt), dt, kind, lr, wd,
+                assert ou.step_errors64(p, h, idx, grads, dr["p"].astype(dt), dr["h"].astype(dt), dt, kind, lr, wd,
                                       eps), f"a dropped loser accepted: {case}"
             p, h = good_p, good_h
     assert seen > 20

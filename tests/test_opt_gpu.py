@@ -140,7 +140,7 @@ def test_steps_meet_the_one_step_bound(cuda, case, dt, path):
             p = read_p(sh)
             h = read_h(sh) if kind == "adagrad" else None
             do_apply(sh, keys, grads, path, cuda)
-            ou.check_step(p, h, keys.astype(np.int64) - kb, grads, read_p(sh),
+            ou.check_step64(p, h, keys.astype(np.int64) - kb, grads, read_p(sh),
                           read_h(sh) if kind == "adagrad" else None, dt, kind, lr, wd, eps,
                           msg=f"{path} step {step}")
         sh.sync()
@@ -208,7 +208,7 @@ def test_apply_interleaves_with_add_and_get(cuda, w, options):
         grads = (rng.standard_normal((n, w)) * 3).astype(dt)
         p, h = read_p(sh), read_h(sh)
         sh.apply(tdev(keys, cuda), tdev(grads, cuda))
-        ou.check_step(p, h, keys.astype(np.int64) - kb, grads, read_p(sh), read_h(sh), dt, "adagrad", lr, wd, eps)
+        ou.check_step64(p, h, keys.astype(np.int64) - kb, grads, read_p(sh), read_h(sh), dt, "adagrad", lr, wd, eps)
 
     with ps.Shard(kb, ke, dt, width=w, options=options) as sh:
         sh.set_optimizer("adagrad", lr=lr, weight_decay=wd, eps=eps, init_accum=init)
