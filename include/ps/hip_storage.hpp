@@ -31,6 +31,10 @@
 // (pskv_apply); AddGrouped, the BSP model's flush, is ONE step over the summed
 // gradients of all its messages (pskv_apply_grouped).  Float Val only; keys
 // outside the range abort the call (pskv.h "Optimizer steps").
+// Pooled pulls (SubGetPooled, pskv_get_pooled): one reply row per bag of keys,
+// the weighted sum of the bag's rows computed in the shard -- the margin
+// sum_i w[key_i] * x_i of the reference's logistic-regression worker as one
+// pull of one value per sample.  Keys outside the range abort.
 #pragma once
 
 #include <cstdint>
@@ -149,6 +153,24 @@ class HipStorage : public AbstractStorage {
     pskv_check(pskv_get(shard_, typed_keys.data(), typed_keys.size(), reply_vals.data(),
                         PSKV_HOST | PSKV_HOST_FRAME),
                "pskv_get");
+    return third_party::SArray<char>(reply_vals);
+  }
+
+  // One pooled row per bag (pskv_get_pooled): bag b is typed_keys[offsets[b],
+  // offsets[b+1]); weights null: every weight one.  The reply is a frame of
+  // (offsets.size() - 1) * width values.  Not part of AbstractStorage.
+  third_party::SArray<char> SubGetPooled(const third_party::SArray<Key>& typed_keys,
+                                         const third_party::SArray<Val>* weights,
+                                         const third_party::SArray<uint64_t>& offsets) {
+    if (offsets.size() == 0 || (weights && weights->size() != typed_keys.size())) {
+      std::fprintf(stderr, "Check failed: offsets.size() >= 1 and weights.size() == typed_keys.size()\n");
+      std::abort();
+    }
+    const uint64_t nbags = offsets.size() - 1;
+    auto reply_vals = FrameArray<Val>(nbags * width_);
+    pskv_check(pskv_get_pooled(shard_, typed_keys.data(), typed_keys.size(), weights ? weights->data() : nullptr,
+                               offsets.data(), nbags, reply_vals.data(), PSKV_HOST | PSKV_HOST_FRAME),
+               "pskv_get_pooled");
     return third_party::SArray<char>(reply_vals);
   }
 

@@ -129,6 +129,46 @@
  * pskv_put_state and pskv_set_step, restores a shard bit for bit.
  * Not provided: decoupled weight decay (AdamW), amsgrad, per-key step counts.
  *
+ * Pooled pulls (pskv_get_pooled): one row per BAG of keys, a bag
+ * being one sample's contiguous run of the call's keys (bag b = keys
+ * [offsets[b], offsets[b+1])):
+ *     out[b*W + j] = sum over i in the bag of weights[i] * row(keys[i])[j]
+ * -- the margin sum_i w[key_i] * x_i of the reference's logistic-regression
+ * and SVM workers (app/logistic_regression.cpp:441-446), an embedding bag --
+ * computed in the shard, so the reply holds nbags * W values, not n * W.
+ *   - any dtype, any width (1 included), either creation mode; the dense
+ *     parameter array is the only source (no optimizer state, no overflow
+ *     table); the call counts in n_get_calls;
+ *   - everything is computed in the shard's value type T.  weights == NULL:
+ *     every weight is one and nothing is multiplied.  The sum of an empty bag
+ *     is +0; the sum of one term is that term (a bag of one key with NULL
+ *     weights equals pskv_get of the key bit for bit); a longer bag's
+ *     additions run in an order that is a function of the bag's LENGTH alone
+ *     (key order; a bag of more than 256 keys in chunks of 256 whose partial
+ *     sums are added in chunk order), never of the launch, the alignment, an
+ *     option or timing, and there are no atomics: the same call on the same
+ *     contents returns the same bits.  Each multiply-add is one fused
+ *     operation.  PSKV_I32: int32 weights, two's complement with wrap;
+ *   - keys outside [key_begin, key_end) follow pskv_apply's rule at every
+ *     width: a host call returns PSKV_EINVAL naming the first and writes
+ *     nothing; a device call counts such a key as a row of zeros and the next
+ *     pskv_sync returns PSKV_ESTATE (pskv_clear resets it).  This holds at
+ *     width 1 too, where pskv_get would have served the key from the overflow
+ *     table;
+ *   - flags, null pointers with a non-zero count and a host call's offsets
+ *     (offsets[0] == 0, non-decreasing, offsets[nbags] == n) are checked
+ *     before the handle is looked at: PSKV_EINVAL naming the first bad bag,
+ *     also for a null shard.  nbags == 0 is a successful call that does
+ *     nothing more; n == 0 with nbags > 0 writes zeros;
+ *   - device offsets cannot be read by the library: the kernels clamp bag b
+ *     to [min(o_b, n), min(max(o_b+1, o_b), n)), so malformed device offsets
+ *     give unspecified values and never an access outside keys, weights, out;
+ *   - PSKV_HOST_FRAME buffers are treated as plain host memory; a host call is
+ *     synchronous, a device call stream-ordered, as pskv_get; with the
+ *     resident request server (SERVE = 1) the call first ends the server;
+ *   - not provided: a grouped form, mean or max pooling (weights give the
+ *     mean), the backward pass, overflow keys.
+ *
  * Threading: one shard handle is used by one host thread at a time (the
  * reference calls a storage only from its ServerThread, server_thread.cpp:20-50);
  * distinct handles may be used concurrently.  Every call selects the shard's
@@ -268,6 +308,14 @@ int pskv_add(pskv_shard* s, const uint32_t* keys, const void* vals, uint64_t n, 
 /* Pull: out[i] = value of keys[i] (0 if never written).  Synchronous for host
  * `out` (PSKV_HOST), stream-ordered for device `out` (PSKV_DEVICE). */
 int pskv_get(pskv_shard* s, const uint32_t* keys, uint64_t n, void* out, int flags);
+
+/* Pooled pull (semantics: the header comment, "Pooled pulls"):
+ * out[b*W + j] = sum over i in [offsets[b], offsets[b+1]) of weights[i] * row(keys[i])[j].
+ * keys: n keys, bag after bag; weights: n values of the shard's type, or NULL
+ * (every weight one); offsets: nbags + 1 values; out: nbags * W values.
+ * Synchronous for host buffers, stream-ordered for PSKV_DEVICE ones. */
+int pskv_get_pooled(pskv_shard* s, const uint32_t* keys, uint64_t n, const void* weights,
+                    const uint64_t* offsets, uint64_t nbags, void* out, int flags);
 
 /* Grouped forms: nb batches in one call, semantically identical to nb
  * consecutive pskv_add / pskv_get calls in array order, executed in a small,
@@ -428,6 +476,10 @@ int pskv_reset_timing(pskv_shard* s);
  * one operation per launch group (a call of at most 64 batches is one). */
 #define PSKV_TIME_APPLY (1u << 14)
 int pskv_apply_time(pskv_shard* s, uint64_t* launches, double* total_ms, uint64_t* elements);
+/* A pooled pull's launches likewise: one operation per call in a slot of its
+ * own; elements counts keys. */
+#define PSKV_TIME_POOLED (1u << 15)
+int pskv_pooled_time(pskv_shard* s, uint64_t* launches, double* total_ms, uint64_t* elements);
 
 /* Mirror of RangePartitionManager::Slice (base/range_partition_manager.hpp:19-46):
  * walk `keys` once; a key goes to the current range if it lies in it or the

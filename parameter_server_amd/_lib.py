@@ -43,6 +43,7 @@ PSKV_K_ROW_ACCUMULATE = 13
 PSKV_K_COUNT = 14
 PSKV_MAX_WIDTH = 4096
 PSKV_TIME_APPLY = 1 << 14
+PSKV_TIME_POOLED = 1 << 15
 PSKV_OPT_NONE, PSKV_OPT_SGD, PSKV_OPT_ADAGRAD = 0, 1, 2
 PSKV_OPT_MOMENTUM, PSKV_OPT_ADAM = 3, 4  # only through pskv_shard_set_optimizer_ex
 KERNEL_NAMES = {
@@ -75,6 +76,7 @@ EXPORTED = [
     "pskv_get_state", "pskv_apply_time",
     "pskv_shard_set_optimizer_ex", "pskv_shard_get_optimizer_ex", "pskv_get_state_slot", "pskv_put_state",
     "pskv_get_step", "pskv_set_step",
+    "pskv_get_pooled", "pskv_pooled_time",
 ]
 
 
@@ -163,6 +165,8 @@ def _load():
         "pskv_put_state": ([vp, i32, vp, vp, u64, i32], i32),
         "pskv_get_step": ([vp, ctypes.POINTER(u64)], i32),
         "pskv_set_step": ([vp, u64], i32),
+        "pskv_get_pooled": ([vp, vp, u64, vp, vp, u64, vp, i32], i32),
+        "pskv_pooled_time": ([vp, ctypes.POINTER(u64), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(u64)], i32),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)

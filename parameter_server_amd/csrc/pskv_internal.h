@@ -293,4 +293,24 @@ hipError_t launch_row_apply(int dtype, int kind, const GroupArgs& ga, uint32_t n
 // p[0..n) = v (float or double by dtype): the accumulator's initial value.
 hipError_t launch_fill(int dtype, void* p, uint64_t n, double v, hipStream_t st);
 
+// Pooled pull (pskv_get_pooled): out row b = sum over bag b's
+// keys of weight * row(key), in the shard's value type; the bags, their clamp,
+// the order of the additions and the chunks of long bags: pskv_plan.h.
+struct PoolArgs {
+  const uint32_t* keys;     // n
+  const void* weights;      // n values, or null: every weight is one
+  const uint64_t* offsets;  // nbags + 1
+  uint64_t n, nbags;
+  void* out;   // nbags rows
+  void* part;  // pool_slots(n) partial rows of long bags' chunks; null when n <= kPoolChunk
+};
+// Long bags first (launch_row_pooled_chunks, skipped when no bag can be long:
+// n <= kPoolChunk), then every bag (launch_row_pooled).  A key outside the
+// range counts as a zero row and sets kErrRowOutOfRange.  rs by row_shape;
+// unit16 also wants out, part and the dense array 16-byte aligned.
+hipError_t launch_row_pooled_chunks(int dtype, const PoolArgs& a, const DenseView& d, const Ovf& o,
+                                    const RowShape& rs, hipStream_t st);
+hipError_t launch_row_pooled(int dtype, bool nt, const PoolArgs& a, const DenseView& d, const Ovf& o,
+                             const RowShape& rs, hipStream_t st);
+
 }  // namespace pskv

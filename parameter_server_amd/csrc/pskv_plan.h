@@ -1,9 +1,10 @@
 // pskv_plan.h — the host planner: the pure arithmetic of a shard's host paths
 // (pskv_shard.cpp).  How a call's batches are cut into pieces, launch groups
 // and DMA windows, where each batch lies in a staging buffer, the vectorised
-// key check of host inputs, and K5's bucket rule.  No HIP and no shard state:
-// everything here is a function of its arguments, so it is tested on the CPU
-// (tests/cpp/host_plan_test.cpp).  Internal linkage throughout: libpskv.so
+// key check of host inputs, K5's bucket rule, and the bags, chunks and windows
+// of a pooled pull (the part the kernels share is marked PSKV_HD).  No HIP and
+// no shard state: everything here is a function of its arguments, so it is
+// tested on the CPU (tests/cpp/host_plan_test.cpp, tests/cpp/pooled_plan_test.cpp).  Internal linkage throughout: libpskv.so
 // exports nothing from this header (the types the kernels do not share are in
 // an unnamed namespace, so that no instantiation over them is exported either).
 #pragma once
@@ -258,6 +259,101 @@ static inline std::vector<Span> piece_windows(const std::vector<Piece>& pieces, 
     i = j;
   }
   return wins;
+}
+
+// ------------------------------------------------------------ pooled pulls
+// pskv_get_pooled (pskv.h "Pooled pulls"): bag b of a call is
+// keys [offsets[b], offsets[b+1]).  Everything below is a function of its
+// arguments and is shared, where marked PSKV_HD, by k_row_pooled and the CPU
+// test of it (tests/cpp/pooled_plan_test.cpp).
+#if defined(__HIP__)
+#define PSKV_HD __host__ __device__
+#else
+#define PSKV_HD
+#endif
+
+constexpr uint64_t kPoolChunk = 256;      // keys per chunk of a long bag (a bag of more than kPoolChunk keys)
+// Bags per virtual workgroup.  Few, so that a call of few, long bags still
+// spreads over the CUs (1 Mi keys in bags of 64 are 512 workgroups); a row of
+// at most 4 units leaves part of such a workgroup's 256 / L lane groups idle.
+constexpr uint32_t kPoolBagsPerWg = 32;
+constexpr uint64_t kPoolNone = ~0ull;
+
+// The keys of a bag as the kernel takes them: device offsets cannot be checked
+// by the library, so every bag is clamped to
+// [min(o_b, n), min(max(o_b+1, o_b), n)): begin <= end <= n whatever the offsets hold.
+struct PoolBag {
+  uint64_t begin, end;
+};
+PSKV_HD static inline PoolBag pool_clamp(uint64_t o0, uint64_t o1, uint64_t n) {
+  PoolBag b;
+  b.begin = o0 < n ? o0 : n;
+  const uint64_t e = o1 > o0 ? o1 : o0;
+  b.end = e < n ? e : n;
+  return b;
+}
+
+// The order of a bag's additions, a function of its length m alone:
+//   m <= kPoolChunk  t_0, then + t_1, + t_2, ... in key order (t_i = w_i * row_i;
+//                    the sum of no term is +0, the sum of one term is that term)
+//   m >  kPoolChunk  chunk c = keys [c * kPoolChunk, min((c+1) * kPoolChunk, m)) of the
+//                    bag is summed as above into a partial row s_c; the result is
+//                    s_0, then + s_1, + s_2, ... in chunk order.
+PSKV_HD static inline uint64_t pool_chunks(uint64_t m) { return m <= kPoolChunk ? 1 : (m + kPoolChunk - 1) / kPoolChunk; }
+
+// Long bags' chunks are summed by a launch of their own whose work items are
+// the WINDOWS of the call's key array: window q = key positions [q * kPoolChunk,
+// (q+1) * kPoolChunk).  A chunk belongs to the window its first key lies in.
+// A long bag covers more than a window's worth of positions, so it holds the
+// first or the last position of every window one of its chunks starts in: at
+// most two chunks start in a window, one of a bag that holds the window's
+// first position (slot 0) and one of a bag that begins inside it (slot 1).
+// pool_window_chunk: the chunk of the bag [b0, b1) that starts in window q, or
+// kPoolNone (none does, or the bag is not long).
+PSKV_HD static inline uint64_t pool_window_chunk(uint64_t b0, uint64_t b1, uint64_t q) {
+  if (b1 < b0 || b1 - b0 <= kPoolChunk) return kPoolNone;
+  const uint64_t lo = q * kPoolChunk;
+  const uint64_t c = b0 >= lo ? 0 : (lo - b0 + kPoolChunk - 1) / kPoolChunk;
+  const uint64_t p = b0 + c * kPoolChunk;
+  return (p >= lo && p - lo < kPoolChunk && p < b1) ? c : kPoolNone;
+}
+// The partial row of chunk c of the bag that begins at b0: two slots per window.
+PSKV_HD static inline uint64_t pool_slot(uint64_t b0, uint64_t c) {
+  const uint64_t q = (b0 + c * kPoolChunk) / kPoolChunk;
+  return 2 * q + (b0 > q * kPoolChunk ? 1u : 0u);
+}
+// Partial rows a call of n keys needs at most (every slot index is below it).
+PSKV_HD static inline uint64_t pool_slots(uint64_t n) { return 2 * ((n + kPoolChunk - 1) / kPoolChunk); }
+
+// The last index i of off[0 .. cnt) with off[i] <= x (0 when there is none):
+// the bag that holds key position x when the offsets are well formed.
+PSKV_HD static inline uint64_t pool_bag_of(const uint64_t* off, uint64_t cnt, uint64_t x) {
+  uint64_t lo = 0, hi = cnt;
+  while (hi - lo > 1) {
+    const uint64_t mid = lo + ((hi - lo) >> 1);
+    if (off[mid] <= x)
+      lo = mid;
+    else
+      hi = mid;
+  }
+  return lo;
+}
+
+// A host call's offsets: nbags + 1 values, offsets[0] == 0, non-decreasing,
+// offsets[nbags] == n.  Null when they hold (nbags == 0: nothing to check),
+// else what is wrong, with the first bad bag in *bad.
+static inline const char* pool_offsets_error(const uint64_t* off, uint64_t nbags, uint64_t n, uint64_t* bad) {
+  if (nbags == 0) return nullptr;
+  *bad = 0;
+  if (off[0] != 0) return "offsets[0] must be 0";
+  for (uint64_t b = 0; b < nbags; ++b) {
+    *bad = b;
+    if (off[b + 1] < off[b]) return "offsets must not decrease";
+    if (off[b + 1] > n) return "the bag ends past the n keys";
+  }
+  *bad = nbags - 1;
+  if (off[nbags] != n) return "offsets[nbags] must equal n";
+  return nullptr;
 }
 
 }  // namespace

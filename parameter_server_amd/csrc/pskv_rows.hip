@@ -6,6 +6,8 @@
 //   k_row_accumulate  accumulate Add: one no-return atomic add per element
 //   k_row_grad_losers optimizer step: gradient rows of non-winners summed into gsum
 //   k_row_apply       optimizer step: each key's winner applies SGD / Adagrad / momentum / Adam once
+//   k_row_pooled      pooled pull: out[b] = sum over bag b's keys of weight * row(key)
+//   k_row_pooled_chunks  pooled pull: the chunks of bags longer than kPoolChunk, into partial rows
 //
 // Lane mapping (all of them).  A row is U units long (RowShape); a group of
 // L = min(64, next_pow2(U)) consecutive lanes owns one row at a time, lane l
@@ -429,6 +431,232 @@ void launch_row_apply_kind(int kind, uint32_t grid, const GroupArgs& ga, const D
     k_row_apply<T, 1, V><<<grid, kBlock, 0, st>>>(ga, d, g, s1, s2, owner, epoch, rs, o);
 }
 
+// ----------------------------------------------------------- pooled pulls
+// pskv_get_pooled: a lane group owns a BAG at a time and keeps
+// one accumulator unit per lane: the unit strips of a row wider than the
+// group are the outer loop, the bag's keys the inner one (the keys are re-read
+// from cache), so a 4096-wide row costs the registers of a 64-unit one.  The
+// additions are a dependent chain, the row loads in front of them are not: R
+// rows are loaded before the first is added.  T is the shard's value type
+// (int32 as uint32_t: exact with wrap); the multiply-add is always one fma, in
+// every instantiation, so the unit-16 and the element path return the same bits.
+// Order of the additions, the clamp of device offsets and the chunks of bags
+// longer than kPoolChunk: pskv_plan.h.
+constexpr int kPoolChunkRowsInFlight = 16;  // k_row_pooled_chunks: a chunk is one lane group's chain
+constexpr int kPoolPartsInFlight = 8;       // partial rows of a long bag, read back by k_row_pooled
+
+__device__ __forceinline__ float pool_fma(float w, float p, float a) { return __builtin_fmaf(w, p, a); }
+__device__ __forceinline__ double pool_fma(double w, double p, double a) { return __builtin_fma(w, p, a); }
+__device__ __forceinline__ uint32_t pool_fma(uint32_t w, uint32_t p, uint32_t a) { return a + w * p; }
+
+template <typename T, int V>
+__device__ __forceinline__ OptUnit<T, V> zero_opt_unit() {
+  OptUnit<T, V> r;
+#pragma unroll
+  for (int i = 0; i < V; ++i) r.e[i] = T(0);
+  return r;
+}
+
+template <typename T, int V, bool NT>
+__device__ __forceinline__ void store_pool_unit(T* p, uint64_t unit, const OptUnit<T, V>& r) {
+  if constexpr (V == 1) {
+    store_unit<NT>(p + unit, r.e[0]);
+  } else {
+    typedef T vt __attribute__((ext_vector_type(V)));
+    vt v;
+#pragma unroll
+    for (int i = 0; i < V; ++i) v[i] = r.e[i];
+    store_unit<NT>(reinterpret_cast<vt*>(p + unit * V), v);
+  }
+}
+
+// acc = t when it is the first term (the sum of one term is that term, bit
+// for bit), else acc + t.
+template <typename T, int V>
+__device__ __forceinline__ void pool_add_unit(OptUnit<T, V>& acc, bool& have, const OptUnit<T, V>& t) {
+#pragma unroll
+  for (int i = 0; i < V; ++i) acc.e[i] = have ? acc.e[i] + t.e[i] : t.e[i];
+  have = true;
+}
+
+// Unit u of the sum over key positions [b, e), in key order, R rows in flight.
+// The keys (and weights) of the next R positions are loaded before the rows
+// of this round are added, so a long bag's chain costs one memory latency per
+// round, not a key's and then a row's.
+// oor: some key lay outside the range (it counted as a zero row).
+template <typename T, int V, int R, bool WEIGHTED>
+__device__ __forceinline__ OptUnit<T, V> pool_sum(const uint32_t* __restrict__ keys, const T* __restrict__ weights,
+                                                  uint64_t b, uint64_t e, const T* __restrict__ param,
+                                                  const DenseView& d, uint32_t U, uint32_t u, bool& oor) {
+  OptUnit<T, V> acc = zero_opt_unit<T, V>();
+  bool have = false;
+  uint32_t k[R];
+  T w[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    k[r] = b + r < e ? keys[b + r] : 0u;
+    w[r] = (WEIGHTED && b + r < e) ? weights[b + r] : T(0);
+  }
+  for (uint64_t i = b; i < e; i += R) {
+    OptUnit<T, V> p[R];
+    T wc[R];
+    bool live[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      live[r] = i + r < e;
+      const uint32_t off = k[r] - d.key_begin;
+      const bool in = live[r] && (uint64_t)off < d.range;
+      oor |= live[r] && !in;
+      wc[r] = w[r];
+      p[r] = in ? load_opt_unit<T, V>(param, (uint64_t)off * U + u) : zero_opt_unit<T, V>();
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const uint64_t nx = i + R + r;
+      k[r] = nx < e ? keys[nx] : 0u;
+      w[r] = (WEIGHTED && nx < e) ? weights[nx] : T(0);
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      if (!live[r]) continue;
+#pragma unroll
+      for (int j = 0; j < V; ++j) {
+        if (WEIGHTED)
+          acc.e[j] = have ? pool_fma(wc[r], p[r].e[j], acc.e[j]) : wc[r] * p[r].e[j];
+        else
+          acc.e[j] = have ? acc.e[j] + p[r].e[j] : p[r].e[j];
+      }
+      have = true;
+    }
+  }
+  return acc;
+}
+
+// Work items: the windows of the key array (pskv_plan.h), one lane group per
+// window.  Each sums the at most two long-bag chunks that start in its window
+// into their partial rows.
+template <typename T, int V, bool WEIGHTED>
+__global__ __launch_bounds__(kBlock) void k_row_pooled_chunks(PoolArgs a, DenseView d, uint32_t* err, RowShape rs) {
+  const uint32_t lane = threadIdx.x & (rs.lanes - 1u);
+  const uint32_t grp = threadIdx.x >> rs.lshift;
+  const uint32_t G = (uint32_t)kBlock >> rs.lshift;
+  const uint32_t U = rs.units;
+  const T* __restrict__ param = reinterpret_cast<const T*>(d.param);
+  const T* __restrict__ weights = reinterpret_cast<const T*>(a.weights);
+  T* __restrict__ part = reinterpret_cast<T*>(a.part);
+  const uint64_t nwin = (a.n + kPoolChunk - 1) / kPoolChunk;
+  for (uint64_t q = (uint64_t)blockIdx.x * G + grp; q < nwin; q += (uint64_t)gridDim.x * G) {
+    const uint64_t lo = q * kPoolChunk;
+    const uint64_t hi = (lo + kPoolChunk < a.n ? lo + kPoolChunk : a.n) - 1;
+    const uint64_t ba = pool_bag_of(a.offsets, a.nbags, lo);
+    const uint64_t bb = pool_bag_of(a.offsets, a.nbags, hi);
+    for (int cand = 0; cand < 2; ++cand) {
+      if (cand == 1 && bb == ba) break;
+      const uint64_t bag = cand ? bb : ba;  // < nbags
+      const PoolBag bg = pool_clamp(a.offsets[bag], a.offsets[bag + 1], a.n);
+      const uint64_t c = pool_window_chunk(bg.begin, bg.end, q);
+      if (c == kPoolNone) continue;
+      const uint64_t p0 = bg.begin + c * kPoolChunk;  // in the window, below bg.end <= n
+      const uint64_t p1 = p0 + kPoolChunk < bg.end ? p0 + kPoolChunk : bg.end;
+      const uint64_t slot = pool_slot(bg.begin, c);  // < pool_slots(n), as p0 < n
+      bool oor = false;
+      for (uint32_t u = lane; u < U; u += rs.lanes) {
+        const OptUnit<T, V> acc =
+            pool_sum<T, V, kPoolChunkRowsInFlight, WEIGHTED>(a.keys, weights, p0, p1, param, d, U, u, oor);
+        store_opt_unit<T, V>(part, slot * U + u, acc);
+      }
+      if (oor && lane == 0) atomicOr(err, kErrRowOutOfRange);
+    }
+  }
+}
+
+// Work items: bags, in virtual workgroups of kPoolBagsPerWg, grid-stride; group
+// g of the workgroup's G takes the workgroup's bags g, g + G, ...  A bag of at
+// most kPoolChunk keys is summed here; a longer one adds up its chunks'
+// partial rows (k_row_pooled_chunks ran first) in chunk order.
+template <typename T, int V, bool NT, bool WEIGHTED>
+__global__ __launch_bounds__(kBlock) void k_row_pooled(PoolArgs a, DenseView d, uint32_t* err, RowShape rs) {
+  const uint32_t lane = threadIdx.x & (rs.lanes - 1u);
+  const uint32_t grp = threadIdx.x >> rs.lshift;
+  const uint32_t G = (uint32_t)kBlock >> rs.lshift;
+  const uint32_t U = rs.units;
+  const T* __restrict__ param = reinterpret_cast<const T*>(d.param);
+  const T* __restrict__ weights = reinterpret_cast<const T*>(a.weights);
+  const T* __restrict__ part = reinterpret_cast<const T*>(a.part);
+  T* __restrict__ out = reinterpret_cast<T*>(a.out);
+  const uint64_t nvwg = (a.nbags + kPoolBagsPerWg - 1) / kPoolBagsPerWg;
+  for (uint64_t wg = blockIdx.x; wg < nvwg; wg += gridDim.x) {
+    for (uint32_t g = grp; g < kPoolBagsPerWg; g += G) {
+      const uint64_t bag = wg * kPoolBagsPerWg + g;
+      if (bag >= a.nbags) break;
+      const PoolBag bg = pool_clamp(a.offsets[bag], a.offsets[bag + 1], a.n);
+      const uint64_t m = bg.end - bg.begin;
+      bool oor = false;
+      for (uint32_t u = lane; u < U; u += rs.lanes) {
+        OptUnit<T, V> acc;
+        if (m > kPoolChunk) {
+          const uint64_t nc = pool_chunks(m);
+          bool have = false;
+          acc = zero_opt_unit<T, V>();
+          for (uint64_t c = 0; c < nc; c += kPoolPartsInFlight) {
+            OptUnit<T, V> s[kPoolPartsInFlight];
+#pragma unroll
+            for (int r = 0; r < kPoolPartsInFlight; ++r)
+              if (c + r < nc) s[r] = load_opt_unit<T, V>(part, pool_slot(bg.begin, c + r) * U + u);
+#pragma unroll
+            for (int r = 0; r < kPoolPartsInFlight; ++r)
+              if (c + r < nc) pool_add_unit<T, V>(acc, have, s[r]);
+          }
+        } else {
+          acc = pool_sum<T, V, kRowsInFlight, WEIGHTED>(a.keys, weights, bg.begin, bg.end, param, d, U, u, oor);
+        }
+        store_pool_unit<T, V, NT>(out, bag * U + u, acc);
+      }
+      if (oor && lane == 0) atomicOr(err, kErrRowOutOfRange);
+    }
+  }
+}
+
+// f(T()) with T the arithmetic type of a pooled pull (dtype 0: int32 summed as
+// uint32_t, 1: float, 2: double), then the launch's error.
+template <typename F>
+hipError_t with_pool_type(int dtype, F&& f) {
+  if (dtype == 0)
+    f(uint32_t());
+  else if (dtype == 1)
+    f(float());
+  else if (dtype == 2)
+    f(double());
+  else
+    return hipErrorInvalidValue;
+  return hipGetLastError();
+}
+
+template <typename T, int V>
+void launch_row_pooled_v(uint32_t grid, bool nt, const PoolArgs& a, const DenseView& d, uint32_t* err,
+                         const RowShape& rs, hipStream_t st) {
+  if (a.weights) {
+    if (nt)
+      k_row_pooled<T, V, true, true><<<grid, kBlock, 0, st>>>(a, d, err, rs);
+    else
+      k_row_pooled<T, V, false, true><<<grid, kBlock, 0, st>>>(a, d, err, rs);
+  } else {
+    if (nt)
+      k_row_pooled<T, V, true, false><<<grid, kBlock, 0, st>>>(a, d, err, rs);
+    else
+      k_row_pooled<T, V, false, false><<<grid, kBlock, 0, st>>>(a, d, err, rs);
+  }
+}
+
+template <typename T, int V>
+void launch_row_pooled_chunks_v(uint32_t grid, const PoolArgs& a, const DenseView& d, uint32_t* err,
+                                const RowShape& rs, hipStream_t st) {
+  if (a.weights)
+    k_row_pooled_chunks<T, V, true><<<grid, kBlock, 0, st>>>(a, d, err, rs);
+  else
+    k_row_pooled_chunks<T, V, false><<<grid, kBlock, 0, st>>>(a, d, err, rs);
+}
+
 }  // namespace
 
 RowShape row_shape(uint32_t width, int vb, bool unit16) {
@@ -517,6 +745,38 @@ hipError_t launch_fill(int dtype, void* p, uint64_t n, double v, hipStream_t st)
   return with_float_type(dtype, [&](auto z) {
     using T = decltype(z);
     k_fill<T><<<grid, kBlock, 0, st>>>(static_cast<T*>(p), n, (T)v);
+  });
+}
+
+hipError_t launch_row_pooled_chunks(int dtype, const PoolArgs& a, const DenseView& d, const Ovf& o,
+                                    const RowShape& rs, hipStream_t st) {
+  if (a.nbags == 0 || a.n <= kPoolChunk) return hipSuccess;  // no bag can be long
+  if (!a.part) return hipErrorInvalidValue;
+  const uint64_t G = (uint64_t)kBlock >> rs.lshift;
+  const uint64_t nwg = ((a.n + kPoolChunk - 1) / kPoolChunk + G - 1) / G;
+  const uint32_t grid = row_grid((uint32_t)std::min<uint64_t>(nwg, 4096));
+  uint32_t* err = &o.c->stat[1];
+  return with_pool_type(dtype, [&](auto z) {
+    using T = decltype(z);
+    if (rs.unit_bytes == 16)
+      launch_row_pooled_chunks_v<T, 16 / sizeof(T)>(grid, a, d, err, rs, st);
+    else
+      launch_row_pooled_chunks_v<T, 1>(grid, a, d, err, rs, st);
+  });
+}
+
+hipError_t launch_row_pooled(int dtype, bool nt, const PoolArgs& a, const DenseView& d, const Ovf& o,
+                             const RowShape& rs, hipStream_t st) {
+  if (a.nbags == 0) return hipSuccess;
+  const uint64_t nwg = (a.nbags + kPoolBagsPerWg - 1) / kPoolBagsPerWg;
+  const uint32_t grid = row_grid((uint32_t)std::min<uint64_t>(nwg, 4096));
+  uint32_t* err = &o.c->stat[1];
+  return with_pool_type(dtype, [&](auto z) {
+    using T = decltype(z);
+    if (rs.unit_bytes == 16)
+      launch_row_pooled_v<T, 16 / sizeof(T)>(grid, nt, a, d, err, rs, st);
+    else
+      launch_row_pooled_v<T, 1>(grid, nt, a, d, err, rs, st);
   });
 }
 

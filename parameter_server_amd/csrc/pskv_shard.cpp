@@ -95,10 +95,13 @@ struct TimedLaunch {
 };
 
 // Timing slots: the kernels of enum pskv_kernel, then one slot for a whole
-// optimizer step (pskv_apply_time; PSKV_TIME_APPLY is its mask bit).
+// optimizer step (pskv_apply_time; PSKV_TIME_APPLY is its mask bit) and one for
+// a whole pooled pull (pskv_pooled_time; PSKV_TIME_POOLED).
 constexpr int kTimeApply = PSKV_K_COUNT;
-constexpr int kTimeSlots = PSKV_K_COUNT + 1;
+constexpr int kTimePooled = PSKV_K_COUNT + 1;
+constexpr int kTimeSlots = PSKV_K_COUNT + 2;
 static_assert(PSKV_TIME_APPLY == (1u << kTimeApply), "the apply slot follows the kernel ids");
+static_assert(PSKV_TIME_POOLED == (1u << kTimePooled), "the pooled slot follows the apply slot");
 
 // ---------------------------------------------------------------- host pool
 // A small persistent pool for the host side of the path: copying zmq-buffer
@@ -267,6 +270,10 @@ struct pskv_shard {
   size_t rb_loff_bytes = 0;
   void* rb_ent = nullptr;
   size_t rb_ent_bytes = 0;
+  // pooled pulls: the partial rows of long bags' chunks (grown on demand, as
+  // the K5 scratch: a steady workload allocates nothing)
+  void* pool_part = nullptr;
+  size_t pool_part_bytes = 0;
   int general_path = 1;  // PSKV_GENERAL: stamps = 0 (K4 always), auto = 1, radix = 2 (K5 always)
   // tuning knobs (environment, read at creation): PSKV_TILE_SHIFT, PSKV_TILE_GRID
   uint32_t tune_tile_shift = 0;
@@ -449,7 +456,8 @@ const char* const kKernelNames[kTimeSlots] = {
     "k_dense_check (K6)",         "k_acc_dense (K7)",              "k_inline_add (K8)",
     "k_inline_get (K8)",          "k_replay (K4r)",                "k_row_gather (row Get)",
     "k_general_mark + k_row_commit (row assign Add)",              "k_row_accumulate (row accumulate Add)",
-    "k_general_mark + k_row_grad_losers + k_row_apply (optimizer step)"};
+    "k_general_mark + k_row_grad_losers + k_row_apply (optimizer step)",
+    "k_row_pooled_chunks + k_row_pooled (pooled pull)"};
 
 std::string wait_report(const pskv_shard* s, const char* what, const void* handle, double ms) {
   char buf[384];
@@ -1612,11 +1620,11 @@ struct RowCall {
   const std::vector<pskv_batch>& views() const { return host ? dv : v; }  // what the kernels read
 };
 
-// A host call's keys are checked before anything is queued (nothing is
-// applied); its pieces are then on their way to the device staging, and
-// `hold`, the caller's, is armed.
-int rows_front(pskv_shard* s, const std::vector<pskv_batch>& in, int flags, const RowFront& f, HstageHold& hold,
-               RowCall* c) {
+// The front's checks, without the staging (a pooled pull stages its own
+// layout): the pieces are in c->v (empty: the call holds no key and nothing
+// further was done), the call is counted, the device is selected, the server
+// stopped and a host call's keys are inside the range.
+int rows_front_checks(pskv_shard* s, const std::vector<pskv_batch>& in, int flags, const RowFront& f, RowCall* c) {
   for (auto& b : in) {
     if (b.n == 0) continue;
     if (!b.keys || !b.vals) return fail(PSKV_EINVAL, std::string(f.what) + ": null keys/vals with n > 0");
@@ -1632,6 +1640,16 @@ int rows_front(pskv_shard* s, const std::vector<pskv_batch>& in, int flags, cons
     if (const uint32_t* k = first_key_outside(c->v, s->key_begin, s->range))
       return fail(PSKV_EINVAL, std::string(f.what) + ": " + f.refusal + " " + std::to_string(*k) +
                                    " is outside [key_begin, key_end); " + f.why + " (nothing was applied)");
+  return PSKV_OK;
+}
+
+// A host call's keys are checked before anything is queued (nothing is
+// applied); its pieces are then on their way to the device staging, and
+// `hold`, the caller's, is armed.
+int rows_front(pskv_shard* s, const std::vector<pskv_batch>& in, int flags, const RowFront& f, HstageHold& hold,
+               RowCall* c) {
+  if (int rc = rows_front_checks(s, in, flags, f, c)) return rc;
+  if (c->v.empty() || (flags & PSKV_DEVICE)) return PSKV_OK;
   c->host = true;
   c->lay = stage_layout(c->v, row_bytes(s), StageOrder::kKeysFirst);
   return stage_keys_first(s, c->v, c->lay, row_bytes(s), f.with_values, hold, &c->dv);
@@ -1716,6 +1734,84 @@ int rows_get_from(pskv_shard* s, const std::vector<pskv_batch>& in, int flags, c
 
 int rows_get(pskv_shard* s, const std::vector<pskv_batch>& in, int flags) {
   return rows_get_from(s, in, flags, s->dview(), "pskv_get", &s->n_get);
+}
+
+// ------------------------------------------------------------ pooled pulls
+// pskv_get_pooled (pskv.h "Pooled pulls"), at any width, 1
+// included.  One or two launches, timed as one operation (kTimePooled):
+//   k_row_pooled_chunks   only when n > kPoolChunk (else no bag can be long):
+//                         the chunks of long bags into their partial rows
+//   k_row_pooled          every bag: its sum, or the sum of its partial rows
+// The offsets stay where the caller has them, so a device call's launches do
+// not depend on them; the kernels clamp every bag (pool_clamp).
+struct PoolCall {
+  const uint32_t* keys;
+  uint64_t n;
+  const void* weights;  // or null
+  const uint64_t* offsets;
+  uint64_t nbags;
+  void* out;
+};
+
+int pooled_device(pskv_shard* s, const PoolCall& c) {
+  PoolArgs a{c.keys, c.weights, c.offsets, c.n, c.nbags, c.out, nullptr};
+  if (c.n > kPoolChunk) {
+    if (int rc = ensure_scratch(s, &s->pool_part, &s->pool_part_bytes, pool_slots(c.n) * row_bytes(s))) return rc;
+    a.part = s->pool_part;
+  }
+  const bool unit16 = row_bytes(s) % 16 == 0 && aligned16(s->dense) && aligned16(c.out) && aligned16(a.part);
+  const RowShape rs = row_shape(s->width, s->vb, unit16);
+  LaunchTimer t(s, kTimePooled, c.n);
+  PSKV_HIP(launch_row_pooled_chunks(s->dtype, a, s->dview(), s->ovf, rs, s->stream));
+  PSKV_HIP(launch_row_pooled(s->dtype, s->tune_nt, a, s->dview(), s->ovf, rs, s->stream));
+  t.done();
+  return PSKV_OK;
+}
+
+// The arguments hold (pskv_get_pooled checked them, a host call's offsets included).
+int pooled_impl(pskv_shard* s, const PoolCall& call, int flags) {
+  ++s->n_get;
+  if (call.nbags == 0) return PSKV_OK;
+  // rows_front's checks on the keys; `out` stands in for the values, which the
+  // checks only want non-null
+  RowCall c;
+  const std::vector<pskv_batch> in{pskv_batch{call.keys, call.out, call.n}};
+  int rc = rows_front_checks(s, in, flags,
+                             RowFront{"pskv_get_pooled", nullptr, /*stop_server=*/true, "key",
+                                      "a pooled pull reads the dense array only, not the overflow table; out is untouched",
+                                      /*with_values=*/false},
+                             &c);
+  if (rc) return rc;
+  if (c.v.empty()) {  // no key, but bags: rows of zeros
+    if ((rc = use_device(s)) || (rc = srv_stop(s))) return rc;
+  }
+  if (flags & PSKV_DEVICE) return pooled_device(s, call);
+  // host buffers: keys, weights, offsets into the pinned staging and on to the
+  // device staging, 16-byte aligned, the pooled rows behind them
+  const size_t rb = row_bytes(s);
+  const size_t wo = round16(call.n * 4);
+  const size_t oo = wo + (call.weights ? round16(call.n * (size_t)s->vb) : 0);
+  const size_t ro = oo + round16((call.nbags + 1) * sizeof(uint64_t));
+  const size_t total = ro + round16(call.nbags * rb);
+  HstageHold hold(s);
+  if ((rc = ensure_hstage(s, total)) || (rc = ensure_dstage(s, total))) return rc;
+  char* h = static_cast<char*>(s->hstage);
+  char* d = static_cast<char*>(s->dstage);
+  std::vector<Piece> pieces;
+  add_pieces(pieces, call.keys, h, call.n * 4, -1);
+  if (call.weights) add_pieces(pieces, call.weights, h + wo, call.n * (size_t)s->vb, -1);
+  add_pieces(pieces, call.offsets, h + oo, (call.nbags + 1) * sizeof(uint64_t), -1);
+  if ((rc = pipelined_h2d(s, pieces, h, d, hold))) return rc;
+  const PoolCall dc{reinterpret_cast<const uint32_t*>(d), call.n, call.weights ? d + wo : nullptr,
+                    reinterpret_cast<const uint64_t*>(d + oo), call.nbags, d + ro};
+  if ((rc = pooled_device(s, dc))) return rc;
+  PSKV_HIP(hipMemcpyAsync(h + ro, d + ro, call.nbags * rb, hipMemcpyDeviceToHost, s->stream));
+  if ((rc = wait_stream(s, s->stream, "shard stream (pooled pull to host)"))) return rc;
+  hold.dismiss();
+  std::vector<Piece> back;
+  add_pieces(back, h + ro, static_cast<char*>(call.out), call.nbags * rb, -1);
+  run_copies(s, back, 0, back.size());
+  return PSKV_OK;
 }
 
 // -------------------------------------------------------- optimizer steps
@@ -2526,6 +2622,7 @@ int pskv_shard_destroy(pskv_shard* s) {
   if (s->dstage) (void)hipFree(s->dstage);
   if (s->rb_loff) (void)hipFree(s->rb_loff);
   if (s->rb_ent) (void)hipFree(s->rb_ent);
+  if (s->pool_part) (void)hipFree(s->pool_part);
   if (s->hstage) (void)hipHostFree(s->hstage);
   if (s->ireply) (void)hipHostFree(s->ireply);
   if (s->stat_host) (void)hipHostFree(s->stat_host);
@@ -2578,6 +2675,24 @@ int pskv_get_grouped(pskv_shard* s, const pskv_batch* batches, uint64_t nb, int 
   if (nb && !batches) return fail(PSKV_EINVAL, "pskv_get_grouped: null batches");
   if (bad_flags(flags)) return fail(PSKV_EINVAL, "pskv_get_grouped: unknown flags");
   return get_impl(s, std::vector<pskv_batch>(batches, batches + nb), flags);
+}
+
+// Flags, pointers and a host call's offsets are checked before the handle is
+// looked at (as pskv_shard_set_optimizer checks its configuration).
+int pskv_get_pooled(pskv_shard* s, const uint32_t* keys, uint64_t n, const void* weights, const uint64_t* offsets,
+                    uint64_t nbags, void* out, int flags) {
+  if (bad_flags(flags)) return fail(PSKV_EINVAL, "pskv_get_pooled: unknown flags");
+  if (n && !keys) return fail(PSKV_EINVAL, "pskv_get_pooled: null keys with n > 0");
+  if (nbags && !offsets) return fail(PSKV_EINVAL, "pskv_get_pooled: null offsets with nbags > 0");
+  if (nbags && !out) return fail(PSKV_EINVAL, "pskv_get_pooled: null out with nbags > 0");
+  if (!(flags & PSKV_DEVICE)) {
+    uint64_t bad = 0;
+    if (const char* why = pool_offsets_error(offsets, nbags, n, &bad))
+      return fail(PSKV_EINVAL, "pskv_get_pooled: offsets: bag " + std::to_string(bad) + ": " + why + " (n = " +
+                                   std::to_string(n) + ", nbags = " + std::to_string(nbags) + ")");
+  }
+  if (!s) return fail(PSKV_EINVAL, "pskv_get_pooled: null shard");
+  return pooled_impl(s, PoolCall{keys, n, weights, offsets, nbags, out}, flags);
 }
 
 int pskv_shard_set_optimizer(pskv_shard* s, const pskv_optimizer* cfg) {
@@ -2694,6 +2809,18 @@ int pskv_apply_time(pskv_shard* s, uint64_t* launches, double* total_ms, uint64_
   return PSKV_OK;
 }
 
+int pskv_pooled_time(pskv_shard* s, uint64_t* launches, double* total_ms, uint64_t* elements) {
+  if (!s) return fail(PSKV_EINVAL, "pskv_pooled_time: null shard");
+  int rc = use_device(s);
+  if (rc) return rc;
+  rc = drain_timing(s);
+  if (rc) return rc;
+  if (launches) *launches = s->t_launches[kTimePooled];
+  if (total_ms) *total_ms = s->t_ms[kTimePooled];
+  if (elements) *elements = s->t_elems[kTimePooled];
+  return PSKV_OK;
+}
+
 int pskv_sync(pskv_shard* s) {
   if (!s) return fail(PSKV_EINVAL, "pskv_sync: null shard");
   int rc = use_device(s);
@@ -2709,9 +2836,9 @@ int pskv_sync(pskv_shard* s) {
                 "request was not answered within SYNC_TIMEOUT_MS, or its allocation failed)");
   if (err & kErrRowOutOfRange)
     return fail(PSKV_ESTATE,
-                "row shard: a device Add or optimizer step held out-of-range keys; their rows were dropped (a row "
-                "shard, and an optimizer step at any width, stores no key outside [key_begin, key_end); pskv_clear "
-                "resets this)");
+                "row shard: a device Add, optimizer step or pooled pull held out-of-range keys; their rows were dropped "
+                "(a pooled pull read them as zeros) (a row shard, and an optimizer step or a pooled pull at any "
+                "width, holds no key outside [key_begin, key_end); pskv_clear resets this)");
   if (2 * (uint64_t)cnt > s->ocap) return grow_overflow(s, cnt);
   return PSKV_OK;
 }

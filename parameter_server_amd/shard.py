@@ -150,6 +150,58 @@ class Shard:
         check(lib.pskv_get(self._h, k.ctypes.data, k.size, res.ctypes.data, flags))
         return res
 
+    def get_pooled(self, keys, offsets, weights=None, out=None):
+        """One pooled row per bag (pskv_get_pooled): bag b is keys[offsets[b] :
+        offsets[b+1]], its row sum_i weights[i] * row(keys[i]) (weights None:
+        every weight one).  numpy inputs -> host path, returns a numpy array;
+        torch tensors -> device path (offsets an int64 tensor), stream-ordered.
+        Returns (nbags, width), or (nbags,) at width 1."""
+        if _is_torch(keys):
+            import torch
+
+            if offsets.dtype != torch.int64 or offsets.numel() < 1:
+                raise ValueError("get_pooled: device offsets must be an int64 tensor of nbags + 1 values")
+            nbags = offsets.numel() - 1
+            tdt = _torch_dtype(self.dtype)
+            ts = [keys, offsets]
+            if weights is not None:
+                if weights.dtype != tdt or weights.numel() != keys.numel():
+                    raise ValueError("get_pooled: weights must hold one value of the shard's dtype per key")
+                ts.append(weights)
+            if out is None:
+                out = torch.empty((nbags, self.width) if self.width > 1 else nbags, dtype=tdt, device=keys.device)
+            elif out.dtype != tdt or out.numel() != nbags * self.width:
+                raise ValueError("get_pooled: out must hold nbags * width values of the shard's dtype")
+            self._check_dev(*ts, out)
+            check(lib.pskv_get_pooled(self._h, keys.data_ptr(), keys.numel(),
+                                      weights.data_ptr() if weights is not None else None, offsets.data_ptr(),
+                                      nbags, out.data_ptr(), _lib.PSKV_DEVICE))
+            return out
+        k = self._host_keys(keys)
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        if off.size < 1:
+            raise ValueError("get_pooled: offsets must hold nbags + 1 values")
+        nbags = off.size - 1
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=self.dtype)
+            if w.size != k.size:
+                raise ValueError(f"get_pooled: {w.size} weights for {k.size} keys")
+        if out is None:
+            out = np.empty((nbags, self.width) if self.width > 1 else nbags, dtype=self.dtype)
+        elif not (isinstance(out, np.ndarray) and out.dtype == self.dtype and out.flags.c_contiguous
+                  and out.size == nbags * self.width):
+            raise ValueError("get_pooled: out must be a C-contiguous array of nbags * width values")
+        check(lib.pskv_get_pooled(self._h, k.ctypes.data, k.size, w.ctypes.data if w is not None else None,
+                                  off.ctypes.data, nbags, out.ctypes.data, _lib.PSKV_HOST))
+        return out
+
+    def pooled_time(self):
+        """Pooled pulls timed as one operation each (pskv_pooled_time)."""
+        n, ms, el = ctypes.c_uint64(), ctypes.c_double(), ctypes.c_uint64()
+        check(lib.pskv_pooled_time(self._h, ctypes.byref(n), ctypes.byref(ms), ctypes.byref(el)))
+        return {"launches": n.value, "total_ms": ms.value, "elements": el.value}
+
     def prepare(self, batches, is_get: bool = False) -> "BatchSet":
         """Validate and pack a batch list once, for repeated grouped calls."""
         arr, keep, flags = self._batch_array(batches, is_get=is_get)
