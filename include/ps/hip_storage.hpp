@@ -174,6 +174,23 @@ class HipStorage : public AbstractStorage {
     return third_party::SArray<char>(reply_vals);
   }
 
+  // One optimizer step from one gradient row per bag (pskv_apply_pooled), the
+  // bags as SubGetPooled's: the gradient row of typed_keys[i] is weights[i] *
+  // bag_grads[b], b the bag that holds position i; bag_grads holds
+  // (offsets.size() - 1) * width values.  Not part of AbstractStorage.
+  void SubApplyPooled(const third_party::SArray<Key>& typed_keys, const third_party::SArray<Val>* weights,
+                      const third_party::SArray<uint64_t>& offsets, const third_party::SArray<Val>& bag_grads) {
+    if (offsets.size() == 0 || (weights && weights->size() != typed_keys.size()) ||
+        bag_grads.size() != (offsets.size() - 1) * width_) {
+      std::fprintf(stderr, "Check failed: offsets.size() >= 1, weights.size() == typed_keys.size() and "
+                           "bag_grads.size() == (offsets.size() - 1) * width\n");
+      std::abort();
+    }
+    pskv_check(pskv_apply_pooled(shard_, typed_keys.data(), typed_keys.size(), weights ? weights->data() : nullptr,
+                                 offsets.data(), offsets.size() - 1, bag_grads.data(), PSKV_HOST | PSKV_HOST_FRAME),
+               "pskv_apply_pooled");
+  }
+
   // The reference's FinishIter is a no-op (map_storage.hpp:47); here it is the
   // point where deferred device errors surface and the overflow table, which
   // grows on the device as keys arrive, is trimmed and its old arrays freed.

@@ -167,7 +167,59 @@
  *     synchronous, a device call stream-ordered, as pskv_get; with the
  *     resident request server (SERVE = 1) the call first ends the server;
  *   - not provided: a grouped form, mean or max pooling (weights give the
- *     mean), the backward pass, overflow keys.
+ *     mean), overflow keys.  The backward pass is the pooled push below.
+ *
+ * Pooled pushes (pskv_apply_pooled): the backward half of a
+ * pooled pull.  The caller sends one gradient row per BAG (the reference's
+ * err_s, app/logistic_regression.cpp:451-456; an embedding bag's output
+ * gradient) and the per-key weights of the pull; the shard forms each key
+ * position's gradient row itself,
+ *     rows[i] = weights[i] * bag_grads[bag(i)],   offsets[bag(i)] <= i < offsets[bag(i)+1]
+ * in registers inside the optimizer step, so the push holds nbags * W values,
+ * not n * W.
+ *   - one call is one step, the step pskv_apply(keys, rows, n) would make
+ *     ("Optimizer steps", "Momentum and Adam"): the rows of all occurrences of
+ *     a key are summed in unspecified order, the shard's rule is applied once
+ *     per distinct key, every other key keeps p and state bit for bit.  A key
+ *     whose weight or whose bag's row is zero is still a key of the call and
+ *     takes a step with that zero contribution (weight decay, momentum and
+ *     Adam decay act on it), as a zero gradient row does in pskv_apply;
+ *   - arithmetic in the shard's type T: each product is ONE multiplication
+ *     rounded to T (never contracted with the addition behind it);
+ *     weights == NULL: the term is the bag's row itself, bit for bit; the rest
+ *     is pskv_apply's expression.  When every key of the call is distinct the
+ *     result (p, every state slot) equals pskv_apply of the rows
+ *     fl_T(weights[i] * bag_grads[...]) bit for bit; with duplicated keys the
+ *     sums differ from it by their order only;
+ *   - float shards only (PSKV_I32: PSKV_EINVAL), any width (1 included),
+ *     either creation mode; a shard without an optimizer: PSKV_EINVAL;
+ *   - the step counter follows pskv_apply's rules: a call that queues work
+ *     advances it by one; n == 0 (whatever nbags) or nbags == 0 does nothing,
+ *     returns PSKV_OK and does not advance it; a refused call does not; a
+ *     device call that drops out-of-range keys does;
+ *   - flags, null keys / offsets / bag_grads with a non-zero count, n > 2^31
+ *     (a pooled push is one launch group: PSKV_EINVAL) and a host call's
+ *     offsets (as a pooled pull's) are checked before the handle is looked
+ *     at: PSKV_EINVAL naming the first bad bag, also for a null shard;
+ *   - keys outside [key_begin, key_end) follow pskv_apply's rule at every
+ *     width: a host call returns PSKV_EINVAL naming the first and applies
+ *     nothing; a device call applies the in-range keys, drops the others and
+ *     the next pskv_sync returns PSKV_ESTATE (pskv_clear resets it);
+ *   - device offsets cannot be read by the library: the kernels take for
+ *     position i a bag index that is always below nbags, so malformed device
+ *     offsets give unspecified values to the keys of the call, never an access
+ *     outside keys, weights, offsets[0..nbags], bag_grads[0 .. nbags*W), and
+ *     never a change to a key that is not in `keys`;
+ *   - PSKV_HOST_FRAME buffers are treated as plain host memory; a host call
+ *     returns as a host pskv_apply does (once its copies are queued), a device
+ *     call is stream-ordered; with the resident request server (SERVE = 1)
+ *     the call first ends the server;
+ *   - timing: one operation of pskv_apply_time's slot (PSKV_TIME_APPLY), with
+ *     elements = n;
+ *   - not provided: a grouped form, an accumulate-mode pskv_add counterpart,
+ *     int32, slicing inside KVClientTable (a worker of a range-partitioned
+ *     table sends each server its part of every bag with the bag's full
+ *     gradient row).
  *
  * Threading: one shard handle is used by one host thread at a time (the
  * reference calls a storage only from its ServerThread, server_thread.cpp:20-50);
@@ -316,6 +368,15 @@ int pskv_get(pskv_shard* s, const uint32_t* keys, uint64_t n, void* out, int fla
  * Synchronous for host buffers, stream-ordered for PSKV_DEVICE ones. */
 int pskv_get_pooled(pskv_shard* s, const uint32_t* keys, uint64_t n, const void* weights,
                     const uint64_t* offsets, uint64_t nbags, void* out, int flags);
+
+/* Pooled push: one optimizer step (semantics: "Optimizer steps", "Momentum and Adam",
+ * "Pooled pushes") whose gradient row for key position i is
+ * weights[i] * bag_grads[bag(i)], bag(i) the bag b with
+ * offsets[b] <= i < offsets[b+1].  keys: n keys, bag after bag; weights: n values of the shard's
+ * type or NULL (every weight one, nothing is multiplied); offsets: nbags + 1 values;
+ * bag_grads: nbags * W values, row b at element b * W. */
+int pskv_apply_pooled(pskv_shard* s, const uint32_t* keys, uint64_t n, const void* weights,
+                      const uint64_t* offsets, uint64_t nbags, const void* bag_grads, int flags);
 
 /* Grouped forms: nb batches in one call, semantically identical to nb
  * consecutive pskv_add / pskv_get calls in array order, executed in a small,

@@ -77,6 +77,7 @@ EXPORTED = [
     "pskv_shard_set_optimizer_ex", "pskv_shard_get_optimizer_ex", "pskv_get_state_slot", "pskv_put_state",
     "pskv_get_step", "pskv_set_step",
     "pskv_get_pooled", "pskv_pooled_time",
+    "pskv_apply_pooled",
 ]
 
 
@@ -167,6 +168,7 @@ def _load():
         "pskv_set_step": ([vp, u64], i32),
         "pskv_get_pooled": ([vp, vp, u64, vp, vp, u64, vp, i32], i32),
         "pskv_pooled_time": ([vp, ctypes.POINTER(u64), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(u64)], i32),
+        "pskv_apply_pooled": ([vp, vp, u64, vp, vp, u64, vp, i32], i32),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)

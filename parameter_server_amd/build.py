@@ -26,6 +26,7 @@ CPP_TESTS = {  # program -> (source in tests/cpp, links the oracle checker)
     "hip_storage_opt_test": ("hip_storage_opt_test.cpp", False),
     "hip_storage_opt2_test": ("hip_storage_opt2_test.cpp", False),
     "hip_storage_pooled_test": ("hip_storage_pooled_test.cpp", False),
+    "hip_storage_pooled_push_test": ("hip_storage_pooled_push_test.cpp", False),
 }
 ORACLE_DIR = os.path.join(ROOT, "oracle")
 BIN_DIR = os.path.join(PKG, "bin")

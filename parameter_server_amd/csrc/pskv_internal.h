@@ -290,6 +290,28 @@ hipError_t launch_row_grad_losers(int dtype, const GroupArgs& ga, uint32_t nwg, 
 hipError_t launch_row_apply(int dtype, int kind, const GroupArgs& ga, uint32_t nwg, const DenseView& d, void* gsum,
                             void* const state[2], const unsigned long long* owner, uint32_t epoch,
                             const RowShape& rs, const OptArgs<double>& hy, hipStream_t st);
+// Pooled push (pskv_apply_pooled): the two launches above with
+// the gradient row of key position i formed in registers,
+// weights[i] * bag_grads[bag(i)] (one multiplication rounded to the value
+// type; weights null: the bag's row itself).  One batch of n <= kMaxPiece
+// keys behind launch_general_mark over {keys, n} with the same epoch; nbags
+// >= 1.  The bag of a position: pskv_plan.h (pool_bag_span, pool_bags_in);
+// whatever the offsets hold it is below nbags.
+struct PoolPushArgs {
+  const uint32_t* keys;     // n
+  const void* weights;      // n values, or null
+  const uint64_t* offsets;  // nbags + 1 (the kernels read [0, nbags))
+  uint64_t n, nbags;
+  const void* bag_grads;    // nbags rows
+};
+// rs built with unit16 = false.
+hipError_t launch_row_pooled_grad_losers(int dtype, const PoolPushArgs& a, const DenseView& d, void* gsum,
+                                         const unsigned long long* owner, const Ovf& o, uint32_t epoch,
+                                         const RowShape& rs, hipStream_t st);
+// unit16 also wants bag_grads 16-byte aligned.
+hipError_t launch_row_pooled_apply(int dtype, int kind, const PoolPushArgs& a, const DenseView& d, void* gsum,
+                                   void* const state[2], const unsigned long long* owner, uint32_t epoch,
+                                   const RowShape& rs, const OptArgs<double>& hy, hipStream_t st);
 // p[0..n) = v (float or double by dtype): the accumulator's initial value.
 hipError_t launch_fill(int dtype, void* p, uint64_t n, double v, hipStream_t st);
 

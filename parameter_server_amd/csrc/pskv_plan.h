@@ -339,6 +339,53 @@ PSKV_HD static inline uint64_t pool_bag_of(const uint64_t* off, uint64_t cnt, ui
   return lo;
 }
 
+// Pooled pushes (pskv_apply_pooled) work position-major: the
+// kernels need the bag of a key position, not the positions of a bag.  A
+// virtual workgroup of consecutive positions [first, last] finds the bags of
+// its two ends once (pool_bag_span); every position in between then searches
+// only off[lo .. hi] by pool_bag_of's rule (pool_bags_in), and not at all when
+// one bag covers the workgroup (lo == hi).  With well-formed offsets the result
+// is pool_bag_of's, the true bag, empty bags skipped (pool_bag_of does not
+// decrease in x, so lo <= pool_bag_of(x) <= hi); with any offsets it lies in
+// [lo, hi], so below nbags (nbags >= 1).
+struct PoolSpan {
+  uint64_t lo, hi;  // lo <= hi < nbags
+};
+PSKV_HD static inline PoolSpan pool_bag_span(const uint64_t* off, uint64_t nbags, uint64_t first, uint64_t last) {
+  PoolSpan sp;
+  sp.lo = pool_bag_of(off, nbags, first);
+  sp.hi = pool_bag_of(off, nbags, last);
+  if (sp.hi < sp.lo) sp.hi = sp.lo;  // (malformed offsets only)
+  return sp;
+}
+// bag[r] = the last index i of [sp.lo, sp.hi] with off[i] <= x[r] (sp.lo when
+// there is none), for every r with want[r]; the others get sp.lo unsearched.
+// The R searches are independent and advance in step, so their loads are
+// issued together and a round costs one memory latency, not R.
+template <int R>
+PSKV_HD static inline void pool_bags_in(const uint64_t* off, const PoolSpan& sp, const uint64_t (&x)[R],
+                                        const bool (&want)[R], uint64_t (&bag)[R]) {
+  uint64_t hi[R];
+  bool more = false;
+  for (int r = 0; r < R; ++r) {
+    bag[r] = sp.lo;
+    hi[r] = want[r] ? sp.hi + 1 : sp.lo + 1;
+    more |= hi[r] - bag[r] > 1;
+  }
+  while (more) {
+    more = false;
+    for (int r = 0; r < R; ++r) {
+      if (hi[r] - bag[r] <= 1) continue;
+      const uint64_t mid = bag[r] + ((hi[r] - bag[r]) >> 1);
+      if (off[mid] <= x[r])
+        bag[r] = mid;
+      else
+        hi[r] = mid;
+      more |= hi[r] - bag[r] > 1;
+    }
+  }
+}
+
 // A host call's offsets: nbags + 1 values, offsets[0] == 0, non-decreasing,
 // offsets[nbags] == n.  Null when they hold (nbags == 0: nothing to check),
 // else what is wrong, with the first bad bag in *bad.

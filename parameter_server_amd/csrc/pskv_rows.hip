@@ -6,6 +6,8 @@
 //   k_row_accumulate  accumulate Add: one no-return atomic add per element
 //   k_row_grad_losers optimizer step: gradient rows of non-winners summed into gsum
 //   k_row_apply       optimizer step: each key's winner applies SGD / Adagrad / momentum / Adam once
+//   k_row_pooled_grad_losers  pooled push: k_row_grad_losers with rows weight * bag_grads[bag]
+//   k_row_pooled_apply        pooled push: k_row_apply with the winner's row formed the same way
 //   k_row_pooled      pooled pull: out[b] = sum over bag b's keys of weight * row(key)
 //   k_row_pooled_chunks  pooled pull: the chunks of bags longer than kPoolChunk, into partial rows
 //
@@ -298,6 +300,37 @@ __global__ __launch_bounds__(kBlock) void k_row_grad_losers(GroupArgs ga, DenseV
   }
 }
 
+// The rule on one unit, written once for k_row_apply and k_row_pooled_apply:
+// g the winner's own gradient unit, gs the key's gsum unit (set to zero), p
+// and the state units h (slot 0), h2 (slot 1) stepped in place.  Returns
+// whether gs held a non-zero bit (then its zeros are to be written back).
+template <typename T, int KIND, int V>
+__device__ __forceinline__ bool opt_step_unit(const OptUnit<T, V>& g, OptUnit<T, V>& gs, OptUnit<T, V>& p,
+                                              OptUnit<T, V>& h, OptUnit<T, V>& h2, const OptArgs<T>& o) {
+  bool dirty = false;
+#pragma unroll
+  for (int i = 0; i < V; ++i) {
+    dirty |= nonzero_bits(gs.e[i]);
+    const T dd = (g.e[i] + gs.e[i]) + o.wd * p.e[i];
+    if (KIND == 2) {
+      h.e[i] = h.e[i] + dd * dd;
+      p.e[i] = p.e[i] - o.lr * (dd / (sqrt(h.e[i]) + o.eps));
+    } else if (KIND == 3) {
+      h.e[i] = o.mu * h.e[i] + dd;
+      const T step = o.nesterov ? dd + o.mu * h.e[i] : h.e[i];
+      p.e[i] = p.e[i] - o.lr * step;
+    } else if (KIND == 4) {
+      h.e[i] = o.beta1 * h.e[i] + o.omb1 * dd;
+      h2.e[i] = o.beta2 * h2.e[i] + o.omb2 * (dd * dd);
+      p.e[i] = p.e[i] - o.a * (h.e[i] / (sqrt(h2.e[i]) * o.b + o.eps));
+    } else {
+      p.e[i] = p.e[i] - o.lr * dd;
+    }
+    gs.e[i] = T(0);
+  }
+  return dirty;
+}
+
 // KIND: 1 = SGD, 2 = Adagrad, 3 = momentum, 4 = Adam (pskv_optimizer_kind).
 // One writer per row.  `state` is slot 0 (h / v / m), `state2` slot 1 (Adam's
 // v).  No instantiation spills with kRowsInFlight rows in flight (DESIGN.md
@@ -349,27 +382,157 @@ __global__ __launch_bounds__(kBlock) void k_row_apply(GroupArgs ga, DenseView d,
         for (int r = 0; r < kRowsInFlight; ++r) {
           if (!win[r]) continue;
           const uint64_t at = (uint64_t)s.off[r] * U + u;
-          bool dirty = false;
+          const bool dirty = opt_step_unit<T, KIND, V>(g[r], gs[r], p[r], h[r], h2[r], o);
+          store_opt_unit<T, V>(param, at, p[r]);
+          if (KIND >= 2) store_opt_unit<T, V>(state, at, h[r]);
+          if (KIND == 4) store_opt_unit<T, V>(state2, at, h2[r]);
+          if (dirty) store_opt_unit<T, V>(gsum, at, gs[r]);
+        }
+      }
+    }
+  }
+}
+
+// ----------------------------------------------------------- pooled pushes
+// pskv_apply_pooled: pskv_apply's step with the gradient row of
+// key position i formed here, weights[i] * bag_grads[bag(i)].  One batch, so a
+// position is its own stamp index.  Position-major, k_row_grad_losers' and
+// k_row_apply's work split; the bag of a position: pskv_plan.h.
+
+// One multiplication rounded to T: the empty statement keeps the product out
+// of a contraction with the addition that follows, so a weighted term is the
+// same value in gsum, in a winner's step and in a host-expanded pskv_apply.
+__device__ __forceinline__ float rounded_mul(float w, float x) {
+  float r = w * x;
+  asm("" : "+v"(r));
+  return r;
+}
+__device__ __forceinline__ double rounded_mul(double w, double x) {
+  double r = w * x;
+  asm("" : "+v"(r));
+  return r;
+}
+
+// The bags of a step's wanted rows; the workgroup's span is looked up at the
+// first step that wants one (`have`), so a lane group of winners only
+// (k_row_pooled_grad_losers, distinct keys) reads no offset.
+__device__ __forceinline__ void push_bags(const PoolPushArgs& a, uint64_t base, PoolSpan& sp, bool& have,
+                                          const RowStep& s, const bool (&want)[kRowsInFlight],
+                                          uint64_t (&bag)[kRowsInFlight]) {
+  if (!have) {
+    const uint64_t end = base + kGeneralChunk < a.n ? base + kGeneralChunk : a.n;  // base < n
+    sp = pool_bag_span(a.offsets, a.nbags, base, end - 1);
+    have = true;
+  }
+  pool_bags_in<kRowsInFlight>(a.offsets, sp, s.i, want, bag);
+}
+
+// One element per lane, as k_row_grad_losers.
+template <typename AT, bool WEIGHTED>
+__global__ __launch_bounds__(kBlock) void k_row_pooled_grad_losers(PoolPushArgs a, DenseView d,
+                                                                   AT* __restrict__ gsum,
+                                                                   const unsigned long long* __restrict__ owner,
+                                                                   uint32_t* err, uint32_t epoch, RowShape rs) {
+  const uint32_t lane = threadIdx.x & (rs.lanes - 1u);
+  const uint32_t grp = threadIdx.x >> rs.lshift;
+  const uint32_t G = (uint32_t)kBlock >> rs.lshift;
+  const uint32_t U = rs.units;
+  const AT* __restrict__ weights = reinterpret_cast<const AT*>(a.weights);
+  const AT* __restrict__ bg = reinterpret_cast<const AT*>(a.bag_grads);
+  const uint32_t nvwg = (uint32_t)((a.n + kGeneralChunk - 1) / kGeneralChunk);
+  for (uint32_t wg = blockIdx.x; wg < nvwg; wg += gridDim.x) {
+    const uint64_t base = (uint64_t)wg * kGeneralChunk;
+    PoolSpan sp{0, 0};
+    bool have = false;
+    for (uint32_t r0 = grp; r0 < (uint32_t)kGeneralChunk; r0 += kRowsInFlight * G) {
+      if (base + r0 >= a.n) break;
+      RowStep s;
+      load_step(s, a.keys, a.n, base, r0, G, d);
+      bool lose[kRowsInFlight];
+      bool any = false;
 #pragma unroll
-          for (int i = 0; i < V; ++i) {
-            dirty |= nonzero_bits(gs[r].e[i]);
-            const T dd = (g[r].e[i] + gs[r].e[i]) + o.wd * p[r].e[i];
-            if (KIND == 2) {
-              h[r].e[i] = h[r].e[i] + dd * dd;
-              p[r].e[i] = p[r].e[i] - o.lr * (dd / (sqrt(h[r].e[i]) + o.eps));
-            } else if (KIND == 3) {
-              h[r].e[i] = o.mu * h[r].e[i] + dd;
-              const T step = o.nesterov ? dd + o.mu * h[r].e[i] : h[r].e[i];
-              p[r].e[i] = p[r].e[i] - o.lr * step;
-            } else if (KIND == 4) {
-              h[r].e[i] = o.beta1 * h[r].e[i] + o.omb1 * dd;
-              h2[r].e[i] = o.beta2 * h2[r].e[i] + o.omb2 * (dd * dd);
-              p[r].e[i] = p[r].e[i] - o.a * (h[r].e[i] / (sqrt(h2[r].e[i]) * o.b + o.eps));
-            } else {
-              p[r].e[i] = p[r].e[i] - o.lr * dd;
-            }
-            gs[r].e[i] = T(0);
+      for (int r = 0; r < kRowsInFlight; ++r) {
+        const unsigned long long tag = row_tag(epoch, base + r0 + (uint32_t)r * G);
+        lose[r] = s.in[r] && owner[s.off[r]] != tag;
+        any |= lose[r];
+        if (s.live[r] && !s.in[r] && lane == 0) atomicOr(err, kErrRowOutOfRange);
+      }
+      if (!any) continue;  // distinct keys: only keys and stamps were read
+      uint64_t bag[kRowsInFlight];
+      push_bags(a, base, sp, have, s, lose, bag);
+      AT w[kRowsInFlight];
+#pragma unroll
+      for (int r = 0; r < kRowsInFlight; ++r) w[r] = (WEIGHTED && lose[r]) ? weights[s.i[r]] : AT(1);
+      for (uint32_t u = lane; u < U; u += rs.lanes) {
+        AT v[kRowsInFlight];
+#pragma unroll
+        for (int r = 0; r < kRowsInFlight; ++r) v[r] = lose[r] ? bg[bag[r] * U + u] : AT(0);
+#pragma unroll
+        for (int r = 0; r < kRowsInFlight; ++r)
+          if (lose[r]) (void)atomicAdd(gsum + (uint64_t)s.off[r] * U + u, WEIGHTED ? rounded_mul(w[r], v[r]) : v[r]);
+      }
+    }
+  }
+}
+
+// Winners only, one writer per row: k_row_apply with the winner's own gradient
+// unit weights[i] * (the bag row's unit).
+template <typename T, int KIND, int V, bool WEIGHTED>
+__global__ __launch_bounds__(kBlock) void k_row_pooled_apply(PoolPushArgs a, DenseView d, T* __restrict__ gsum,
+                                                             T* __restrict__ state, T* __restrict__ state2,
+                                                             const unsigned long long* __restrict__ owner,
+                                                             uint32_t epoch, RowShape rs, OptArgs<T> o) {
+  const uint32_t lane = threadIdx.x & (rs.lanes - 1u);
+  const uint32_t grp = threadIdx.x >> rs.lshift;
+  const uint32_t G = (uint32_t)kBlock >> rs.lshift;
+  const uint32_t U = rs.units;
+  T* __restrict__ param = reinterpret_cast<T*>(d.param);
+  const T* __restrict__ weights = reinterpret_cast<const T*>(a.weights);
+  const T* __restrict__ bg = reinterpret_cast<const T*>(a.bag_grads);
+  const uint32_t nvwg = (uint32_t)((a.n + kGeneralChunk - 1) / kGeneralChunk);
+  for (uint32_t wg = blockIdx.x; wg < nvwg; wg += gridDim.x) {
+    const uint64_t base = (uint64_t)wg * kGeneralChunk;
+    PoolSpan sp{0, 0};
+    bool have = false;
+    for (uint32_t r0 = grp; r0 < (uint32_t)kGeneralChunk; r0 += kRowsInFlight * G) {
+      if (base + r0 >= a.n) break;
+      RowStep s;
+      load_step(s, a.keys, a.n, base, r0, G, d);
+      bool win[kRowsInFlight];
+      bool any = false;
+#pragma unroll
+      for (int r = 0; r < kRowsInFlight; ++r) {
+        const unsigned long long tag = row_tag(epoch, base + r0 + (uint32_t)r * G);
+        win[r] = s.in[r] && owner[s.off[r]] == tag;
+        any |= win[r];
+      }
+      if (!any) continue;
+      uint64_t bag[kRowsInFlight];
+      push_bags(a, base, sp, have, s, win, bag);
+      T w[kRowsInFlight];
+#pragma unroll
+      for (int r = 0; r < kRowsInFlight; ++r) w[r] = (WEIGHTED && win[r]) ? weights[s.i[r]] : T(1);
+      for (uint32_t u = lane; u < U; u += rs.lanes) {
+        OptUnit<T, V> g[kRowsInFlight], gs[kRowsInFlight], p[kRowsInFlight], h[kRowsInFlight], h2[kRowsInFlight];
+#pragma unroll
+        for (int r = 0; r < kRowsInFlight; ++r) {
+          if (!win[r]) continue;
+          const uint64_t at = (uint64_t)s.off[r] * U + u;
+          g[r] = load_opt_unit<T, V>(bg, bag[r] * U + u);
+          gs[r] = load_opt_unit<T, V>(gsum, at);
+          p[r] = load_opt_unit<T, V>(param, at);
+          if (KIND >= 2) h[r] = load_opt_unit<T, V>(state, at);
+          if (KIND == 4) h2[r] = load_opt_unit<T, V>(state2, at);
+        }
+#pragma unroll
+        for (int r = 0; r < kRowsInFlight; ++r) {
+          if (!win[r]) continue;
+          const uint64_t at = (uint64_t)s.off[r] * U + u;
+          if (WEIGHTED) {
+#pragma unroll
+            for (int i = 0; i < V; ++i) g[r].e[i] = rounded_mul(w[r], g[r].e[i]);
           }
+          const bool dirty = opt_step_unit<T, KIND, V>(g[r], gs[r], p[r], h[r], h2[r], o);
           store_opt_unit<T, V>(param, at, p[r]);
           if (KIND >= 2) store_opt_unit<T, V>(state, at, h[r]);
           if (KIND == 4) store_opt_unit<T, V>(state2, at, h2[r]);
@@ -429,6 +592,23 @@ void launch_row_apply_kind(int kind, uint32_t grid, const GroupArgs& ga, const D
     k_row_apply<T, 2, V><<<grid, kBlock, 0, st>>>(ga, d, g, s1, s2, owner, epoch, rs, o);
   else
     k_row_apply<T, 1, V><<<grid, kBlock, 0, st>>>(ga, d, g, s1, s2, owner, epoch, rs, o);
+}
+
+template <typename T, int V, bool WEIGHTED>
+void launch_row_pooled_apply_kind(int kind, uint32_t grid, const PoolPushArgs& a, const DenseView& d, void* gsum,
+                                  void* const state[2], const unsigned long long* owner, uint32_t epoch,
+                                  const RowShape& rs, const OptArgs<T>& o, hipStream_t st) {
+  T* g = static_cast<T*>(gsum);
+  T* s1 = static_cast<T*>(state[0]);
+  T* s2 = static_cast<T*>(state[1]);
+  if (kind == 4)
+    k_row_pooled_apply<T, 4, V, WEIGHTED><<<grid, kBlock, 0, st>>>(a, d, g, s1, s2, owner, epoch, rs, o);
+  else if (kind == 3)
+    k_row_pooled_apply<T, 3, V, WEIGHTED><<<grid, kBlock, 0, st>>>(a, d, g, s1, s2, owner, epoch, rs, o);
+  else if (kind == 2)
+    k_row_pooled_apply<T, 2, V, WEIGHTED><<<grid, kBlock, 0, st>>>(a, d, g, s1, s2, owner, epoch, rs, o);
+  else
+    k_row_pooled_apply<T, 1, V, WEIGHTED><<<grid, kBlock, 0, st>>>(a, d, g, s1, s2, owner, epoch, rs, o);
 }
 
 // ----------------------------------------------------------- pooled pulls
@@ -735,6 +915,53 @@ hipError_t launch_row_apply(int dtype, int kind, const GroupArgs& ga, uint32_t n
       launch_row_apply_kind<T, 16 / sizeof(T)>(kind, grid, ga, d, gsum, state, owner, epoch, rs, o, st);
     else
       launch_row_apply_kind<T, 1>(kind, grid, ga, d, gsum, state, owner, epoch, rs, o, st);
+  });
+}
+
+// Virtual workgroups of a pooled push: kGeneralChunk positions each, as the
+// mark's over the same single batch (n <= kMaxPiece).
+static uint32_t push_grid(const PoolPushArgs& a) {
+  return row_grid((uint32_t)((a.n + kGeneralChunk - 1) / kGeneralChunk));
+}
+
+hipError_t launch_row_pooled_grad_losers(int dtype, const PoolPushArgs& a, const DenseView& d, void* gsum,
+                                         const unsigned long long* owner, const Ovf& o, uint32_t epoch,
+                                         const RowShape& rs, hipStream_t st) {
+  if (a.n == 0) return hipSuccess;
+  if (a.n > kMaxPiece || a.nbags == 0) return hipErrorInvalidValue;
+  const uint32_t grid = push_grid(a);
+  uint32_t* err = &o.c->stat[1];
+  return with_float_type(dtype, [&](auto z) {
+    using T = decltype(z);
+    if (a.weights)
+      k_row_pooled_grad_losers<T, true><<<grid, kBlock, 0, st>>>(a, d, static_cast<T*>(gsum), owner, err, epoch, rs);
+    else
+      k_row_pooled_grad_losers<T, false><<<grid, kBlock, 0, st>>>(a, d, static_cast<T*>(gsum), owner, err, epoch, rs);
+  });
+}
+
+hipError_t launch_row_pooled_apply(int dtype, int kind, const PoolPushArgs& a, const DenseView& d, void* gsum,
+                                   void* const state[2], const unsigned long long* owner, uint32_t epoch,
+                                   const RowShape& rs, const OptArgs<double>& hy, hipStream_t st) {
+  if (a.n == 0) return hipSuccess;
+  if (a.n > kMaxPiece || a.nbags == 0) return hipErrorInvalidValue;
+  if (kind < 1 || kind > 4 || (kind >= 2 && !state[0]) || (kind == 4 && !state[1])) return hipErrorInvalidValue;
+  const uint32_t grid = push_grid(a);
+  return with_float_type(dtype, [&](auto z) {
+    using T = decltype(z);
+    const OptArgs<T> o = round_opt_args<T>(hy);
+    constexpr int V16 = 16 / sizeof(T);
+    if (rs.unit_bytes == 16) {
+      if (a.weights)
+        launch_row_pooled_apply_kind<T, V16, true>(kind, grid, a, d, gsum, state, owner, epoch, rs, o, st);
+      else
+        launch_row_pooled_apply_kind<T, V16, false>(kind, grid, a, d, gsum, state, owner, epoch, rs, o, st);
+    } else {
+      if (a.weights)
+        launch_row_pooled_apply_kind<T, 1, true>(kind, grid, a, d, gsum, state, owner, epoch, rs, o, st);
+      else
+        launch_row_pooled_apply_kind<T, 1, false>(kind, grid, a, d, gsum, state, owner, epoch, rs, o, st);
+    }
   });
 }
 

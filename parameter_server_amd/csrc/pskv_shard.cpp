@@ -1920,6 +1920,85 @@ int apply_impl(pskv_shard* s, const std::vector<pskv_batch>& in, int flags) {
   return c.v.empty() ? PSKV_OK : apply_device(s, c.views());
 }
 
+// ----------------------------------------------------------- pooled pushes
+// pskv_apply_pooled (pskv.h "Pooled pushes"): pskv_apply's step
+// for one batch whose gradient rows the kernels form themselves,
+// weights[i] * bag_grads[bag(i)].  One launch group (n <= kMaxPiece), three
+// launches, timed as one operation in pskv_apply's slot (kTimeApply):
+//   K4a (stamp mode, unchanged: it reads keys only)   the winner element of each key
+//   k_row_pooled_grad_losers                          every other element's row -> gsum
+//   k_row_pooled_apply                                each winner steps its key's row
+// The offsets stay where the caller has them: a device call's launches do not
+// depend on them, the kernels' bag lookup stays below nbags whatever they hold.
+struct PoolPush {
+  const uint32_t* keys;
+  uint64_t n;
+  const void* weights;  // or null
+  const uint64_t* offsets;
+  uint64_t nbags;
+  const void* bag_grads;
+};
+
+int apply_pooled_device(pskv_shard* s, const PoolPush& c) {
+  if (int rc = ensure_owner(s)) return rc;
+  const std::vector<pskv_batch> v{pskv_batch{c.keys, const_cast<void*>(c.bag_grads), c.n}};
+  const bool vec = rows_unit16(s, {s->dense, s->opt_gsum, s->opt_slot[0], s->opt_slot[1]}, v);
+  const LaunchGroup g = make_group(v, 0, 1, kGeneralChunk);
+  const uint32_t epoch = next_epoch(s);  // one epoch: next_epoch takes a wrap-around itself
+  const OptArgs<double> hy = opt_args(s->opt, ++s->opt_step);
+  const PoolPushArgs a{c.keys, c.weights, c.offsets, c.n, c.nbags, c.bag_grads};
+  LaunchTimer t(s, kTimeApply, c.n);
+  PSKV_HIP(launch_general_mark(s->dtype, PSKV_ASSIGN, g.ga, g.nwg, s->dview(), s->flag + 1, s->owner, nullptr, epoch,
+                               s->stream));
+  PSKV_HIP(launch_row_pooled_grad_losers(s->dtype, a, s->dview(), s->opt_gsum, s->owner, s->ovf, epoch,
+                                         row_shape(s->width, s->vb, false), s->stream));
+  PSKV_HIP(launch_row_pooled_apply(s->dtype, s->opt.kind, a, s->dview(), s->opt_gsum, s->opt_slot, s->owner, epoch,
+                                   row_shape(s->width, s->vb, vec), hy, s->stream));
+  t.done();
+  s->n_general += 3;
+  return PSKV_OK;
+}
+
+// The arguments hold (pskv_apply_pooled checked them, a host call's offsets included).
+int apply_pooled_impl(pskv_shard* s, const PoolPush& call, int flags) {
+  if (s->dtype != PSKV_F32 && s->dtype != PSKV_F64)
+    return fail(PSKV_EINVAL, "pskv_apply_pooled: float shards only (an int32 shard takes no optimizer step)");
+  if (s->opt.kind == PSKV_OPT_NONE)
+    return fail(PSKV_EINVAL, "pskv_apply_pooled: the shard has no optimizer (pskv_shard_set_optimizer)");
+  if (call.n == 0 || call.nbags == 0) return PSKV_OK;  // no key, or no bag to take a row from: no step
+  // rows_front's checks on the keys (apply_impl's: the request server ends, a
+  // host call refuses an out-of-range key); the bag rows stand in for the
+  // values, which the checks only want non-null
+  RowCall c;
+  const std::vector<pskv_batch> in{pskv_batch{call.keys, const_cast<void*>(call.bag_grads), call.n}};
+  int rc = rows_front_checks(s, in, flags,
+                             RowFront{"pskv_apply_pooled", nullptr, /*stop_server=*/true, "key",
+                                      "an optimizer step takes no out-of-range keys", /*with_values=*/false},
+                             &c);
+  if (rc) return rc;
+  if (flags & PSKV_DEVICE) return apply_pooled_device(s, call);
+  // host buffers: pooled_impl's staging layout (keys, weights, offsets, 16-byte
+  // aligned) with the bag rows as an input behind them
+  const size_t rb = row_bytes(s);
+  const size_t wo = round16(call.n * 4);
+  const size_t oo = wo + (call.weights ? round16(call.n * (size_t)s->vb) : 0);
+  const size_t ro = oo + round16((call.nbags + 1) * sizeof(uint64_t));
+  const size_t total = ro + round16(call.nbags * rb);
+  HstageHold hold(s);  // the call returns before its DMA: the hold stays armed
+  if ((rc = ensure_hstage(s, total)) || (rc = ensure_dstage(s, total))) return rc;
+  char* h = static_cast<char*>(s->hstage);
+  char* d = static_cast<char*>(s->dstage);
+  std::vector<Piece> pieces;
+  add_pieces(pieces, call.keys, h, call.n * 4, -1);
+  if (call.weights) add_pieces(pieces, call.weights, h + wo, call.n * (size_t)s->vb, -1);
+  add_pieces(pieces, call.offsets, h + oo, (call.nbags + 1) * sizeof(uint64_t), -1);
+  add_pieces(pieces, call.bag_grads, h + ro, call.nbags * rb, -1);
+  if ((rc = pipelined_h2d(s, pieces, h, d, hold))) return rc;
+  return apply_pooled_device(s, PoolPush{reinterpret_cast<const uint32_t*>(d), call.n,
+                                         call.weights ? d + wo : nullptr, reinterpret_cast<const uint64_t*>(d + oo),
+                                         call.nbags, d + ro});
+}
+
 // What is wrong with a configuration, or null (checked before any handle;
 // fields a kind does not use are ignored).  legacy: the configuration was
 // widened from a pskv_optimizer, which has no size and only the first kinds.
@@ -2760,6 +2839,26 @@ int pskv_apply_grouped(pskv_shard* s, const pskv_batch* batches, uint64_t nb, in
   if (nb && !batches) return fail(PSKV_EINVAL, "pskv_apply_grouped: null batches");
   if (bad_flags(flags)) return fail(PSKV_EINVAL, "pskv_apply_grouped: unknown flags");
   return apply_impl(s, std::vector<pskv_batch>(batches, batches + nb), flags);
+}
+
+// Flags, pointers, the size limit and a host call's offsets are checked before
+// the handle is looked at, as pskv_get_pooled checks its arguments.
+int pskv_apply_pooled(pskv_shard* s, const uint32_t* keys, uint64_t n, const void* weights, const uint64_t* offsets,
+                      uint64_t nbags, const void* bag_grads, int flags) {
+  if (bad_flags(flags)) return fail(PSKV_EINVAL, "pskv_apply_pooled: unknown flags");
+  if (n && !keys) return fail(PSKV_EINVAL, "pskv_apply_pooled: null keys with n > 0");
+  if (nbags && !offsets) return fail(PSKV_EINVAL, "pskv_apply_pooled: null offsets with nbags > 0");
+  if (nbags && !bag_grads) return fail(PSKV_EINVAL, "pskv_apply_pooled: null bag_grads with nbags > 0");
+  if (n > kMaxPiece)
+    return fail(PSKV_EINVAL, "pskv_apply_pooled: n = " + std::to_string(n) + " exceeds 2^31 keys (a pooled push is one launch group)");
+  if (!(flags & PSKV_DEVICE)) {
+    uint64_t bad = 0;
+    if (const char* why = pool_offsets_error(offsets, nbags, n, &bad))
+      return fail(PSKV_EINVAL, "pskv_apply_pooled: offsets: bag " + std::to_string(bad) + ": " + why + " (n = " +
+                                   std::to_string(n) + ", nbags = " + std::to_string(nbags) + ")");
+  }
+  if (!s) return fail(PSKV_EINVAL, "pskv_apply_pooled: null shard");
+  return apply_pooled_impl(s, PoolPush{keys, n, weights, offsets, nbags, bag_grads}, flags);
 }
 
 // The three state entry points: a row Get from, or (put) a row assign Add

@@ -293,6 +293,48 @@ class Shard:
         bs = batches if isinstance(batches, BatchSet) else self.prepare(batches)
         check(lib.pskv_apply_grouped(self._h, bs.arr, bs.n, bs.flags))
 
+    def apply_pooled(self, keys, offsets, bag_grads, weights=None):
+        """One optimizer step from one gradient row per bag (pskv_apply_pooled):
+        the gradient row of keys[i] is weights[i] * bag_grads[b], b the bag with
+        offsets[b] <= i < offsets[b+1] (weights None: the bag's row itself).
+        Arguments as get_pooled's, with bag_grads (nbags * width values) in the
+        place of its output.  numpy -> host path; torch tensors -> device path
+        (offsets an int64 tensor), stream-ordered."""
+        if _is_torch(keys):
+            import torch
+
+            if offsets.dtype != torch.int64 or offsets.numel() < 1:
+                raise ValueError("apply_pooled: device offsets must be an int64 tensor of nbags + 1 values")
+            nbags = offsets.numel() - 1
+            tdt = _torch_dtype(self.dtype)
+            ts = [keys, offsets, bag_grads]
+            if weights is not None:
+                if weights.dtype != tdt or weights.numel() != keys.numel():
+                    raise ValueError("apply_pooled: weights must hold one value of the shard's dtype per key")
+                ts.append(weights)
+            if bag_grads.dtype != tdt or bag_grads.numel() != nbags * self.width:
+                raise ValueError("apply_pooled: bag_grads must hold nbags * width values of the shard's dtype")
+            self._check_dev(*ts)
+            check(lib.pskv_apply_pooled(self._h, keys.data_ptr(), keys.numel(),
+                                        weights.data_ptr() if weights is not None else None, offsets.data_ptr(),
+                                        nbags, bag_grads.data_ptr(), _lib.PSKV_DEVICE))
+            return
+        k = self._host_keys(keys)
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        if off.size < 1:
+            raise ValueError("apply_pooled: offsets must hold nbags + 1 values")
+        nbags = off.size - 1
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=self.dtype)
+            if w.size != k.size:
+                raise ValueError(f"apply_pooled: {w.size} weights for {k.size} keys")
+        g = np.ascontiguousarray(bag_grads, dtype=self.dtype)
+        if g.size != nbags * self.width:
+            raise ValueError(f"apply_pooled: {g.size} bag gradient values for {nbags} bags of width {self.width}")
+        check(lib.pskv_apply_pooled(self._h, k.ctypes.data, k.size, w.ctypes.data if w is not None else None,
+                                    off.ctypes.data, nbags, g.ctypes.data, _lib.PSKV_HOST))
+
     def get_state(self, keys, out=None, slot: int = 0):
         """The rows of `keys` in state slot `slot` (pskv_get_state_slot; Adagrad
         h, momentum v, Adam m and v), as get returns values."""
