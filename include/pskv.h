@@ -305,6 +305,7 @@ typedef struct pskv_info {
   uint64_t n_get_calls;
   uint64_t n_sorted_launches;   /* sorted-path kernel launches */
   uint64_t n_general_launches;  /* general (dedup) path launches, repairs included */
+  uint64_t resident_bytes;      /* the effective resident window (option RESIDENT_BYTES), 0 = none */
 } pskv_info;
 
 /* Kernel ids for pskv_kernel_time. */
@@ -501,6 +502,17 @@ int pskv_shard_info(pskv_shard* s, pskv_info* info);
 /* Tuning and path options of one shard, by name (DESIGN.md §5 lists them and
  * what each selects): GENERAL (0 = K4 stamps, 1 = auto, 2 = K5 always),
  * UNROLL, GET_UNROLL (K1's keys per lane: 0 = by launch size, 4, 8), NT, NTP,
+ * RESIDENT_BYTES (the resident window, DESIGN.md §7: this many bytes of the
+ * dense array from its start are kept in the 256 MiB Infinity Cache -- the
+ * dense-window Add (K2g) stores there plainly and the Get (K1 / K1r) loads
+ * there plainly, and both reach every other parameter non-temporally, so that
+ * nothing displaces the window; -1 = auto, the default: no window for an array
+ * of at most 224 MiB, else 224 MiB; 0 = off; a larger value is clamped to the
+ * array; pskv_info.resident_bytes reports the effective value.  The budget is
+ * one shard's: shards busy on one device at the same time share the cache, and
+ * should have the option set explicitly so that their windows together fit
+ * it.  Scalar-valued shards only; a workload whose hot keys all lie outside
+ * the window is better off with 0),
  * EARLY (K2g early loads: 0 never, 1 always, 2 auto),
  * PAGEABLE_DMA, DMA_MIN_BYTES, DMA_MIN_BYTES_GET,
  * DMA_MIN_BYTES_PINNED, ZC_MAX_BYTES, FRAME_ZC_MAX_BYTES, INLINE,

@@ -92,7 +92,7 @@ class PskvInfo(ctypes.Structure):
         ("dense_bytes", ctypes.c_uint64), ("overflow_capacity", ctypes.c_uint64),
         ("overflow_count", ctypes.c_uint64), ("n_add_calls", ctypes.c_uint64),
         ("n_get_calls", ctypes.c_uint64), ("n_sorted_launches", ctypes.c_uint64),
-        ("n_general_launches", ctypes.c_uint64),
+        ("n_general_launches", ctypes.c_uint64), ("resident_bytes", ctypes.c_uint64),
     ]
 
 

@@ -114,12 +114,25 @@ def build_random_access(force=False):
     return RA_OUT
 
 
+RW_SRC = os.path.join(ROOT, "tools", "micro", "resident_window.hip")
+RW_OUT = os.path.join(ROOT, "tools", "micro", "resident_window")
+
+
+def build_resident_window(force=False):
+    """The resident-window probe (a stand-alone program, not part of libpskv)."""
+    if force or _stale(RW_OUT, [RW_SRC]):
+        _run([HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17", RW_SRC, "-o", RW_OUT])
+    return RW_OUT
+
+
 def build_all(force=False):
     lib = build_lib(force)
     orc = build_oracle()
     progs = build_cpp_tests(force)
     ra = build_random_access(force)
-    return {"lib": lib, "cpp": progs, "oracle": orc, "random_access": ra, "in_tree": build_in_tree()}
+    rw = build_resident_window(force)
+    return {"lib": lib, "cpp": progs, "oracle": orc, "random_access": ra, "resident_window": rw,
+            "in_tree": build_in_tree()}
 
 
 if __name__ == "__main__":

@@ -116,6 +116,12 @@ struct DenseView {
   void* param;
   uint32_t key_begin;
   uint64_t range;  // number of owned keys, <= 2^32
+  // The resident window (option RESIDENT_BYTES): offsets [0,
+  // resident) of the dense array, in keys from key_begin, are meant to stay in
+  // the Infinity Cache.  K2g's dense mode and K1 / K1r reach them with plain
+  // stores and loads and every other parameter with non-temporal ones; a cache
+  // hint only, every other kernel ignores it.  0: no window.
+  uint64_t resident;
 };
 
 // The overflow table: open addressing over u64 key slots (EMPTY = ~0) for the
@@ -166,7 +172,8 @@ hipError_t launch_assign_sorted(int vb, bool vec, const uint32_t* keys, const vo
                                 hipStream_t st);
 // Grouped sorted Add.  `ga` must be built with stream_chunk(unroll) elements per chunk
 // (used by the dense-window mode); the tile mode ignores the chunking.
-// ntp: non-temporal parameter stores in the dense-window mode
+// ntp: non-temporal parameter stores in the dense-window mode, outside the
+// resident window (d.resident; chunks inside it store plainly)
 hipError_t launch_assign_group(int vb, bool vec, int unroll, bool nt, bool ntp, bool early,
                                const GroupArgs& ga,
                                const DenseView& d, uint32_t tile_shift, uint64_t ntiles,

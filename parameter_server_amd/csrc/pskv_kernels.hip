@@ -412,17 +412,51 @@ __device__ unsigned long long g_step_stamps[2][8192][4];
 // key; cfg 4's producer windows do); otherwise four scalar gathers.  (Round 3
 // loaded the two slots such a run straddles and selected: K1 ran 4-6 % slower
 // at phases 1-3 than at phase 0, `profiles/r03_probes/align_probe_own_range.log`.)
-template <typename VT, bool NTP = false, bool FRESH = false>
+//
+// The resident window (DenseView::resident): a run outside it is loaded
+// non-temporally, so that it does not displace the window from the Infinity
+// Cache.  The choice is the wave's, from its first lane's key (a scalar
+// branch; a dense pull's wave covers 1 KiB of parameters, and a wave that
+// straddles the edge or whose keys are scattered may take either load: a cache
+// hint, never a result).  Every lane of the wave calls this together.
+__device__ __forceinline__ bool outside_resident(const DenseView& d, uint32_t off0) {
+  return d.resident != 0 && (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)off0) >= d.resident;
+}
+// K2g's dense mode: the chunk whose first parameter offset is `off` (workgroup-
+// uniform) stores plainly inside the window and non-temporally (option NTP)
+// outside; a chunk that straddles the edge follows its first offset.
+__device__ __forceinline__ bool chunk_resident(const DenseView& d, uint64_t off) {
+  return uniform64(off) < d.resident;
+}
+// A load or store chosen at run time between its plain and its non-temporal
+// form sits in two branches that differ in nothing but that hint, and the
+// compiler's branch folding merges such twins into one access WITHOUT the hint.
+// An empty asm statement before and after the non-temporal twin keeps the two
+// branches apart (it emits nothing).
+__device__ __forceinline__ void nt_apart() { asm volatile(""); }
+
+template <typename VT, bool FRESH = false>
 __device__ __forceinline__ void gather4(const DenseView& d, const Ovf& o, const uint32_t (&k)[4],
                                         VT (&v)[4]) {
   const uint32_t off0 = k[0] - d.key_begin;
   const bool run = (k[1] == k[0] + 1u) & (k[2] == k[0] + 2u) & (k[3] == k[0] + 3u) &
                    ((uint64_t)off0 + 3u < d.range);
+  const bool ntp = outside_resident(d, off0);
   if (run && (off0 & 3u) == 0u) {
-    Vec4<VT>::template load<NTP>(reinterpret_cast<const VT*>(d.param) + off0, v);
+    if (ntp) {
+      nt_apart();
+      Vec4<VT>::template load<true>(reinterpret_cast<const VT*>(d.param) + off0, v);
+      nt_apart();
+    } else
+      Vec4<VT>::template load<false>(reinterpret_cast<const VT*>(d.param) + off0, v);
   } else if (sizeof(VT) == 4 && run) {
     uint32_t t[4];
-    ld16a4<NTP>(reinterpret_cast<const uint32_t*>(d.param) + off0, t);
+    if (ntp) {
+      nt_apart();
+      ld16a4<true>(reinterpret_cast<const uint32_t*>(d.param) + off0, t);
+      nt_apart();
+    } else
+      ld16a4<false>(reinterpret_cast<const uint32_t*>(d.param) + off0, t);
 #pragma unroll
     for (int e = 0; e < 4; ++e) v[e] = (VT)t[e];
   } else {
@@ -439,11 +473,22 @@ __device__ __forceinline__ void gather2(const DenseView& d, const Ovf& o, const 
   using T = unsigned long long;
   const uint32_t off0 = k[0] - d.key_begin;
   const bool run = (k[1] == k[0] + 1u) & ((uint64_t)off0 + 1u < d.range);
+  const bool ntp = outside_resident(d, off0);
   if (run && (off0 & 1u) == 0u) {
-    Vec2x8::load(reinterpret_cast<const T*>(d.param) + off0, v);
+    if (ntp) {
+      nt_apart();
+      Vec2x8::load<true>(reinterpret_cast<const T*>(d.param) + off0, v);
+      nt_apart();
+    } else
+      Vec2x8::load<false>(reinterpret_cast<const T*>(d.param) + off0, v);
   } else if (run) {
     uint32_t t[4];
-    ld16a4<false>(reinterpret_cast<const uint32_t*>(reinterpret_cast<const T*>(d.param) + off0), t);
+    if (ntp) {
+      nt_apart();
+      ld16a4<true>(reinterpret_cast<const uint32_t*>(reinterpret_cast<const T*>(d.param) + off0), t);
+      nt_apart();
+    } else
+      ld16a4<false>(reinterpret_cast<const uint32_t*>(reinterpret_cast<const T*>(d.param) + off0), t);
     v[0] = (T)t[0] | ((T)t[1] << 32);
     v[1] = (T)t[2] | ((T)t[3] << 32);
   } else {
@@ -501,7 +546,7 @@ __device__ __forceinline__ void gather_chunk(const GroupArgs& ga, const DenseVie
 #endif
     VT v[U][4];
 #pragma unroll
-    for (int u = 0; u < U; ++u) gather4<VT, false, FRESH>(d, o, k[u], v[u]);
+    for (int u = 0; u < U; ++u) gather4<VT, FRESH>(d, o, k[u], v[u]);
 #pragma unroll
     for (int u = 0; u < U; ++u)
       Vec4<VT>::template store<NT>(out + base + (uint64_t)(u * kBlock + tid) * 4, v[u]);
@@ -766,6 +811,7 @@ __device__ __forceinline__ bool dense_chunk(const GroupArgs& ga, const DenseView
       }
     }
     T* __restrict__ p8 = reinterpret_cast<T*>(param);
+    const bool ntp = NTP && !chunk_resident(d, (uint64_t)p0 + base);
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const uint64_t i = base + (uint64_t)(u * kBlock + tid) * 4;
@@ -776,8 +822,15 @@ __device__ __forceinline__ bool dense_chunk(const GroupArgs& ga, const DenseView
       const uint32_t ka = first + (uint32_t)(base + (uint64_t)(u * kBlock + (tid & ~63)) * 4) + 2u * lane;
       const uint32_t offa = ka - d.key_begin;
       if (later == 0 && (offa & 1u) == 0u) {
-        Vec2x8::store<NTP>(p8 + offa, va[u]);
-        Vec2x8::store<NTP>(p8 + offa + 128, vb[u]);
+        if (ntp) {
+          nt_apart();
+          Vec2x8::store<true>(p8 + offa, va[u]);
+          Vec2x8::store<true>(p8 + offa + 128, vb[u]);
+          nt_apart();
+        } else {
+          Vec2x8::store<false>(p8 + offa, va[u]);
+          Vec2x8::store<false>(p8 + offa + 128, vb[u]);
+        }
       } else {
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
@@ -863,6 +916,7 @@ __device__ __forceinline__ bool dense_chunk_own(const GroupArgs& ga, const Dense
     const uint32_t* __restrict__ kc = keys + base;
     const uint32_t* __restrict__ vc = vals + base;
     uint32_t* __restrict__ pc = param + p0 + base;
+    const bool ntp = NTP && !chunk_resident(d, (uint64_t)p0 + base);
     if (!PRE) {
 #pragma unroll
       for (int u = 0; u < U; ++u) {
@@ -879,7 +933,12 @@ __device__ __forceinline__ bool dense_chunk_own(const GroupArgs& ga, const Dense
       bad |= lbad;
       if (covered || lbad) continue;
       if (later == 0) {
-        st16a4<NTP>(pc + o, v[u]);
+        if (ntp) {
+          nt_apart();
+          st16a4<true>(pc + o, v[u]);
+          nt_apart();
+        } else
+          st16a4<false>(pc + o, v[u]);
       } else {
 #pragma unroll
         for (int e = 0; e < 4; ++e)

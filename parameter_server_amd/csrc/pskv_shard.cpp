@@ -86,6 +86,13 @@ constexpr uint64_t kDefaultOverflowSlots = 1ull << 16;
 // up to 2 Ki keys (DMA 26), DMA ahead from 4 Ki keys
 constexpr size_t kDefaultDmaMinBytes = 32ull << 20;
 constexpr size_t kDefaultDmaMinBytesGet = 32ull << 10;
+// Option RESIDENT_BYTES (DESIGN.md §7 "Resident window").  kResidentAutoBytes:
+// what auto (-1) keeps resident of a dense array larger than itself.  The
+// headline sweep (profiles/resident_window/sweep.txt): 128 MiB and less lose or
+// gain nothing, 224-256 MiB gain 2.3 %, 288 MiB loses 1 %; 224 leaves the
+// 256 MiB cache some room for what else runs.
+constexpr uint64_t kResidentAutoBytes = 224ull << 20;
+constexpr int64_t kResidentDefault = -1;
 
 struct TimedLaunch {
   int kernel;
@@ -378,7 +385,24 @@ struct pskv_shard {
   void* opt_slot[2] = {nullptr, nullptr};  // the first opt_slots(opt.kind) are allocated
   uint64_t opt_step = 0;
 
-  DenseView dview() const { return DenseView{dense, key_begin, range}; }
+  // PSKV_RESIDENT_BYTES: the resident window, bytes of the dense
+  // array from its start that K2g's dense mode and K1 / K1r keep in the
+  // Infinity Cache (plain stores and loads inside, non-temporal ones outside).
+  // -1 = auto (resident_bytes() below), 0 = off, else bytes (clamped to the
+  // array).  The budget is this shard's alone: shards busy on one device at
+  // the same time share the cache and should have the option set explicitly.
+  int64_t tune_resident_bytes = kResidentDefault;
+
+  // The effective window in bytes.  Auto: none for an array the cache holds
+  // anyway (at most the budget), else the budget.  Row shards have none (the
+  // row kernels do not look at it).
+  uint64_t resident_bytes() const {
+    if (width != 1) return 0;
+    const uint64_t bytes = range * (uint64_t)vb;
+    if (tune_resident_bytes < 0) return bytes <= kResidentAutoBytes ? 0 : kResidentAutoBytes;
+    return std::min<uint64_t>((uint64_t)tune_resident_bytes, bytes);
+  }
+  DenseView dview() const { return DenseView{dense, key_begin, range, resident_bytes() / (uint64_t)vb}; }
 };
 
 namespace {
@@ -2346,6 +2370,7 @@ const Option kOptions[] = {
     PSKV_OPT("FOLD_REPLAY", 0, 1, tune_fold_replay, int),   // add_get: K4r folded into K1 (K1r)
     PSKV_OPT("NT", 0, 1, tune_nt, bool),
     PSKV_OPT("NTP", 0, 1, tune_ntp, bool),
+    PSKV_OPT("RESIDENT_BYTES", -1, INT64_MAX, tune_resident_bytes, int64_t),  // -1 = auto, 0 = off
     PSKV_OPT("EARLY", 0, 2, tune_early, int),
     PSKV_OPT("PAGEABLE_DMA", 0, 1, tune_pageable_dma, bool),
     PSKV_OPT("DMA_MIN_BYTES", 0, INT64_MAX, tune_dma_min_bytes, size_t),
@@ -2877,7 +2902,7 @@ static int state_call(pskv_shard* s, const std::string& who, bool adagrad_only, 
   rc = srv_stop(s);
   if (rc) return rc;
   const std::vector<pskv_batch> in{pskv_batch{keys, vals, n}};
-  const DenseView d{arr, s->key_begin, s->range};
+  const DenseView d{arr, s->key_begin, s->range, 0};
   if (!put) return rows_get_from(s, in, flags, d, who.c_str(), nullptr);
   return rows_add_to(s, in, flags, d, PSKV_ASSIGN,
                      RowFront{who.c_str(), nullptr, false, "key",
@@ -2990,6 +3015,7 @@ int pskv_shard_info(pskv_shard* s, pskv_info* info) {
   info->n_get_calls = s->n_get;
   info->n_sorted_launches = s->n_sorted;
   info->n_general_launches = s->n_general;
+  info->resident_bytes = s->resident_bytes();
   return PSKV_OK;
 }
 
