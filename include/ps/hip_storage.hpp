@@ -35,6 +35,10 @@
 // the weighted sum of the bag's rows computed in the shard -- the margin
 // sum_i w[key_i] * x_i of the reference's logistic-regression worker as one
 // pull of one value per sample.  Keys outside the range abort.
+// Pooled pushes (SubApplyPooled, pskv_apply_pooled): one gradient row per bag,
+// expanded in the shard inside one optimizer step; SubApplyPooledGrouped
+// (pskv_apply_pooled_grouped) makes ONE step of several workers' pooled pushes,
+// the BSP flush, as AddGrouped does of their plain pushes.
 #pragma once
 
 #include <cstdint>
@@ -189,6 +193,37 @@ class HipStorage : public AbstractStorage {
     pskv_check(pskv_apply_pooled(shard_, typed_keys.data(), typed_keys.size(), weights ? weights->data() : nullptr,
                                  offsets.data(), offsets.size() - 1, bag_grads.data(), PSKV_HOST | PSKV_HOST_FRAME),
                "pskv_apply_pooled");
+  }
+
+  // The four arrays of one SubApplyPooled call, each a counted reference, so a
+  // deferred push keeps its data alive until the flush (weighted false: every
+  // weight is one and `weights` is not read).
+  struct PooledPush {
+    third_party::SArray<Key> keys;
+    third_party::SArray<Val> weights;
+    bool weighted;
+    third_party::SArray<uint64_t> offsets;
+    third_party::SArray<Val> bag_grads;
+  };
+
+  // ONE optimizer step from the pooled pushes of several workers
+  // (pskv_apply_pooled_grouped): the BSP flush of an iteration's deferred
+  // SubApplyPooled calls, as AddGrouped is to SubAdd.  Not part of AbstractStorage.
+  void SubApplyPooledGrouped(const std::vector<PooledPush>& pushes) {
+    std::vector<pskv_pool_batch> batches;
+    batches.reserve(pushes.size());
+    for (const PooledPush& p : pushes) {
+      if (p.offsets.size() == 0 || (p.weighted && p.weights.size() != p.keys.size()) ||
+          p.bag_grads.size() != (p.offsets.size() - 1) * width_) {
+        std::fprintf(stderr, "Check failed: batch %zu: offsets.size() >= 1, weights.size() == keys.size() and "
+                             "bag_grads.size() == (offsets.size() - 1) * width\n", batches.size());
+        std::abort();
+      }
+      batches.push_back(pskv_pool_batch{p.keys.data(), p.weighted ? p.weights.data() : nullptr, p.offsets.data(),
+                                        p.bag_grads.data(), p.keys.size(), p.offsets.size() - 1});
+    }
+    pskv_check(pskv_apply_pooled_grouped(shard_, batches.data(), batches.size(), PSKV_HOST | PSKV_HOST_FRAME),
+               "pskv_apply_pooled_grouped");
   }
 
   // The reference's FinishIter is a no-op (map_storage.hpp:47); here it is the

@@ -216,10 +216,45 @@
  *     the call first ends the server;
  *   - timing: one operation of pskv_apply_time's slot (PSKV_TIME_APPLY), with
  *     elements = n;
- *   - not provided: a grouped form, an accumulate-mode pskv_add counterpart,
+ *   - not provided: an accumulate-mode pskv_add counterpart,
  *     int32, slicing inside KVClientTable (a worker of a range-partitioned
  *     table sends each server its part of every bag with the bag's full
  *     gradient row).
+ *
+ * Grouped pooled pushes (pskv_apply_pooled_grouped): the pooled
+ * pushes of several workers as one step, as pskv_apply_grouped is to
+ * pskv_apply (a BSP flush is one step over the summed minibatch gradient).
+ *   - the call is the ONE step pskv_apply_pooled would make of the
+ *     concatenation of the batches: keys, weights and bag rows back to back,
+ *     each batch's offsets shifted by the keys before it.  Occurrences of a
+ *     key in any batch are summed in unspecified order, the rule is applied
+ *     once per distinct key, every other key keeps p and its state bit for bit;
+ *   - the step counter advances by one per call that queues work, however
+ *     many batches or launch groups (32 batches, fewer than 2^32 keys each)
+ *     the call has; every launch group uses the same t;
+ *   - each product is one multiplication rounded to T, as in
+ *     pskv_apply_pooled; a batch with weights == NULL beside weighted batches
+ *     contributes its bag rows bit for bit.  When every key of the whole call
+ *     is distinct, p and every state slot equal, bit for bit,
+ *     pskv_apply_pooled of the concatenation and pskv_apply_grouped of the
+ *     host-expanded rows fl_T(w_i * bg);
+ *   - a batch with n == 0 or nbags == 0 contributes nothing; a call of such
+ *     batches only, or nb == 0, returns PSKV_OK, queues nothing and leaves
+ *     the step counter alone;
+ *   - checked before the handle is looked at: flags as for
+ *     pskv_apply_pooled; null batches with nb > 0; per batch the null
+ *     pointers, n > 2^31 and a host call's offsets as pskv_apply_pooled
+ *     checks them: PSKV_EINVAL naming the BATCH and the first bad bag;
+ *   - with the handle: float shards with an optimizer only; a host call that
+ *     holds a key outside [key_begin, key_end) returns PSKV_EINVAL naming the
+ *     batch and the key and applies nothing; a device call drops such keys and
+ *     the next pskv_sync returns PSKV_ESTATE; SERVE = 1 is ended first;
+ *   - malformed device offsets in any batch give unspecified values to the
+ *     keys of the call, never an access outside that batch's arrays and never
+ *     a change to a key that is not in the call;
+ *   - a host call returns as a host pskv_apply does; timing: PSKV_TIME_APPLY's
+ *     slot, one operation per launch group, elements = the sum of n;
+ *   - not provided: a grouped pooled PULL (it would save launches only).
  *
  * Threading: one shard handle is used by one host thread at a time (the
  * reference calls a storage only from its ServerThread, server_thread.cpp:20-50);
@@ -378,6 +413,19 @@ int pskv_get_pooled(pskv_shard* s, const uint32_t* keys, uint64_t n, const void*
  * bag_grads: nbags * W values, row b at element b * W. */
 int pskv_apply_pooled(pskv_shard* s, const uint32_t* keys, uint64_t n, const void* weights,
                       const uint64_t* offsets, uint64_t nbags, const void* bag_grads, int flags);
+
+/* Grouped pooled push (semantics: "Grouped pooled pushes"): ONE optimizer step
+ * from the pooled pushes of nb workers, the step pskv_apply_pooled would make
+ * of their concatenation.  Each batch holds the arguments of one
+ * pskv_apply_pooled call. */
+typedef struct pskv_pool_batch {
+  const uint32_t* keys;      /* n keys, bag after bag */
+  const void* weights;       /* n values of the shard's type, or NULL (every weight one) */
+  const uint64_t* offsets;   /* nbags + 1 */
+  const void* bag_grads;     /* nbags * W values */
+  uint64_t n, nbags;
+} pskv_pool_batch;
+int pskv_apply_pooled_grouped(pskv_shard* s, const pskv_pool_batch* batches, uint64_t nb, int flags);
 
 /* Grouped forms: nb batches in one call, semantically identical to nb
  * consecutive pskv_add / pskv_get calls in array order, executed in a small,

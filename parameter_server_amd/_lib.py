@@ -77,12 +77,17 @@ EXPORTED = [
     "pskv_shard_set_optimizer_ex", "pskv_shard_get_optimizer_ex", "pskv_get_state_slot", "pskv_put_state",
     "pskv_get_step", "pskv_set_step",
     "pskv_get_pooled", "pskv_pooled_time",
-    "pskv_apply_pooled",
+    "pskv_apply_pooled", "pskv_apply_pooled_grouped",
 ]
 
 
 class PskvBatch(ctypes.Structure):
     _fields_ = [("keys", ctypes.c_void_p), ("vals", ctypes.c_void_p), ("n", ctypes.c_uint64)]
+
+
+class PskvPoolBatch(ctypes.Structure):
+    _fields_ = [("keys", ctypes.c_void_p), ("weights", ctypes.c_void_p), ("offsets", ctypes.c_void_p),
+                ("bag_grads", ctypes.c_void_p), ("n", ctypes.c_uint64), ("nbags", ctypes.c_uint64)]
 
 
 class PskvInfo(ctypes.Structure):
@@ -169,6 +174,7 @@ def _load():
         "pskv_get_pooled": ([vp, vp, u64, vp, vp, u64, vp, i32], i32),
         "pskv_pooled_time": ([vp, ctypes.POINTER(u64), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(u64)], i32),
         "pskv_apply_pooled": ([vp, vp, u64, vp, vp, u64, vp, i32], i32),
+        "pskv_apply_pooled_grouped": ([vp, ctypes.POINTER(PskvPoolBatch), u64, i32], i32),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)

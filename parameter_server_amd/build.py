@@ -27,6 +27,8 @@ CPP_TESTS = {  # program -> (source in tests/cpp, links the oracle checker)
     "hip_storage_opt2_test": ("hip_storage_opt2_test.cpp", False),
     "hip_storage_pooled_test": ("hip_storage_pooled_test.cpp", False),
     "hip_storage_pooled_push_test": ("hip_storage_pooled_push_test.cpp", False),
+    "hip_storage_pooled_push_group_test": ("hip_storage_pooled_push_group_test.cpp", False),
+    "pooled_push_group_plan_test": ("pooled_push_group_plan_test.cpp", False),  # host-only: the planner's arithmetic
 }
 ORACLE_DIR = os.path.join(ROOT, "oracle")
 BIN_DIR = os.path.join(PKG, "bin")
@@ -67,7 +69,7 @@ def build_cpp_tests(force=False):
     for prog, (src, with_oracle) in CPP_TESTS.items():
         s = os.path.join(ROOT, "tests", "cpp", src)
         out = os.path.join(BIN_DIR, prog)
-        deps = [s, LIB_OUT] + hdrs
+        deps = [s, LIB_OUT, os.path.join(CSRC, "pskv_plan.h")] + hdrs  # (the planner: the host-only programs include it)
         extra = []
         if with_oracle:  # test programs only: the checker is linked beside the product
             deps.append(os.path.join(ORACLE_DIR, "liboracle.so"))

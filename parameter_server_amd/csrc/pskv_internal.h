@@ -319,6 +319,21 @@ hipError_t launch_row_pooled_grad_losers(int dtype, const PoolPushArgs& a, const
 hipError_t launch_row_pooled_apply(int dtype, int kind, const PoolPushArgs& a, const DenseView& d, void* gsum,
                                    void* const state[2], const unsigned long long* owner, uint32_t epoch,
                                    const RowShape& rs, const OptArgs<double>& hy, hipStream_t st);
+// Grouped pooled push (pskv_apply_pooled_grouped): the two
+// launches above over a launch group of pooled batches (PoolGroupArgs,
+// pskv_plan.h), behind launch_general_mark over the GroupArgs of the same
+// batches (keys and n) with the same epoch.  A virtual workgroup belongs to
+// one batch; a position's tag carries the keys of the batches before it.
+// weighted: some batch of the group has weights (a batch without them then
+// contributes its bag rows unmultiplied).  rs built with unit16 = false.
+hipError_t launch_row_pooled_group_grad_losers(int dtype, const PoolGroupArgs& ga, uint32_t nwg, bool weighted,
+                                               const DenseView& d, void* gsum, const unsigned long long* owner,
+                                               const Ovf& o, uint32_t epoch, const RowShape& rs, hipStream_t st);
+// unit16 also wants every batch's bag_grads 16-byte aligned.
+hipError_t launch_row_pooled_group_apply(int dtype, int kind, const PoolGroupArgs& ga, uint32_t nwg, bool weighted,
+                                         const DenseView& d, void* gsum, void* const state[2],
+                                         const unsigned long long* owner, uint32_t epoch, const RowShape& rs,
+                                         const OptArgs<double>& hy, hipStream_t st);
 // p[0..n) = v (float or double by dtype): the accumulator's initial value.
 hipError_t launch_fill(int dtype, void* p, uint64_t n, double v, hipStream_t st);
 

@@ -1,10 +1,13 @@
 // pskv_plan.h — the host planner: the pure arithmetic of a shard's host paths
 // (pskv_shard.cpp).  How a call's batches are cut into pieces, launch groups
 // and DMA windows, where each batch lies in a staging buffer, the vectorised
-// key check of host inputs, K5's bucket rule, and the bags, chunks and windows
-// of a pooled pull (the part the kernels share is marked PSKV_HD).  No HIP and
+// key check of host inputs, K5's bucket rule, the bags, chunks and windows
+// of a pooled pull, the bag of a position of a pooled push, and the launch
+// groups, descriptors and staging of a grouped pooled push (the part the
+// kernels share is marked PSKV_HD).  No HIP and
 // no shard state: everything here is a function of its arguments, so it is
-// tested on the CPU (tests/cpp/host_plan_test.cpp, tests/cpp/pooled_plan_test.cpp).  Internal linkage throughout: libpskv.so
+// tested on the CPU (tests/cpp/host_plan_test.cpp, tests/cpp/pooled_plan_test.cpp,
+// tests/cpp/pooled_push_plan_test.cpp, tests/cpp/pooled_push_group_plan_test.cpp).  Internal linkage throughout: libpskv.so
 // exports nothing from this header (the types the kernels do not share are in
 // an unnamed namespace, so that no instantiation over them is exported either).
 #pragma once
@@ -401,6 +404,138 @@ static inline const char* pool_offsets_error(const uint64_t* off, uint64_t nbags
   *bad = nbags - 1;
   if (off[nbags] != n) return "offsets[nbags] must equal n";
   return nullptr;
+}
+
+}  // namespace
+
+// ---------------------------------------------------- grouped pooled pushes
+// pskv_apply_pooled_grouped (pskv.h "Grouped pooled pushes"): the pooled
+// pushes of several workers as ONE step.  The live batches (n > 0 and nbags >
+// 0) of a call are cut into launch groups of at most kMaxPoolBatches batches
+// and fewer than kMaxGroupElems keys; a launch group's descriptors travel by
+// value in the kernel arguments, cut into virtual workgroups of `chunk`
+// positions as a GroupArgs of the same batches is, so that K4a, given that
+// GroupArgs (keys and n only), stamps the tags the pooled kernels compare.
+constexpr int kMaxPoolBatches = 32;  // batches per launch group of a grouped pooled push (kernarg budget)
+
+struct PoolBatchDesc {
+  const uint32_t* keys;     // n
+  const void* weights;      // n values, or null: this batch's terms are its bag rows themselves
+  const uint64_t* offsets;  // nbags + 1 (the kernels read [0, nbags))
+  const void* bag_grads;    // nbags rows
+  uint64_t n, nbags;        // both > 0
+};
+struct PoolGroupArgs {
+  int nb;
+  uint32_t wg_prefix[kMaxPoolBatches + 1];  // first virtual workgroup of each batch
+  PoolBatchDesc b[kMaxPoolBatches];
+};
+static_assert(sizeof(PoolBatchDesc) == 48, "six 8-byte words per batch");
+// beside it in the 4 KiB kernarg segment: DenseView (32), five pointers, the
+// epoch, RowShape (16), OptArgs<double> (88) and the hidden arguments (~300)
+static_assert(sizeof(PoolGroupArgs) <= 1800, "a pooled group plus the other arguments fit the 4 KiB kernarg segment");
+
+namespace {
+
+// The live batches of a call, in call order (a batch without a key or without
+// a bag contributes nothing), and each one's index in the call.
+static inline std::vector<pskv_pool_batch> pool_live_batches(const pskv_pool_batch* b, uint64_t nb,
+                                                             std::vector<uint64_t>* index = nullptr) {
+  std::vector<pskv_pool_batch> out;
+  for (uint64_t i = 0; i < nb; ++i) {
+    if (b[i].n == 0 || b[i].nbags == 0) continue;
+    out.push_back(b[i]);
+    if (index) index->push_back(i);
+  }
+  return out;
+}
+
+// The batches as the mark takes them: keys and n (the bag rows stand in for
+// the values, which the mark does not read).
+static inline std::vector<pskv_batch> pool_mark_batches(const std::vector<pskv_pool_batch>& v) {
+  std::vector<pskv_batch> out;
+  for (const auto& b : v) out.push_back(pskv_batch{b.keys, const_cast<void*>(b.bag_grads), b.n});
+  return out;
+}
+
+// Launch groups of live batches (each of at most kMaxPiece keys): split_groups
+// with the pooled limit.
+static inline std::vector<Span> pool_split_groups(const std::vector<pskv_pool_batch>& v,
+                                                  size_t max_batches = kMaxPoolBatches,
+                                                  uint64_t max_elems = kMaxGroupElems) {
+  return split_groups(pool_mark_batches(v), max_batches, max_elems);
+}
+
+// The descriptor of batches [b, e) of a list (e - b <= kMaxPoolBatches), cut
+// into virtual workgroups of `chunk` positions; *nwg: their number.
+static inline PoolGroupArgs make_pool_group(const std::vector<pskv_pool_batch>& v, size_t b, size_t e, uint64_t chunk,
+                                            uint32_t* nwg, uint64_t* elems) {
+  PoolGroupArgs g;
+  std::memset(&g, 0, sizeof(g));
+  g.nb = (int)(e - b);
+  uint64_t wg = 0, el = 0;
+  for (size_t i = b; i < e; ++i) {
+    const size_t j = i - b;
+    g.wg_prefix[j] = (uint32_t)wg;
+    g.b[j] = PoolBatchDesc{v[i].keys, v[i].weights, v[i].offsets, v[i].bag_grads, v[i].n, v[i].nbags};
+    wg += (v[i].n + chunk - 1) / chunk;
+    el += v[i].n;
+  }
+  g.wg_prefix[e - b] = (uint32_t)wg;
+  *nwg = (uint32_t)wg;
+  *elems = el;
+  return g;
+}
+
+// The batch of virtual workgroup wg: the last batch whose first workgroup is
+// at or before it (live batches hold at least one workgroup each, so the
+// prefix increases strictly).
+PSKV_HD static inline int pool_group_batch_of(const PoolGroupArgs& ga, uint32_t wg) {
+  int lo = 0, hi = ga.nb;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (ga.wg_prefix[mid] <= wg)
+      lo = mid;
+    else
+      hi = mid;
+  }
+  return lo;
+}
+// Group-wide index of batch j's first position: K4a's elem_prefix over the
+// same batches.  A position's tag is epoch << 32 | (this + the position).
+PSKV_HD static inline uint64_t pool_group_elem_prefix(const PoolGroupArgs& ga, int j) {
+  uint64_t e = 0;
+  for (int i = 0; i < j; ++i) e += ga.b[i].n;
+  return e;
+}
+
+// A host call's staging: every live batch's keys, weights (where it has
+// them), offsets and bag rows, each range on a 16-byte boundary, batch after
+// batch.  vb: bytes per value; rb: bytes per row.
+struct PoolStageSlot {
+  size_t keys, weights, offsets, rows;  // byte offsets from the staging's start (weights: unused without weights)
+};
+struct PoolStageLayout {
+  std::vector<PoolStageSlot> at;  // per live batch
+  size_t total = 0;
+};
+static inline PoolStageLayout pool_stage_layout(const std::vector<pskv_pool_batch>& v, size_t vb, size_t rb) {
+  PoolStageLayout l;
+  l.at.resize(v.size());
+  size_t o = 0;
+  for (size_t i = 0; i < v.size(); ++i) {
+    PoolStageSlot& s = l.at[i];
+    s.keys = o;
+    o += round16(v[i].n * 4);
+    s.weights = o;
+    if (v[i].weights) o += round16(v[i].n * vb);
+    s.offsets = o;
+    o += round16((v[i].nbags + 1) * sizeof(uint64_t));
+    s.rows = o;
+    o += round16(v[i].nbags * rb);
+  }
+  l.total = o;
+  return l;
 }
 
 }  // namespace

@@ -8,6 +8,8 @@
 //   k_row_apply       optimizer step: each key's winner applies SGD / Adagrad / momentum / Adam once
 //   k_row_pooled_grad_losers  pooled push: k_row_grad_losers with rows weight * bag_grads[bag]
 //   k_row_pooled_apply        pooled push: k_row_apply with the winner's row formed the same way
+//   k_row_pooled_group_grad_losers  grouped pooled push: k_row_pooled_grad_losers over a launch group of batches
+//   k_row_pooled_group_apply        grouped pooled push: k_row_pooled_apply over a launch group of batches
 //   k_row_pooled      pooled pull: out[b] = sum over bag b's keys of weight * row(key)
 //   k_row_pooled_chunks  pooled pull: the chunks of bags longer than kPoolChunk, into partial rows
 //
@@ -543,6 +545,172 @@ __global__ __launch_bounds__(kBlock) void k_row_pooled_apply(PoolPushArgs a, Den
   }
 }
 
+// --------------------------------------------------- grouped pooled pushes
+// pskv_apply_pooled_grouped: the two kernels above over a
+// launch group of pooled batches.  A virtual workgroup of kGeneralChunk
+// positions belongs to ONE batch (the wg_prefix search); its bags are looked
+// up in that batch's offsets, its span ends at that batch's last position, and
+// its tags carry the keys of the batches before it: the index K4a stamped when
+// given the same batches as a GroupArgs.  WEIGHTED: some batch of the group
+// has weights; one without them (uniform over the workgroup) adds its bag
+// rows unmultiplied.
+
+// A wave-uniform value held in vector registers from here on (PIN), or left
+// to the compiler.
+template <bool PIN, typename X>
+__device__ __forceinline__ X in_vgprs(X x) {
+  if constexpr (PIN) asm("" : "+v"(x));
+  return x;
+}
+
+// push_bags for batch `a` of a group.
+__device__ __forceinline__ void group_push_bags(const PoolBatchDesc& a, uint64_t base, PoolSpan& sp, bool& have,
+                                                const RowStep& s, const bool (&want)[kRowsInFlight],
+                                                uint64_t (&bag)[kRowsInFlight]) {
+  if (!have) {
+    const uint64_t end = base + kGeneralChunk < a.n ? base + kGeneralChunk : a.n;  // base < n of THIS batch
+    sp = pool_bag_span(a.offsets, a.nbags, base, end - 1);
+    have = true;
+  }
+  pool_bags_in<kRowsInFlight>(a.offsets, sp, s.i, want, bag);
+}
+
+template <typename AT, bool WEIGHTED>
+__global__ __launch_bounds__(kBlock) void k_row_pooled_group_grad_losers(PoolGroupArgs ga, DenseView d,
+                                                                         AT* __restrict__ gsum,
+                                                                         const unsigned long long* __restrict__ owner,
+                                                                         uint32_t* err, uint32_t epoch, RowShape rs) {
+  const uint32_t lane = threadIdx.x & (rs.lanes - 1u);
+  const uint32_t grp = threadIdx.x >> rs.lshift;
+  const uint32_t G = (uint32_t)kBlock >> rs.lshift;
+  const uint32_t U = rs.units;
+  const uint32_t nvwg = ga.wg_prefix[ga.nb];
+  for (uint32_t wg = blockIdx.x; wg < nvwg; wg += gridDim.x) {
+    const int j = pool_group_batch_of(ga, wg);
+    const PoolBatchDesc& a = ga.b[j];
+    const AT* __restrict__ weights = reinterpret_cast<const AT*>(a.weights);
+    const AT* __restrict__ bg = reinterpret_cast<const AT*>(a.bag_grads);
+    const bool mul = WEIGHTED && weights != nullptr;
+    const uint64_t base = (uint64_t)(wg - ga.wg_prefix[j]) * kGeneralChunk;
+    const uint64_t gbase = pool_group_elem_prefix(ga, j) + base;
+    PoolSpan sp{0, 0};
+    bool have = false;
+    for (uint32_t r0 = grp; r0 < (uint32_t)kGeneralChunk; r0 += kRowsInFlight * G) {
+      if (base + r0 >= a.n) break;
+      RowStep s;
+      load_step(s, a.keys, a.n, base, r0, G, d);
+      bool lose[kRowsInFlight];
+      bool any = false;
+#pragma unroll
+      for (int r = 0; r < kRowsInFlight; ++r) {
+        const unsigned long long tag = row_tag(epoch, gbase + r0 + (uint32_t)r * G);
+        lose[r] = s.in[r] && owner[s.off[r]] != tag;
+        any |= lose[r];
+        if (s.live[r] && !s.in[r] && lane == 0) atomicOr(err, kErrRowOutOfRange);
+      }
+      if (!any) continue;  // distinct keys: only keys and stamps were read
+      uint64_t bag[kRowsInFlight];
+      group_push_bags(a, base, sp, have, s, lose, bag);
+      AT w[kRowsInFlight];
+#pragma unroll
+      for (int r = 0; r < kRowsInFlight; ++r) w[r] = (mul && lose[r]) ? weights[s.i[r]] : AT(1);
+      for (uint32_t u = lane; u < U; u += rs.lanes) {
+        AT v[kRowsInFlight];
+#pragma unroll
+        for (int r = 0; r < kRowsInFlight; ++r) v[r] = lose[r] ? bg[bag[r] * U + u] : AT(0);
+#pragma unroll
+        for (int r = 0; r < kRowsInFlight; ++r)
+          if (lose[r]) (void)atomicAdd(gsum + (uint64_t)s.off[r] * U + u, mul ? rounded_mul(w[r], v[r]) : v[r]);
+      }
+    }
+  }
+}
+
+template <typename T, int KIND, int V, bool WEIGHTED>
+__global__ __launch_bounds__(kBlock) void k_row_pooled_group_apply(PoolGroupArgs ga, DenseView d,
+                                                                   T* __restrict__ gsum, T* __restrict__ state,
+                                                                   T* __restrict__ state2,
+                                                                   const unsigned long long* __restrict__ owner,
+                                                                   uint32_t epoch, RowShape rs, OptArgs<T> o) {
+  const uint32_t lane = threadIdx.x & (rs.lanes - 1u);
+  const uint32_t grp = threadIdx.x >> rs.lshift;
+  const uint32_t G = (uint32_t)kBlock >> rs.lshift;
+  const uint32_t U = rs.units;
+  T* __restrict__ param = reinterpret_cast<T*>(d.param);
+  const uint32_t nvwg = ga.wg_prefix[ga.nb];
+  for (uint32_t wg = blockIdx.x; wg < nvwg; wg += gridDim.x) {
+    const int j = pool_group_batch_of(ga, wg);
+    // The descriptor's fields come from a computed place in the kernel
+    // arguments, so unlike the single-batch kernel's they cannot be loaded
+    // again where they are used, and held in scalar registers across the unit
+    // loop they would be spilled (Adam: up to 13 of them).
+    // Where that happens -- every kind with state, but for float rows taken
+    // one element at a time -- what only the per-lane arithmetic in front of
+    // the unit loop reads is kept in vector registers instead.
+    constexpr bool kPin = KIND >= 2 && (V > 1 || sizeof(T) > 4);
+    const uint32_t* keys = in_vgprs<kPin>(ga.b[j].keys);
+    const T* weights = reinterpret_cast<const T*>(ga.b[j].weights);
+    const uint64_t* offsets = in_vgprs<kPin>(ga.b[j].offsets);
+    const T* __restrict__ bg = reinterpret_cast<const T*>(ga.b[j].bag_grads);
+    const uint64_t n = ga.b[j].n;
+    const uint64_t base = (uint64_t)(wg - ga.wg_prefix[j]) * kGeneralChunk;
+    // the tag of the workgroup's first position; a group holds fewer than 2^32
+    // keys, so adding a position's offset never carries into the epoch
+    const unsigned long long tag0 = in_vgprs<kPin>(row_tag(epoch, pool_group_elem_prefix(ga, j) + base));
+    // nearly every workgroup holds a winner: the span is looked up at once
+    const uint64_t end = base + kGeneralChunk < n ? base + kGeneralChunk : n;  // base < n of THIS batch
+    PoolSpan sp = pool_bag_span(ga.b[j].offsets, ga.b[j].nbags, base, end - 1);
+    sp.lo = in_vgprs<kPin>(sp.lo);
+    sp.hi = in_vgprs<kPin>(sp.hi);
+    for (uint32_t r0 = grp; r0 < (uint32_t)kGeneralChunk; r0 += kRowsInFlight * G) {
+      if (base + r0 >= n) break;
+      RowStep s;
+      load_step(s, keys, n, base, r0, G, d);
+      bool win[kRowsInFlight];
+      bool any = false;
+#pragma unroll
+      for (int r = 0; r < kRowsInFlight; ++r) {
+        const unsigned long long tag = tag0 + (r0 + (uint32_t)r * G);
+        win[r] = s.in[r] && owner[s.off[r]] == tag;
+        any |= win[r];
+      }
+      if (!any) continue;
+      uint64_t bag[kRowsInFlight];
+      pool_bags_in<kRowsInFlight>(offsets, sp, s.i, win, bag);
+      T w[kRowsInFlight];
+#pragma unroll
+      for (int r = 0; r < kRowsInFlight; ++r) w[r] = (WEIGHTED && weights && win[r]) ? weights[s.i[r]] : T(1);
+      for (uint32_t u = lane; u < U; u += rs.lanes) {
+        OptUnit<T, V> g[kRowsInFlight], gs[kRowsInFlight], p[kRowsInFlight], h[kRowsInFlight], h2[kRowsInFlight];
+#pragma unroll
+        for (int r = 0; r < kRowsInFlight; ++r) {
+          if (!win[r]) continue;
+          const uint64_t at = (uint64_t)s.off[r] * U + u;
+          g[r] = load_opt_unit<T, V>(bg, bag[r] * U + u);
+          gs[r] = load_opt_unit<T, V>(gsum, at);
+          p[r] = load_opt_unit<T, V>(param, at);
+          if (KIND >= 2) h[r] = load_opt_unit<T, V>(state, at);
+          if (KIND == 4) h2[r] = load_opt_unit<T, V>(state2, at);
+        }
+#pragma unroll
+        for (int r = 0; r < kRowsInFlight; ++r) {
+          if (!win[r]) continue;
+          const uint64_t at = (uint64_t)s.off[r] * U + u;
+          if (WEIGHTED) {  // (a batch without weights: times one, exact)
+#pragma unroll
+            for (int i = 0; i < V; ++i) g[r].e[i] = rounded_mul(w[r], g[r].e[i]);
+          }
+          const bool dirty = opt_step_unit<T, KIND, V>(g[r], gs[r], p[r], h[r], h2[r], o);
+          store_opt_unit<T, V>(param, at, p[r]);
+          if (KIND >= 2) store_opt_unit<T, V>(state, at, h[r]);
+          if (KIND == 4) store_opt_unit<T, V>(state2, at, h2[r]);
+          if (dirty) store_opt_unit<T, V>(gsum, at, gs[r]);
+        }
+      }
+    }
+  }
+}
+
 template <typename T>
 __global__ __launch_bounds__(kBlock) void k_fill(T* __restrict__ p, uint64_t n, T v) {
   for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) p[i] = v;
@@ -609,6 +777,23 @@ void launch_row_pooled_apply_kind(int kind, uint32_t grid, const PoolPushArgs& a
     k_row_pooled_apply<T, 2, V, WEIGHTED><<<grid, kBlock, 0, st>>>(a, d, g, s1, s2, owner, epoch, rs, o);
   else
     k_row_pooled_apply<T, 1, V, WEIGHTED><<<grid, kBlock, 0, st>>>(a, d, g, s1, s2, owner, epoch, rs, o);
+}
+
+template <typename T, int V, bool WEIGHTED>
+void launch_row_pooled_group_apply_kind(int kind, uint32_t grid, const PoolGroupArgs& ga, const DenseView& d,
+                                        void* gsum, void* const state[2], const unsigned long long* owner,
+                                        uint32_t epoch, const RowShape& rs, const OptArgs<T>& o, hipStream_t st) {
+  T* g = static_cast<T*>(gsum);
+  T* s1 = static_cast<T*>(state[0]);
+  T* s2 = static_cast<T*>(state[1]);
+  if (kind == 4)
+    k_row_pooled_group_apply<T, 4, V, WEIGHTED><<<grid, kBlock, 0, st>>>(ga, d, g, s1, s2, owner, epoch, rs, o);
+  else if (kind == 3)
+    k_row_pooled_group_apply<T, 3, V, WEIGHTED><<<grid, kBlock, 0, st>>>(ga, d, g, s1, s2, owner, epoch, rs, o);
+  else if (kind == 2)
+    k_row_pooled_group_apply<T, 2, V, WEIGHTED><<<grid, kBlock, 0, st>>>(ga, d, g, s1, s2, owner, epoch, rs, o);
+  else
+    k_row_pooled_group_apply<T, 1, V, WEIGHTED><<<grid, kBlock, 0, st>>>(ga, d, g, s1, s2, owner, epoch, rs, o);
 }
 
 // ----------------------------------------------------------- pooled pulls
@@ -961,6 +1146,62 @@ hipError_t launch_row_pooled_apply(int dtype, int kind, const PoolPushArgs& a, c
         launch_row_pooled_apply_kind<T, 1, true>(kind, grid, a, d, gsum, state, owner, epoch, rs, o, st);
       else
         launch_row_pooled_apply_kind<T, 1, false>(kind, grid, a, d, gsum, state, owner, epoch, rs, o, st);
+    }
+  });
+}
+
+// A launch group of pooled batches as the kernels assume it: 1 to
+// kMaxPoolBatches batches, each of 1 to kMaxPiece keys and at least one bag,
+// nwg the group's virtual workgroups.
+static bool pool_group_ok(const PoolGroupArgs& ga, uint32_t nwg) {
+  if (ga.nb < 1 || ga.nb > kMaxPoolBatches || ga.wg_prefix[ga.nb] != nwg) return false;
+  for (int j = 0; j < ga.nb; ++j)
+    if (ga.b[j].n == 0 || ga.b[j].n > kMaxPiece || ga.b[j].nbags == 0 ||
+        ga.wg_prefix[j + 1] - ga.wg_prefix[j] != (ga.b[j].n + kGeneralChunk - 1) / kGeneralChunk)
+      return false;
+  return true;
+}
+
+hipError_t launch_row_pooled_group_grad_losers(int dtype, const PoolGroupArgs& ga, uint32_t nwg, bool weighted,
+                                               const DenseView& d, void* gsum, const unsigned long long* owner,
+                                               const Ovf& o, uint32_t epoch, const RowShape& rs, hipStream_t st) {
+  if (nwg == 0) return hipSuccess;
+  if (!pool_group_ok(ga, nwg)) return hipErrorInvalidValue;
+  const uint32_t grid = row_grid(nwg);
+  uint32_t* err = &o.c->stat[1];
+  return with_float_type(dtype, [&](auto z) {
+    using T = decltype(z);
+    if (weighted)
+      k_row_pooled_group_grad_losers<T, true>
+          <<<grid, kBlock, 0, st>>>(ga, d, static_cast<T*>(gsum), owner, err, epoch, rs);
+    else
+      k_row_pooled_group_grad_losers<T, false>
+          <<<grid, kBlock, 0, st>>>(ga, d, static_cast<T*>(gsum), owner, err, epoch, rs);
+  });
+}
+
+hipError_t launch_row_pooled_group_apply(int dtype, int kind, const PoolGroupArgs& ga, uint32_t nwg, bool weighted,
+                                         const DenseView& d, void* gsum, void* const state[2],
+                                         const unsigned long long* owner, uint32_t epoch, const RowShape& rs,
+                                         const OptArgs<double>& hy, hipStream_t st) {
+  if (nwg == 0) return hipSuccess;
+  if (!pool_group_ok(ga, nwg)) return hipErrorInvalidValue;
+  if (kind < 1 || kind > 4 || (kind >= 2 && !state[0]) || (kind == 4 && !state[1])) return hipErrorInvalidValue;
+  const uint32_t grid = row_grid(nwg);
+  return with_float_type(dtype, [&](auto z) {
+    using T = decltype(z);
+    const OptArgs<T> o = round_opt_args<T>(hy);
+    constexpr int V16 = 16 / sizeof(T);
+    if (rs.unit_bytes == 16) {
+      if (weighted)
+        launch_row_pooled_group_apply_kind<T, V16, true>(kind, grid, ga, d, gsum, state, owner, epoch, rs, o, st);
+      else
+        launch_row_pooled_group_apply_kind<T, V16, false>(kind, grid, ga, d, gsum, state, owner, epoch, rs, o, st);
+    } else {
+      if (weighted)
+        launch_row_pooled_group_apply_kind<T, 1, true>(kind, grid, ga, d, gsum, state, owner, epoch, rs, o, st);
+      else
+        launch_row_pooled_group_apply_kind<T, 1, false>(kind, grid, ga, d, gsum, state, owner, epoch, rs, o, st);
     }
   });
 }

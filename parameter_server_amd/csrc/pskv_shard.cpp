@@ -2023,6 +2023,107 @@ int apply_pooled_impl(pskv_shard* s, const PoolPush& call, int flags) {
                                          call.nbags, d + ro});
 }
 
+// --------------------------------------------------- grouped pooled pushes
+// pskv_apply_pooled_grouped (pskv.h "Grouped pooled pushes"):
+// the pooled pushes of several workers as ONE step.  The live batches are cut
+// into G launch groups (pool_split_groups); as apply_device, all marks first,
+// then all loser passes, then all apply passes, one epoch per group and one
+// step number for the call:
+//   G x K4a (stamp mode, over the groups' keys)   the winner position of each key
+//   G x k_row_pooled_group_grad_losers            every other position's row -> gsum
+//   G x k_row_pooled_group_apply                  each winner steps its key's row
+// `v`: live batches where the kernels read them.
+int apply_pooled_grouped_device(pskv_shard* s, const std::vector<pskv_pool_batch>& v) {
+  if (int rc = ensure_owner(s)) return rc;
+  const std::vector<pskv_batch> marks = pool_mark_batches(v);
+  // 16-byte units for the whole call or for none of it
+  const bool vec = rows_unit16(s, {s->dense, s->opt_gsum, s->opt_slot[0], s->opt_slot[1]}, marks);
+  const std::vector<Span> spans = pool_split_groups(v);
+  struct PoolLaunch {
+    LaunchGroup mark;
+    PoolGroupArgs ga;
+    uint32_t nwg;
+    bool weighted;
+    uint32_t epoch;
+  };
+  std::vector<PoolLaunch> groups(spans.size());
+  uint64_t elems = 0;
+  // the call's epochs must not straddle a wrap-around (apply_device)
+  if (0xFFFFFFFFu - s->epoch < spans.size()) s->epoch = 0xFFFFFFFFu;
+  for (size_t i = 0; i < spans.size(); ++i) {
+    PoolLaunch& g = groups[i];
+    g.mark = make_group(marks, spans[i].first, spans[i].second, kGeneralChunk);
+    uint64_t el = 0;
+    g.ga = make_pool_group(v, spans[i].first, spans[i].second, kGeneralChunk, &g.nwg, &el);
+    g.weighted = false;
+    for (size_t j = spans[i].first; j < spans[i].second; ++j) g.weighted |= v[j].weights != nullptr;
+    g.epoch = next_epoch(s);
+    elems += el;
+  }
+  const OptArgs<double> hy = opt_args(s->opt, ++s->opt_step);
+  const RowShape rs1 = row_shape(s->width, s->vb, false);
+  const RowShape rsv = row_shape(s->width, s->vb, vec);
+  LaunchTimer t(s, kTimeApply, elems);
+  t.count = groups.size();
+  for (const PoolLaunch& g : groups)
+    PSKV_HIP(launch_general_mark(s->dtype, PSKV_ASSIGN, g.mark.ga, g.mark.nwg, s->dview(), s->flag + 1, s->owner,
+                                 nullptr, g.epoch, s->stream));
+  for (const PoolLaunch& g : groups)
+    PSKV_HIP(launch_row_pooled_group_grad_losers(s->dtype, g.ga, g.nwg, g.weighted, s->dview(), s->opt_gsum, s->owner,
+                                                 s->ovf, g.epoch, rs1, s->stream));
+  for (const PoolLaunch& g : groups)
+    PSKV_HIP(launch_row_pooled_group_apply(s->dtype, s->opt.kind, g.ga, g.nwg, g.weighted, s->dview(), s->opt_gsum,
+                                           s->opt_slot, s->owner, g.epoch, rsv, hy, s->stream));
+  t.done();
+  s->n_general += 3 * groups.size();
+  return PSKV_OK;
+}
+
+// The arguments hold (pskv_apply_pooled_grouped checked every batch, a host
+// call's offsets included).
+int apply_pooled_grouped_impl(pskv_shard* s, const pskv_pool_batch* batches, uint64_t nb, int flags) {
+  if (s->dtype != PSKV_F32 && s->dtype != PSKV_F64)
+    return fail(PSKV_EINVAL, "pskv_apply_pooled_grouped: float shards only (an int32 shard takes no optimizer step)");
+  if (s->opt.kind == PSKV_OPT_NONE)
+    return fail(PSKV_EINVAL, "pskv_apply_pooled_grouped: the shard has no optimizer (pskv_shard_set_optimizer)");
+  std::vector<uint64_t> index;
+  const std::vector<pskv_pool_batch> live = pool_live_batches(batches, nb, &index);
+  if (live.empty()) return PSKV_OK;  // no batch with a key and a bag: no step
+  int rc = use_device(s);
+  if (rc || (rc = srv_stop(s))) return rc;
+  if (flags & PSKV_DEVICE) return apply_pooled_grouped_device(s, live);
+  for (size_t i = 0; i < live.size(); ++i) {
+    const std::vector<pskv_batch> one{pskv_batch{live[i].keys, const_cast<void*>(live[i].bag_grads), live[i].n}};
+    if (const uint32_t* k = first_key_outside(one, s->key_begin, s->range))
+      return fail(PSKV_EINVAL, "pskv_apply_pooled_grouped: batch " + std::to_string(index[i]) + ": key " +
+                                   std::to_string(*k) +
+                                   " is outside [key_begin, key_end); an optimizer step takes no out-of-range keys "
+                                   "(nothing was applied)");
+  }
+  // host buffers: one staging block, every live batch's keys, weights, offsets
+  // and bag rows (pool_stage_layout), apply_pooled_impl's path
+  const size_t rb = row_bytes(s);
+  const PoolStageLayout lay = pool_stage_layout(live, (size_t)s->vb, rb);
+  HstageHold hold(s);  // the call returns before its DMA: the hold stays armed
+  if ((rc = ensure_hstage(s, lay.total)) || (rc = ensure_dstage(s, lay.total))) return rc;
+  char* h = static_cast<char*>(s->hstage);
+  char* d = static_cast<char*>(s->dstage);
+  std::vector<Piece> pieces;
+  std::vector<pskv_pool_batch> dv(live.size());
+  for (size_t i = 0; i < live.size(); ++i) {
+    const pskv_pool_batch& b = live[i];
+    const PoolStageSlot& at = lay.at[i];
+    add_pieces(pieces, b.keys, h + at.keys, b.n * 4, -1);
+    if (b.weights) add_pieces(pieces, b.weights, h + at.weights, b.n * (size_t)s->vb, -1);
+    add_pieces(pieces, b.offsets, h + at.offsets, (b.nbags + 1) * sizeof(uint64_t), -1);
+    add_pieces(pieces, b.bag_grads, h + at.rows, b.nbags * rb, -1);
+    dv[i] = pskv_pool_batch{reinterpret_cast<const uint32_t*>(d + at.keys), b.weights ? d + at.weights : nullptr,
+                            reinterpret_cast<const uint64_t*>(d + at.offsets), d + at.rows, b.n, b.nbags};
+  }
+  if ((rc = pipelined_h2d(s, pieces, h, d, hold))) return rc;
+  return apply_pooled_grouped_device(s, dv);
+}
+
 // What is wrong with a configuration, or null (checked before any handle;
 // fields a kind does not use are ignored).  legacy: the configuration was
 // widened from a pskv_optimizer, which has no size and only the first kinds.
@@ -2884,6 +2985,30 @@ int pskv_apply_pooled(pskv_shard* s, const uint32_t* keys, uint64_t n, const voi
   }
   if (!s) return fail(PSKV_EINVAL, "pskv_apply_pooled: null shard");
   return apply_pooled_impl(s, PoolPush{keys, n, weights, offsets, nbags, bag_grads}, flags);
+}
+
+// Every batch gets pskv_apply_pooled's checks, before the handle is looked at;
+// a failure names the batch.
+int pskv_apply_pooled_grouped(pskv_shard* s, const pskv_pool_batch* batches, uint64_t nb, int flags) {
+  if (bad_flags(flags)) return fail(PSKV_EINVAL, "pskv_apply_pooled_grouped: unknown flags");
+  if (nb && !batches) return fail(PSKV_EINVAL, "pskv_apply_pooled_grouped: null batches with nb > 0");
+  for (uint64_t i = 0; i < nb; ++i) {
+    const pskv_pool_batch& b = batches[i];
+    const std::string who = "pskv_apply_pooled_grouped: batch " + std::to_string(i) + ": ";
+    if (b.n && !b.keys) return fail(PSKV_EINVAL, who + "null keys with n > 0");
+    if (b.nbags && !b.offsets) return fail(PSKV_EINVAL, who + "null offsets with nbags > 0");
+    if (b.nbags && !b.bag_grads) return fail(PSKV_EINVAL, who + "null bag_grads with nbags > 0");
+    if (b.n > kMaxPiece)
+      return fail(PSKV_EINVAL, who + "n = " + std::to_string(b.n) + " exceeds 2^31 keys (a batch lies in one launch group)");
+    if (!(flags & PSKV_DEVICE)) {
+      uint64_t bad = 0;
+      if (const char* why = pool_offsets_error(b.offsets, b.nbags, b.n, &bad))
+        return fail(PSKV_EINVAL, who + "offsets: bag " + std::to_string(bad) + ": " + why + " (n = " +
+                                     std::to_string(b.n) + ", nbags = " + std::to_string(b.nbags) + ")");
+    }
+  }
+  if (!s) return fail(PSKV_EINVAL, "pskv_apply_pooled_grouped: null shard");
+  return apply_pooled_grouped_impl(s, batches, nb, flags);
 }
 
 // The three state entry points: a row Get from, or (put) a row assign Add

@@ -293,6 +293,44 @@ class Shard:
         bs = batches if isinstance(batches, BatchSet) else self.prepare(batches)
         check(lib.pskv_apply_grouped(self._h, bs.arr, bs.n, bs.flags))
 
+    def _pooled_push_batch(self, who, keys, offsets, bag_grads, weights):
+        """The checks of one pooled push's four arrays (`who` opens the
+        messages).  Returns (keys, weights, offsets, bag_grads pointers, n,
+        nbags), the call's flags and the host arrays behind the pointers, which
+        the caller keeps until its call has returned."""
+        if _is_torch(keys):
+            import torch
+
+            if offsets.dtype != torch.int64 or offsets.numel() < 1:
+                raise ValueError(f"{who}: device offsets must be an int64 tensor of nbags + 1 values")
+            nbags = offsets.numel() - 1
+            tdt = _torch_dtype(self.dtype)
+            ts = [keys, offsets, bag_grads]
+            if weights is not None:
+                if weights.dtype != tdt or weights.numel() != keys.numel():
+                    raise ValueError(f"{who}: weights must hold one value of the shard's dtype per key")
+                ts.append(weights)
+            if bag_grads.dtype != tdt or bag_grads.numel() != nbags * self.width:
+                raise ValueError(f"{who}: bag_grads must hold nbags * width values of the shard's dtype")
+            self._check_dev(*ts)
+            return ((keys.data_ptr(), weights.data_ptr() if weights is not None else None, offsets.data_ptr(),
+                     bag_grads.data_ptr(), keys.numel(), nbags), _lib.PSKV_DEVICE, None)
+        k = self._host_keys(keys)
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        if off.size < 1:
+            raise ValueError(f"{who}: offsets must hold nbags + 1 values")
+        nbags = off.size - 1
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=self.dtype)
+            if w.size != k.size:
+                raise ValueError(f"{who}: {w.size} weights for {k.size} keys")
+        g = np.ascontiguousarray(bag_grads, dtype=self.dtype)
+        if g.size != nbags * self.width:
+            raise ValueError(f"{who}: {g.size} bag gradient values for {nbags} bags of width {self.width}")
+        return ((k.ctypes.data, w.ctypes.data if w is not None else None, off.ctypes.data, g.ctypes.data, k.size,
+                 nbags), _lib.PSKV_HOST, (k, off, w, g))
+
     def apply_pooled(self, keys, offsets, bag_grads, weights=None):
         """One optimizer step from one gradient row per bag (pskv_apply_pooled):
         the gradient row of keys[i] is weights[i] * bag_grads[b], b the bag with
@@ -300,40 +338,34 @@ class Shard:
         Arguments as get_pooled's, with bag_grads (nbags * width values) in the
         place of its output.  numpy -> host path; torch tensors -> device path
         (offsets an int64 tensor), stream-ordered."""
-        if _is_torch(keys):
-            import torch
+        (pk, pw, po, pg, n, nbags), flags, keep = self._pooled_push_batch("apply_pooled", keys, offsets, bag_grads,
+                                                                          weights)
+        check(lib.pskv_apply_pooled(self._h, pk, n, pw, po, nbags, pg, flags))
+        del keep
 
-            if offsets.dtype != torch.int64 or offsets.numel() < 1:
-                raise ValueError("apply_pooled: device offsets must be an int64 tensor of nbags + 1 values")
-            nbags = offsets.numel() - 1
-            tdt = _torch_dtype(self.dtype)
-            ts = [keys, offsets, bag_grads]
-            if weights is not None:
-                if weights.dtype != tdt or weights.numel() != keys.numel():
-                    raise ValueError("apply_pooled: weights must hold one value of the shard's dtype per key")
-                ts.append(weights)
-            if bag_grads.dtype != tdt or bag_grads.numel() != nbags * self.width:
-                raise ValueError("apply_pooled: bag_grads must hold nbags * width values of the shard's dtype")
-            self._check_dev(*ts)
-            check(lib.pskv_apply_pooled(self._h, keys.data_ptr(), keys.numel(),
-                                        weights.data_ptr() if weights is not None else None, offsets.data_ptr(),
-                                        nbags, bag_grads.data_ptr(), _lib.PSKV_DEVICE))
-            return
-        k = self._host_keys(keys)
-        off = np.ascontiguousarray(offsets, dtype=np.uint64)
-        if off.size < 1:
-            raise ValueError("apply_pooled: offsets must hold nbags + 1 values")
-        nbags = off.size - 1
-        w = None
-        if weights is not None:
-            w = np.ascontiguousarray(weights, dtype=self.dtype)
-            if w.size != k.size:
-                raise ValueError(f"apply_pooled: {w.size} weights for {k.size} keys")
-        g = np.ascontiguousarray(bag_grads, dtype=self.dtype)
-        if g.size != nbags * self.width:
-            raise ValueError(f"apply_pooled: {g.size} bag gradient values for {nbags} bags of width {self.width}")
-        check(lib.pskv_apply_pooled(self._h, k.ctypes.data, k.size, w.ctypes.data if w is not None else None,
-                                    off.ctypes.data, nbags, g.ctypes.data, _lib.PSKV_HOST))
+    def apply_pooled_grouped(self, batches):
+        """ONE optimizer step from several pooled pushes (pskv_apply_pooled_grouped):
+        `batches` is a list of (keys, offsets, bag_grads) or (keys, offsets,
+        bag_grads, weights), each shaped as apply_pooled's arguments; the step
+        is the one apply_pooled would make of their concatenation.  All numpy
+        -> host path; all torch tensors on the shard's device -> device path."""
+        batches = [tuple(b) for b in batches]
+        for b in batches:
+            if len(b) not in (3, 4):
+                raise ValueError("apply_pooled_grouped: a batch is (keys, offsets, bag_grads[, weights])")
+        dev = [_is_torch(b[0]) for b in batches]
+        if any(dev) and not all(dev):
+            raise ValueError("apply_pooled_grouped: the batches must all be device or all host batches")
+        arr = (_lib.PskvPoolBatch * max(len(batches), 1))()
+        keep = []  # the host arrays behind the pointers, alive until the call returns
+        flags = _lib.PSKV_HOST
+        for i, b in enumerate(batches):
+            (pk, pw, po, pg, n, nbags), flags, held = self._pooled_push_batch(
+                f"apply_pooled_grouped: batch {i}", b[0], b[1], b[2], b[3] if len(b) == 4 else None)
+            keep.append(held)
+            arr[i] = _lib.PskvPoolBatch(pk, pw, po, pg, n, nbags)
+        check(lib.pskv_apply_pooled_grouped(self._h, arr, len(batches), flags))
+        del keep
 
     def get_state(self, keys, out=None, slot: int = 0):
         """The rows of `keys` in state slot `slot` (pskv_get_state_slot; Adagrad

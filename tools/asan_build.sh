@@ -44,4 +44,10 @@ done
 $CXX -O1 -g -std=c++17 -Wall -Werror -fsanitize=$SAN $NORECOVER -fno-omit-frame-pointer \
   -I "$R/include" -I "$R/parameter_server_amd/csrc" "$R/tests/cpp/host_plan_test.cpp" -o "$O/host_plan_test"
 "$O/host_plan_test"
+# the grouped pooled push's planner (tests/cpp/pooled_push_group_plan_test.cpp): host-only too; the
+# loop above built it as build.py does, this is the strict stand-alone form, run here
+$CXX -O1 -g -std=c++17 -Wall -Werror -fsanitize=$SAN $NORECOVER -fno-omit-frame-pointer \
+  -I "$R/include" -I "$R/parameter_server_amd/csrc" "$R/tests/cpp/pooled_push_group_plan_test.cpp" \
+  -o "$O/pooled_push_group_plan_test_alone"
+"$O/pooled_push_group_plan_test_alone"
 echo "asan build: $O"
