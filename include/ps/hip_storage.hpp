@@ -27,7 +27,8 @@
 // (pskv.h), so construct it with the range the server owns.
 // Optimizer (last constructor argument, pskv_shard_set_optimizer; a
 // pskv_optimizer_ex there, pskv_shard_set_optimizer_ex, also gives momentum
-// and Adam): the storage applies optimizer steps.  SubAdd then carries GRADIENTS and is one step
+// and Adam; a pskv_optimizer_cfg, pskv_shard_set_optimizer_cfg, also
+// FTRL-Proximal): the storage applies optimizer steps.  SubAdd then carries GRADIENTS and is one step
 // (pskv_apply); AddGrouped, the BSP model's flush, is ONE step over the summed
 // gradients of all its messages (pskv_apply_grouped).  Float Val only; keys
 // outside the range abort the call (pskv.h "Optimizer steps").
@@ -96,6 +97,13 @@ class HipStorage : public AbstractStorage {
       : width_(width), stepping_(optimizer != nullptr && optimizer->kind != PSKV_OPT_NONE) {
     Create(device, key_begin, key_end, mode, overflow_slots);
     if (optimizer) pskv_check(pskv_shard_set_optimizer_ex(shard_, optimizer), "pskv_shard_set_optimizer_ex");
+  }
+  // The same with the configuration that also holds FTRL-Proximal (l1, l2, ftrl_beta).
+  HipStorage(int device, uint32_t key_begin, uint64_t key_end, int mode, uint64_t overflow_slots, uint32_t width,
+             const pskv_optimizer_cfg* optimizer)
+      : width_(width), stepping_(optimizer != nullptr && optimizer->kind != PSKV_OPT_NONE) {
+    Create(device, key_begin, key_end, mode, overflow_slots);
+    if (optimizer) pskv_check(pskv_shard_set_optimizer_cfg(shard_, optimizer), "pskv_shard_set_optimizer_cfg");
   }
   ~HipStorage() override { pskv_shard_destroy(shard_); }
   HipStorage(const HipStorage&) = delete;

@@ -124,10 +124,37 @@
  * resets t to 0 and the state to its start values.  pskv_set_step lets a
  * restored shard continue where the saved one stopped.
  * State slots (pskv_get_state_slot, pskv_put_state): SGD has none, Adagrad one
- * (h), momentum one (v), Adam two (m, v).  Saving p and every slot of the
- * whole range with the step count, and putting them back with pskv_add,
- * pskv_put_state and pskv_set_step, restores a shard bit for bit.
+ * (h), momentum one (v), Adam two (m, v), FTRL two (z, n).  Saving p and
+ * every slot of the whole range with the step count, and putting them back
+ * with pskv_add, pskv_put_state and pskv_set_step, restores a shard bit for bit.
  * Not provided: decoupled weight decay (AdamW), amsgrad, per-key step counts.
+ *
+ * FTRL-Proximal (pskv_shard_set_optimizer_cfg, PSKV_OPT_FTRL):
+ * the per-coordinate rule of McMahan et al., "Ad Click Prediction: a View
+ * from the Trenches" (2013), whose L1 threshold leaves most weights of a
+ * sparse model EXACTLY zero.  Steps 1 and 3 of "Optimizer steps" are
+ * unchanged.  Slot 0 is z, starting at 0; slot 1 is n, starting at
+ * init_accum.  Everything is computed in T, every hyper-parameter rounded to
+ * T once per launch; inv_lr = 1 / lr is computed on the host in double:
+ *     d  = g + weight_decay * p
+ *     n' = n + d * d
+ *     r  = sqrt(n')                        (computed once, used twice)
+ *     s  = (r - sqrt(n)) * inv_lr
+ *     z' = (z + d) - s * p
+ *     p' = +0                                                 if |z'| <= l1
+ *          (copysign(l1, z') - z') / ((ftrl_beta + r) * inv_lr + l2)   otherwise
+ *   - the zero is +0 (bit pattern 0), never -0;
+ *   - FTRL OWNS p: a step overwrites p with the closed form of z' and n'.  A
+ *     p written by pskv_add enters the step only through s * p and the
+ *     weight-decay term and is then replaced; to start from given weights,
+ *     put the matching z with pskv_put_state;
+ *   - non-finite inputs, and a negative n written by pskv_put_state, propagate
+ *     by IEEE rules (sqrt of a negative n is a NaN); nothing checks for them;
+ *   - the step counter, pskv_clear (z to 0, n to init_accum, t to 0) and a kind
+ *     change follow the rules above; lazy as Adam: a key not in the call keeps
+ *     p, z and n bit for bit;
+ *   - not provided: lr_power other than -1/2, L2 shrinkage, per-key step
+ *     counts.
  *
  * Pooled pulls (pskv_get_pooled): one row per BAG of keys, a bag
  * being one sample's contiguous run of the call's keys (bag b = keys
@@ -450,7 +477,8 @@ enum pskv_optimizer_kind {
   PSKV_OPT_SGD = 1,
   PSKV_OPT_ADAGRAD = 2,
   PSKV_OPT_MOMENTUM = 3, /* only through pskv_shard_set_optimizer_ex */
-  PSKV_OPT_ADAM = 4      /* only through pskv_shard_set_optimizer_ex */
+  PSKV_OPT_ADAM = 4,     /* only through pskv_shard_set_optimizer_ex */
+  PSKV_OPT_FTRL = 5      /* only through pskv_shard_set_optimizer_cfg */
 };
 typedef struct pskv_optimizer {
   int kind;
@@ -508,13 +536,36 @@ int pskv_shard_set_optimizer_ex(pskv_shard* s, const pskv_optimizer_ex* cfg);
  * new kind fills the fields it has and reports the new kind number.) */
 int pskv_shard_get_optimizer_ex(pskv_shard* s, pskv_optimizer_ex* out, uint64_t* state_bytes);
 /* pskv_get_state with a slot number (slots per kind: SGD 0, Adagrad 1,
- * momentum 1, Adam 2); a slot the kind lacks is PSKV_EINVAL. */
+ * momentum 1, Adam 2, FTRL 2); a slot the kind lacks is PSKV_EINVAL. */
 int pskv_get_state_slot(pskv_shard* s, int slot, const uint32_t* keys, uint64_t n, void* out, int flags);
 /* Write state rows: a row shard's assign Add aimed at a state array (the last
  * occurrence of a key wins with its whole row; host and device paths as
  * pskv_add on a row shard, at any width, 1 included).  Keys outside the range
  * are refused as pskv_apply refuses them.  For restoring a checkpoint. */
 int pskv_put_state(pskv_shard* s, int slot, const uint32_t* keys, const void* vals, uint64_t n, int flags);
+/* The configuration that can grow: every kind, PSKV_OPT_FTRL included (rule:
+ * the header comment, "FTRL-Proximal").  The first 72 bytes are laid out
+ * exactly as pskv_optimizer_ex; fields a kind does not use are ignored. */
+typedef struct pskv_optimizer_cfg {
+  uint32_t size;        /* sizeof(pskv_optimizer_cfg); any other value is PSKV_EINVAL naming "size" */
+  int kind;             /* NONE, SGD, ADAGRAD, MOMENTUM, ADAM, FTRL */
+  double lr;            /* as pskv_optimizer */
+  double weight_decay;  /* as pskv_optimizer */
+  double eps;           /* ADAGRAD and ADAM: finite, > 0 */
+  double init_accum;    /* ADAGRAD and FTRL: finite, >= 0 */
+  double momentum;      /* MOMENTUM: finite, in [0, 1) */
+  int nesterov;         /* MOMENTUM: 0 or 1 */
+  double beta1, beta2;  /* ADAM: finite, in [0, 1) */
+  double l1, l2;        /* FTRL: finite, >= 0 */
+  double ftrl_beta;     /* FTRL: finite, >= 0 (the paper's beta; 1 is its usual value) */
+} pskv_optimizer_cfg;
+/* As pskv_shard_set_optimizer_ex (validated before the handle, a bad field
+ * named also for a null shard; the same kind again keeps the state and the step
+ * count, another kind resets both).  With kinds NONE to ADAM exactly
+ * pskv_shard_set_optimizer_ex.  The two older setters refuse PSKV_OPT_FTRL. */
+int pskv_shard_set_optimizer_cfg(pskv_shard* s, const pskv_optimizer_cfg* cfg);
+/* The older getters on an FTRL shard fill the fields they have and report kind 5. */
+int pskv_shard_get_optimizer_cfg(pskv_shard* s, pskv_optimizer_cfg* out, uint64_t* state_bytes);
 /* The step counter: the number of steps since creation, pskv_clear or a kind
  * change (the next step is t + 1). */
 int pskv_get_step(pskv_shard* s, uint64_t* t);

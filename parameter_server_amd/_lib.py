@@ -46,6 +46,7 @@ PSKV_TIME_APPLY = 1 << 14
 PSKV_TIME_POOLED = 1 << 15
 PSKV_OPT_NONE, PSKV_OPT_SGD, PSKV_OPT_ADAGRAD = 0, 1, 2
 PSKV_OPT_MOMENTUM, PSKV_OPT_ADAM = 3, 4  # only through pskv_shard_set_optimizer_ex
+PSKV_OPT_FTRL = 5  # only through pskv_shard_set_optimizer_cfg
 KERNEL_NAMES = {
     PSKV_K_GATHER: "k_gather",
     PSKV_K_ASSIGN_SORTED: "k_assign_sorted",
@@ -78,6 +79,7 @@ EXPORTED = [
     "pskv_get_step", "pskv_set_step",
     "pskv_get_pooled", "pskv_pooled_time",
     "pskv_apply_pooled", "pskv_apply_pooled_grouped",
+    "pskv_shard_set_optimizer_cfg", "pskv_shard_get_optimizer_cfg",
 ]
 
 
@@ -111,6 +113,12 @@ class PskvOptimizerEx(ctypes.Structure):
                 ("weight_decay", ctypes.c_double), ("eps", ctypes.c_double), ("init_accum", ctypes.c_double),
                 ("momentum", ctypes.c_double), ("nesterov", ctypes.c_int), ("beta1", ctypes.c_double),
                 ("beta2", ctypes.c_double)]
+
+
+class PskvOptimizerCfg(ctypes.Structure):
+    # the first 72 bytes are PskvOptimizerEx's
+    _fields_ = PskvOptimizerEx._fields_ + [("l1", ctypes.c_double), ("l2", ctypes.c_double),
+                                           ("ftrl_beta", ctypes.c_double)]
 
 
 class PskvError(RuntimeError):
@@ -175,6 +183,8 @@ def _load():
         "pskv_pooled_time": ([vp, ctypes.POINTER(u64), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(u64)], i32),
         "pskv_apply_pooled": ([vp, vp, u64, vp, vp, u64, vp, i32], i32),
         "pskv_apply_pooled_grouped": ([vp, ctypes.POINTER(PskvPoolBatch), u64, i32], i32),
+        "pskv_shard_set_optimizer_cfg": ([vp, ctypes.POINTER(PskvOptimizerCfg)], i32),
+        "pskv_shard_get_optimizer_cfg": ([vp, ctypes.POINTER(PskvOptimizerCfg), ctypes.POINTER(u64)], i32),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)

@@ -25,6 +25,7 @@ CPP_TESTS = {  # program -> (source in tests/cpp, links the oracle checker)
     "hip_storage_rows_test": ("hip_storage_rows_test.cpp", False),
     "hip_storage_opt_test": ("hip_storage_opt_test.cpp", False),
     "hip_storage_opt2_test": ("hip_storage_opt2_test.cpp", False),
+    "hip_storage_ftrl_test": ("hip_storage_ftrl_test.cpp", False),
     "hip_storage_pooled_test": ("hip_storage_pooled_test.cpp", False),
     "hip_storage_pooled_push_test": ("hip_storage_pooled_push_test.cpp", False),
     "hip_storage_pooled_push_group_test": ("hip_storage_pooled_push_group_test.cpp", False),

@@ -276,10 +276,22 @@ hipError_t launch_row_accumulate(int dtype, const GroupArgs& ga, uint32_t nwg, c
 // Momentum: mu, nesterov.  Adam: beta1, omb1 = 1 - beta1,
 // beta2, omb2 = 1 - beta2, and the step's bias corrections a = lr / (1 -
 // beta1^t), b = 1 / sqrt(1 - beta2^t), all computed on the host in double.
+// FTRL-Proximal: l1, l2, fbeta (the configuration's
+// ftrl_beta) and inv_lr = 1 / lr, computed on the host in double.  A launch
+// has one kind, and FTRL uses none of momentum's and Adam's fields, so its
+// four share their storage: the struct, and with it the kernel arguments and
+// the code of every older instantiation, stay as they were.
 template <typename T>
 struct OptArgs {
   T lr, wd, eps;
-  T mu, beta1, omb1, beta2, omb2, a, b;
+  union {
+    struct {
+      T mu, beta1, omb1, beta2, omb2, a, b;
+    };
+    struct {
+      T l1, l2, fbeta, inv_lr;
+    };
+  };
   int nesterov;
 };
 // Behind launch_general_mark (stamp mode) over the same `ga` and epoch: every
@@ -290,10 +302,10 @@ struct OptArgs {
 hipError_t launch_row_grad_losers(int dtype, const GroupArgs& ga, uint32_t nwg, const DenseView& d, void* gsum,
                                   const unsigned long long* owner, const Ovf& o, uint32_t epoch,
                                   const RowShape& rs, hipStream_t st);
-// Each winner applies the rule (kind: pskv_optimizer_kind, 1 to 4) once to its
+// Each winner applies the rule (kind: pskv_optimizer_kind, 1 to 5) once to its
 // key's row from its own gradient row plus the gsum row, and writes zeros back
 // to the gsum units it read non-zero.  state[0]: slot 0 (Adagrad's h,
-// momentum's v, Adam's m); state[1]: slot 1 (Adam's v).
+// momentum's v, Adam's m, FTRL's z); state[1]: slot 1 (Adam's v, FTRL's n).
 hipError_t launch_row_apply(int dtype, int kind, const GroupArgs& ga, uint32_t nwg, const DenseView& d, void* gsum,
                             void* const state[2], const unsigned long long* owner, uint32_t epoch,
                             const RowShape& rs, const OptArgs<double>& hy, hipStream_t st);

@@ -5,7 +5,7 @@
 //   k_row_commit      assign Add: the stamped winner of each key copies its whole row
 //   k_row_accumulate  accumulate Add: one no-return atomic add per element
 //   k_row_grad_losers optimizer step: gradient rows of non-winners summed into gsum
-//   k_row_apply       optimizer step: each key's winner applies SGD / Adagrad / momentum / Adam once
+//   k_row_apply       optimizer step: each key's winner applies SGD / Adagrad / momentum / Adam / FTRL once
 //   k_row_pooled_grad_losers  pooled push: k_row_grad_losers with rows weight * bag_grads[bag]
 //   k_row_pooled_apply        pooled push: k_row_apply with the winner's row formed the same way
 //   k_row_pooled_group_grad_losers  grouped pooled push: k_row_pooled_grad_losers over a launch group of batches
@@ -325,6 +325,16 @@ __device__ __forceinline__ bool opt_step_unit(const OptUnit<T, V>& g, OptUnit<T,
       h.e[i] = o.beta1 * h.e[i] + o.omb1 * dd;
       h2.e[i] = o.beta2 * h2.e[i] + o.omb2 * (dd * dd);
       p.e[i] = p.e[i] - o.a * (h.e[i] / (sqrt(h2.e[i]) * o.b + o.eps));
+    } else if (KIND == 5) {  // h is z, h2 is n
+      const T n0 = h2.e[i];
+      const T n1 = n0 + dd * dd;
+      const T r = sqrt(n1);
+      const T s = (r - sqrt(n0)) * o.inv_lr;
+      const T z1 = (h.e[i] + dd) - s * p.e[i];
+      h2.e[i] = n1;
+      h.e[i] = z1;
+      // a NaN z1 fails the comparison and goes on through the closed form
+      p.e[i] = fabs(z1) <= o.l1 ? T(0) : (copysign(o.l1, z1) - z1) / ((o.fbeta + r) * o.inv_lr + o.l2);
     } else {
       p.e[i] = p.e[i] - o.lr * dd;
     }
@@ -333,10 +343,11 @@ __device__ __forceinline__ bool opt_step_unit(const OptUnit<T, V>& g, OptUnit<T,
   return dirty;
 }
 
-// KIND: 1 = SGD, 2 = Adagrad, 3 = momentum, 4 = Adam (pskv_optimizer_kind).
-// One writer per row.  `state` is slot 0 (h / v / m), `state2` slot 1 (Adam's
-// v).  No instantiation spills with kRowsInFlight rows in flight (DESIGN.md
-// §8d has the resource table), Adam's five units per row included.
+// KIND: 1 = SGD, 2 = Adagrad, 3 = momentum, 4 = Adam, 5 = FTRL-Proximal
+// (pskv_optimizer_kind).  One writer per row.  `state` is slot 0 (h / v / m /
+// z), `state2` slot 1 (Adam's v, FTRL's n).  No instantiation spills with
+// kRowsInFlight rows in flight (DESIGN.md §8d and §8i have the resource
+// tables), Adam's and FTRL's five units per row included.
 template <typename T, int KIND, int V>
 __global__ __launch_bounds__(kBlock) void k_row_apply(GroupArgs ga, DenseView d, T* __restrict__ gsum,
                                                       T* __restrict__ state, T* __restrict__ state2,
@@ -378,7 +389,7 @@ __global__ __launch_bounds__(kBlock) void k_row_apply(GroupArgs ga, DenseView d,
           gs[r] = load_opt_unit<T, V>(gsum, at);
           p[r] = load_opt_unit<T, V>(param, at);
           if (KIND >= 2) h[r] = load_opt_unit<T, V>(state, at);
-          if (KIND == 4) h2[r] = load_opt_unit<T, V>(state2, at);
+          if (KIND >= 4) h2[r] = load_opt_unit<T, V>(state2, at);
         }
 #pragma unroll
         for (int r = 0; r < kRowsInFlight; ++r) {
@@ -387,7 +398,7 @@ __global__ __launch_bounds__(kBlock) void k_row_apply(GroupArgs ga, DenseView d,
           const bool dirty = opt_step_unit<T, KIND, V>(g[r], gs[r], p[r], h[r], h2[r], o);
           store_opt_unit<T, V>(param, at, p[r]);
           if (KIND >= 2) store_opt_unit<T, V>(state, at, h[r]);
-          if (KIND == 4) store_opt_unit<T, V>(state2, at, h2[r]);
+          if (KIND >= 4) store_opt_unit<T, V>(state2, at, h2[r]);
           if (dirty) store_opt_unit<T, V>(gsum, at, gs[r]);
         }
       }
@@ -524,7 +535,7 @@ __global__ __launch_bounds__(kBlock) void k_row_pooled_apply(PoolPushArgs a, Den
           gs[r] = load_opt_unit<T, V>(gsum, at);
           p[r] = load_opt_unit<T, V>(param, at);
           if (KIND >= 2) h[r] = load_opt_unit<T, V>(state, at);
-          if (KIND == 4) h2[r] = load_opt_unit<T, V>(state2, at);
+          if (KIND >= 4) h2[r] = load_opt_unit<T, V>(state2, at);
         }
 #pragma unroll
         for (int r = 0; r < kRowsInFlight; ++r) {
@@ -537,7 +548,7 @@ __global__ __launch_bounds__(kBlock) void k_row_pooled_apply(PoolPushArgs a, Den
           const bool dirty = opt_step_unit<T, KIND, V>(g[r], gs[r], p[r], h[r], h2[r], o);
           store_opt_unit<T, V>(param, at, p[r]);
           if (KIND >= 2) store_opt_unit<T, V>(state, at, h[r]);
-          if (KIND == 4) store_opt_unit<T, V>(state2, at, h2[r]);
+          if (KIND >= 4) store_opt_unit<T, V>(state2, at, h2[r]);
           if (dirty) store_opt_unit<T, V>(gsum, at, gs[r]);
         }
       }
@@ -690,7 +701,7 @@ __global__ __launch_bounds__(kBlock) void k_row_pooled_group_apply(PoolGroupArgs
           gs[r] = load_opt_unit<T, V>(gsum, at);
           p[r] = load_opt_unit<T, V>(param, at);
           if (KIND >= 2) h[r] = load_opt_unit<T, V>(state, at);
-          if (KIND == 4) h2[r] = load_opt_unit<T, V>(state2, at);
+          if (KIND >= 4) h2[r] = load_opt_unit<T, V>(state2, at);
         }
 #pragma unroll
         for (int r = 0; r < kRowsInFlight; ++r) {
@@ -703,7 +714,7 @@ __global__ __launch_bounds__(kBlock) void k_row_pooled_group_apply(PoolGroupArgs
           const bool dirty = opt_step_unit<T, KIND, V>(g[r], gs[r], p[r], h[r], h2[r], o);
           store_opt_unit<T, V>(param, at, p[r]);
           if (KIND >= 2) store_opt_unit<T, V>(state, at, h[r]);
-          if (KIND == 4) store_opt_unit<T, V>(state2, at, h2[r]);
+          if (KIND >= 4) store_opt_unit<T, V>(state2, at, h2[r]);
           if (dirty) store_opt_unit<T, V>(gsum, at, gs[r]);
         }
       }
@@ -741,8 +752,13 @@ hipError_t with_unit_type(const RowShape& rs, int vb, F&& f) {
 
 template <typename T>
 OptArgs<T> round_opt_args(const OptArgs<double>& h) {
-  return OptArgs<T>{(T)h.lr,   (T)h.wd,    (T)h.eps,  (T)h.mu, (T)h.beta1,
-                    (T)h.omb1, (T)h.beta2, (T)h.omb2, (T)h.a,  (T)h.b,    h.nesterov};
+  // (mu to b: FTRL's l1, l2, fbeta and inv_lr lie in the same places)
+  OptArgs<T> o;
+  o.lr = (T)h.lr, o.wd = (T)h.wd, o.eps = (T)h.eps;
+  o.mu = (T)h.mu, o.beta1 = (T)h.beta1, o.omb1 = (T)h.omb1, o.beta2 = (T)h.beta2, o.omb2 = (T)h.omb2;
+  o.a = (T)h.a, o.b = (T)h.b;
+  o.nesterov = h.nesterov;
+  return o;
 }
 
 template <typename T, int V>
@@ -752,7 +768,9 @@ void launch_row_apply_kind(int kind, uint32_t grid, const GroupArgs& ga, const D
   T* g = static_cast<T*>(gsum);
   T* s1 = static_cast<T*>(state[0]);
   T* s2 = static_cast<T*>(state[1]);
-  if (kind == 4)
+  if (kind == 5)
+    k_row_apply<T, 5, V><<<grid, kBlock, 0, st>>>(ga, d, g, s1, s2, owner, epoch, rs, o);
+  else if (kind == 4)
     k_row_apply<T, 4, V><<<grid, kBlock, 0, st>>>(ga, d, g, s1, s2, owner, epoch, rs, o);
   else if (kind == 3)
     k_row_apply<T, 3, V><<<grid, kBlock, 0, st>>>(ga, d, g, s1, s2, owner, epoch, rs, o);
@@ -769,7 +787,9 @@ void launch_row_pooled_apply_kind(int kind, uint32_t grid, const PoolPushArgs& a
   T* g = static_cast<T*>(gsum);
   T* s1 = static_cast<T*>(state[0]);
   T* s2 = static_cast<T*>(state[1]);
-  if (kind == 4)
+  if (kind == 5)
+    k_row_pooled_apply<T, 5, V, WEIGHTED><<<grid, kBlock, 0, st>>>(a, d, g, s1, s2, owner, epoch, rs, o);
+  else if (kind == 4)
     k_row_pooled_apply<T, 4, V, WEIGHTED><<<grid, kBlock, 0, st>>>(a, d, g, s1, s2, owner, epoch, rs, o);
   else if (kind == 3)
     k_row_pooled_apply<T, 3, V, WEIGHTED><<<grid, kBlock, 0, st>>>(a, d, g, s1, s2, owner, epoch, rs, o);
@@ -786,7 +806,9 @@ void launch_row_pooled_group_apply_kind(int kind, uint32_t grid, const PoolGroup
   T* g = static_cast<T*>(gsum);
   T* s1 = static_cast<T*>(state[0]);
   T* s2 = static_cast<T*>(state[1]);
-  if (kind == 4)
+  if (kind == 5)
+    k_row_pooled_group_apply<T, 5, V, WEIGHTED><<<grid, kBlock, 0, st>>>(ga, d, g, s1, s2, owner, epoch, rs, o);
+  else if (kind == 4)
     k_row_pooled_group_apply<T, 4, V, WEIGHTED><<<grid, kBlock, 0, st>>>(ga, d, g, s1, s2, owner, epoch, rs, o);
   else if (kind == 3)
     k_row_pooled_group_apply<T, 3, V, WEIGHTED><<<grid, kBlock, 0, st>>>(ga, d, g, s1, s2, owner, epoch, rs, o);
@@ -1091,7 +1113,7 @@ hipError_t launch_row_apply(int dtype, int kind, const GroupArgs& ga, uint32_t n
                             void* const state[2], const unsigned long long* owner, uint32_t epoch,
                             const RowShape& rs, const OptArgs<double>& hy, hipStream_t st) {
   if (nwg == 0) return hipSuccess;
-  if (kind < 1 || kind > 4 || (kind >= 2 && !state[0]) || (kind == 4 && !state[1])) return hipErrorInvalidValue;
+  if (kind < 1 || kind > 5 || (kind >= 2 && !state[0]) || (kind >= 4 && !state[1])) return hipErrorInvalidValue;
   const uint32_t grid = row_grid(nwg);
   return with_float_type(dtype, [&](auto z) {
     using T = decltype(z);
@@ -1130,7 +1152,7 @@ hipError_t launch_row_pooled_apply(int dtype, int kind, const PoolPushArgs& a, c
                                    const RowShape& rs, const OptArgs<double>& hy, hipStream_t st) {
   if (a.n == 0) return hipSuccess;
   if (a.n > kMaxPiece || a.nbags == 0) return hipErrorInvalidValue;
-  if (kind < 1 || kind > 4 || (kind >= 2 && !state[0]) || (kind == 4 && !state[1])) return hipErrorInvalidValue;
+  if (kind < 1 || kind > 5 || (kind >= 2 && !state[0]) || (kind >= 4 && !state[1])) return hipErrorInvalidValue;
   const uint32_t grid = push_grid(a);
   return with_float_type(dtype, [&](auto z) {
     using T = decltype(z);
@@ -1186,7 +1208,7 @@ hipError_t launch_row_pooled_group_apply(int dtype, int kind, const PoolGroupArg
                                          const OptArgs<double>& hy, hipStream_t st) {
   if (nwg == 0) return hipSuccess;
   if (!pool_group_ok(ga, nwg)) return hipErrorInvalidValue;
-  if (kind < 1 || kind > 4 || (kind >= 2 && !state[0]) || (kind == 4 && !state[1])) return hipErrorInvalidValue;
+  if (kind < 1 || kind > 5 || (kind >= 2 && !state[0]) || (kind >= 4 && !state[1])) return hipErrorInvalidValue;
   const uint32_t grid = row_grid(nwg);
   return with_float_type(dtype, [&](auto z) {
     using T = decltype(z);

@@ -380,7 +380,7 @@ struct pskv_shard {
   // scratch (shaped as the dense array, zero between calls) and the kind's
   // state slots (Adagrad h; momentum v; Adam m, v); all allocated when the
   // optimizer is set.  opt_step: steps since creation, clear or a kind change.
-  pskv_optimizer_ex opt{};
+  pskv_optimizer_cfg opt{};  // (its first 72 bytes are a pskv_optimizer_ex)
   void* opt_gsum = nullptr;
   void* opt_slot[2] = {nullptr, nullptr};  // the first opt_slots(opt.kind) are allocated
   uint64_t opt_step = 0;
@@ -1855,12 +1855,13 @@ size_t opt_array_bytes(const pskv_shard* s) { return s->range * row_bytes(s); }
 
 // State slots per kind (pskv_optimizer_kind).
 int opt_slots(int kind) {
-  return kind == PSKV_OPT_ADAM ? 2 : (kind == PSKV_OPT_ADAGRAD || kind == PSKV_OPT_MOMENTUM) ? 1 : 0;
+  return (kind == PSKV_OPT_ADAM || kind == PSKV_OPT_FTRL) ? 2
+         : (kind == PSKV_OPT_ADAGRAD || kind == PSKV_OPT_MOMENTUM) ? 1 : 0;
 }
 
 // The hyper-parameters of step `step` as a launch takes them, in double; a
 // field the kind does not use is 0.
-OptArgs<double> opt_args(const pskv_optimizer_ex& c, uint64_t step) {
+OptArgs<double> opt_args(const pskv_optimizer_cfg& c, uint64_t step) {
   OptArgs<double> o{};
   o.lr = c.lr;
   o.wd = c.weight_decay;
@@ -1875,17 +1876,22 @@ OptArgs<double> opt_args(const pskv_optimizer_ex& c, uint64_t step) {
     o.omb2 = 1.0 - c.beta2;
     o.a = c.lr / (1.0 - std::pow(c.beta1, (double)step));
     o.b = 1.0 / std::sqrt(1.0 - std::pow(c.beta2, (double)step));
+  } else if (c.kind == PSKV_OPT_FTRL) {
+    o.l1 = c.l1;
+    o.l2 = c.l2;
+    o.fbeta = c.ftrl_beta;
+    o.inv_lr = 1.0 / c.lr;
   }
   return o;
 }
 
-// The state back to its start values (Adagrad's h: init_accum; every other
-// slot: 0), the gradient scratch to zero (stream-ordered), the step count to 0.
+// The state back to its start values (Adagrad's h and FTRL's n: init_accum;
+// every other slot: 0), the gradient scratch to zero (stream-ordered), the step count to 0.
 int opt_reset_state(pskv_shard* s) {
   s->opt_step = 0;
   if (s->opt_gsum) PSKV_HIP(hipMemsetAsync(s->opt_gsum, 0, opt_array_bytes(s), s->stream));
   for (int i = 0; i < opt_slots(s->opt.kind); ++i) {
-    if (s->opt.kind == PSKV_OPT_ADAGRAD)
+    if (s->opt.kind == PSKV_OPT_ADAGRAD || (s->opt.kind == PSKV_OPT_FTRL && i == 1))
       PSKV_HIP(launch_fill(s->dtype, s->opt_slot[i], s->range * (uint64_t)s->width, s->opt.init_accum, s->stream));
     else
       PSKV_HIP(hipMemsetAsync(s->opt_slot[i], 0, opt_array_bytes(s), s->stream));
@@ -2127,21 +2133,32 @@ int apply_pooled_grouped_impl(pskv_shard* s, const pskv_pool_batch* batches, uin
 // What is wrong with a configuration, or null (checked before any handle;
 // fields a kind does not use are ignored).  legacy: the configuration was
 // widened from a pskv_optimizer, which has no size and only the first kinds.
-const char* opt_config_error(const pskv_optimizer_ex& c, bool legacy) {
-  if (legacy) {
+// kOptEx: widened from a pskv_optimizer_ex, which ends before FTRL's fields
+// and knows the kinds up to Adam.  c.size is the size of the caller's struct.
+enum OptAbi { kOptLegacy, kOptEx, kOptCfg };
+static_assert(sizeof(pskv_optimizer_ex) == 72 && offsetof(pskv_optimizer_cfg, beta2) == offsetof(pskv_optimizer_ex, beta2) &&
+                  offsetof(pskv_optimizer_cfg, l1) == sizeof(pskv_optimizer_ex) && sizeof(pskv_optimizer_cfg) == 96,
+              "pskv_optimizer_cfg begins as pskv_optimizer_ex and adds three doubles");
+const char* opt_config_error(const pskv_optimizer_cfg& c, OptAbi abi) {
+  if (abi == kOptLegacy) {
     if (c.kind != PSKV_OPT_NONE && c.kind != PSKV_OPT_SGD && c.kind != PSKV_OPT_ADAGRAD)
       return "kind must be PSKV_OPT_NONE, PSKV_OPT_SGD or PSKV_OPT_ADAGRAD";
-  } else {
+  } else if (abi == kOptEx) {
     if (c.size != sizeof(pskv_optimizer_ex)) return "size must be sizeof(pskv_optimizer_ex)";
     if (c.kind < PSKV_OPT_NONE || c.kind > PSKV_OPT_ADAM)
       return "kind must be PSKV_OPT_NONE, PSKV_OPT_SGD, PSKV_OPT_ADAGRAD, PSKV_OPT_MOMENTUM or PSKV_OPT_ADAM";
+  } else {
+    if (c.size != sizeof(pskv_optimizer_cfg)) return "size must be sizeof(pskv_optimizer_cfg)";
+    if (c.kind < PSKV_OPT_NONE || c.kind > PSKV_OPT_FTRL)
+      return "kind must be PSKV_OPT_NONE, PSKV_OPT_SGD, PSKV_OPT_ADAGRAD, PSKV_OPT_MOMENTUM, PSKV_OPT_ADAM or "
+             "PSKV_OPT_FTRL";
   }
   if (c.kind == PSKV_OPT_NONE) return nullptr;
   if (!std::isfinite(c.lr) || !(c.lr > 0)) return "lr must be finite and > 0";
   if (!std::isfinite(c.weight_decay) || !(c.weight_decay >= 0)) return "weight_decay must be finite and >= 0";
   if (c.kind == PSKV_OPT_ADAGRAD || c.kind == PSKV_OPT_ADAM)
     if (!std::isfinite(c.eps) || !(c.eps > 0)) return "eps must be finite and > 0";
-  if (c.kind == PSKV_OPT_ADAGRAD)
+  if (c.kind == PSKV_OPT_ADAGRAD || c.kind == PSKV_OPT_FTRL)
     if (!std::isfinite(c.init_accum) || !(c.init_accum >= 0)) return "init_accum must be finite and >= 0";
   if (c.kind == PSKV_OPT_MOMENTUM) {
     if (!std::isfinite(c.momentum) || !(c.momentum >= 0) || !(c.momentum < 1))
@@ -2151,6 +2168,11 @@ const char* opt_config_error(const pskv_optimizer_ex& c, bool legacy) {
   if (c.kind == PSKV_OPT_ADAM) {
     if (!std::isfinite(c.beta1) || !(c.beta1 >= 0) || !(c.beta1 < 1)) return "beta1 must be finite and in [0, 1)";
     if (!std::isfinite(c.beta2) || !(c.beta2 >= 0) || !(c.beta2 < 1)) return "beta2 must be finite and in [0, 1)";
+  }
+  if (c.kind == PSKV_OPT_FTRL) {
+    if (!std::isfinite(c.l1) || !(c.l1 >= 0)) return "l1 must be finite and >= 0";
+    if (!std::isfinite(c.l2) || !(c.l2 >= 0)) return "l2 must be finite and >= 0";
+    if (!std::isfinite(c.ftrl_beta) || !(c.ftrl_beta >= 0)) return "ftrl_beta must be finite and >= 0";
   }
   return nullptr;
 }
@@ -2582,10 +2604,13 @@ int apply_env_options(pskv_shard* s) {
   return PSKV_OK;
 }
 
-// Both setters end here (legacy: from pskv_shard_set_optimizer, widened).
-int set_optimizer_impl(pskv_shard* s, const pskv_optimizer_ex& cfg, bool legacy, const std::string& who) {
+// Every setter ends here, its configuration widened to a pskv_optimizer_cfg
+// (abi: which struct it came from; the shard keeps the widened form, size =
+// sizeof(pskv_optimizer_cfg)).
+int set_optimizer_impl(pskv_shard* s, pskv_optimizer_cfg cfg, OptAbi abi, const std::string& who) {
   // the configuration first: a bad field is reported whatever the handle
-  if (const char* what = opt_config_error(cfg, legacy)) return fail(PSKV_EINVAL, who + ": " + what);
+  if (const char* what = opt_config_error(cfg, abi)) return fail(PSKV_EINVAL, who + ": " + what);
+  cfg.size = sizeof(pskv_optimizer_cfg);
   if (!s) return fail(PSKV_EINVAL, who + ": null shard");
   if (cfg.kind != PSKV_OPT_NONE && s->dtype != PSKV_F32 && s->dtype != PSKV_F64)
     return fail(PSKV_EINVAL, who + ": optimizers need a float shard (PSKV_F32, PSKV_F64)");
@@ -2651,7 +2676,7 @@ uint64_t opt_state_bytes(const pskv_shard* s) {
 void* opt_slot_array(pskv_shard* s, int slot, const char* who) {
   if (slot < 0 || slot >= opt_slots(s->opt.kind)) {
     (void)fail(PSKV_EINVAL, std::string(who) + ": the shard's optimizer has no state slot " + std::to_string(slot) +
-                                " (slots: SGD 0, Adagrad 1, momentum 1, Adam 2)");
+                                " (slots: SGD 0, Adagrad 1, momentum 1, Adam 2, FTRL 2)");
     return nullptr;
   }
   return s->opt_slot[slot];
@@ -2902,19 +2927,25 @@ int pskv_get_pooled(pskv_shard* s, const uint32_t* keys, uint64_t n, const void*
 
 int pskv_shard_set_optimizer(pskv_shard* s, const pskv_optimizer* cfg) {
   if (!cfg) return fail(PSKV_EINVAL, "pskv_shard_set_optimizer: null configuration");
-  pskv_optimizer_ex x{};
-  x.size = sizeof(x);
+  pskv_optimizer_cfg x{};
   x.kind = cfg->kind;
   x.lr = cfg->lr;
   x.weight_decay = cfg->weight_decay;
   x.eps = cfg->eps;
   x.init_accum = cfg->init_accum;
-  return set_optimizer_impl(s, x, /*legacy=*/true, "pskv_shard_set_optimizer");
+  return set_optimizer_impl(s, x, kOptLegacy, "pskv_shard_set_optimizer");
 }
 
 int pskv_shard_set_optimizer_ex(pskv_shard* s, const pskv_optimizer_ex* cfg) {
   if (!cfg) return fail(PSKV_EINVAL, "pskv_shard_set_optimizer_ex: null configuration");
-  return set_optimizer_impl(s, *cfg, /*legacy=*/false, "pskv_shard_set_optimizer_ex");
+  pskv_optimizer_cfg x{};
+  std::memcpy(&x, cfg, sizeof(pskv_optimizer_ex));  // (the common prefix, size included)
+  return set_optimizer_impl(s, x, kOptEx, "pskv_shard_set_optimizer_ex");
+}
+
+int pskv_shard_set_optimizer_cfg(pskv_shard* s, const pskv_optimizer_cfg* cfg) {
+  if (!cfg) return fail(PSKV_EINVAL, "pskv_shard_set_optimizer_cfg: null configuration");
+  return set_optimizer_impl(s, *cfg, kOptCfg, "pskv_shard_set_optimizer_cfg");
 }
 
 int pskv_shard_get_optimizer(pskv_shard* s, pskv_optimizer* out, uint64_t* state_bytes) {
@@ -2933,8 +2964,18 @@ int pskv_shard_get_optimizer(pskv_shard* s, pskv_optimizer* out, uint64_t* state
 int pskv_shard_get_optimizer_ex(pskv_shard* s, pskv_optimizer_ex* out, uint64_t* state_bytes) {
   if (!s) return fail(PSKV_EINVAL, "pskv_shard_get_optimizer_ex: null shard");
   if (out) {
-    *out = s->opt;
+    std::memcpy(out, &s->opt, sizeof(pskv_optimizer_ex));  // (the common prefix)
     out->size = sizeof(pskv_optimizer_ex);
+  }
+  if (state_bytes) *state_bytes = opt_state_bytes(s);
+  return PSKV_OK;
+}
+
+int pskv_shard_get_optimizer_cfg(pskv_shard* s, pskv_optimizer_cfg* out, uint64_t* state_bytes) {
+  if (!s) return fail(PSKV_EINVAL, "pskv_shard_get_optimizer_cfg: null shard");
+  if (out) {
+    *out = s->opt;
+    out->size = sizeof(pskv_optimizer_cfg);
   }
   if (state_bytes) *state_bytes = opt_state_bytes(s);
   return PSKV_OK;

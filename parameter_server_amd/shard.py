@@ -241,18 +241,30 @@ class Shard:
 
     # ------------------------------------------------------------ optimizer steps
     _OPT_KIND = {None: _lib.PSKV_OPT_NONE, "none": _lib.PSKV_OPT_NONE, "sgd": _lib.PSKV_OPT_SGD,
-                 "adagrad": _lib.PSKV_OPT_ADAGRAD, "momentum": _lib.PSKV_OPT_MOMENTUM, "adam": _lib.PSKV_OPT_ADAM}
+                 "adagrad": _lib.PSKV_OPT_ADAGRAD, "momentum": _lib.PSKV_OPT_MOMENTUM, "adam": _lib.PSKV_OPT_ADAM,
+                 "ftrl": _lib.PSKV_OPT_FTRL}
     _OPT_NAME = {_lib.PSKV_OPT_NONE: None, _lib.PSKV_OPT_SGD: "sgd", _lib.PSKV_OPT_ADAGRAD: "adagrad",
-                 _lib.PSKV_OPT_MOMENTUM: "momentum", _lib.PSKV_OPT_ADAM: "adam"}
-    _OPT_SLOTS = {None: 0, "sgd": 0, "adagrad": 1, "momentum": 1, "adam": 2}
+                 _lib.PSKV_OPT_MOMENTUM: "momentum", _lib.PSKV_OPT_ADAM: "adam", _lib.PSKV_OPT_FTRL: "ftrl"}
+    _OPT_SLOTS = {None: 0, "sgd": 0, "adagrad": 1, "momentum": 1, "adam": 2, "ftrl": 2}
 
     def set_optimizer(self, kind, lr: float = 0.0, weight_decay: float = 0.0, eps: float = 1e-10,
-                      init_accum: float = 0.0, momentum: float = 0.0, nesterov: bool = False,
-                      beta1: float = 0.9, beta2: float = 0.999):
-        """pskv_shard_set_optimizer(_ex): kind "sgd", "adagrad", "momentum", "adam" or
-        None.  The same kind again changes the hyper-parameters of later steps
-        only (state and step count stay); another kind resets both."""
+                      init_accum=None, momentum: float = 0.0, nesterov: bool = False,
+                      beta1: float = 0.9, beta2: float = 0.999, l1: float = 0.0, l2: float = 0.0,
+                      ftrl_beta: float = 1.0):
+        """pskv_shard_set_optimizer(_ex, _cfg): kind "sgd", "adagrad", "momentum",
+        "adam", "ftrl" or None.  The same kind again changes the hyper-parameters
+        of later steps only (state and step count stay); another kind resets
+        both.  init_accum None: 0.1 for "ftrl" (n must not start at 0 beside
+        ftrl_beta = 0), else 0."""
         code = self._OPT_KIND[kind]
+        if init_accum is None:
+            init_accum = 0.1 if code == _lib.PSKV_OPT_FTRL else 0.0
+        if code == _lib.PSKV_OPT_FTRL:
+            cfg = _lib.PskvOptimizerCfg(ctypes.sizeof(_lib.PskvOptimizerCfg), code, float(lr), float(weight_decay),
+                                        float(eps), float(init_accum), float(momentum), int(nesterov), float(beta1),
+                                        float(beta2), float(l1), float(l2), float(ftrl_beta))
+            check(lib.pskv_shard_set_optimizer_cfg(self._h, ctypes.byref(cfg)))
+            return
         if code in (_lib.PSKV_OPT_MOMENTUM, _lib.PSKV_OPT_ADAM):
             cfg = _lib.PskvOptimizerEx(ctypes.sizeof(_lib.PskvOptimizerEx), code, float(lr), float(weight_decay),
                                        float(eps), float(init_accum), float(momentum), int(nesterov), float(beta1),
@@ -265,15 +277,17 @@ class Shard:
     def optimizer(self) -> dict:
         """The configuration, and `state_bytes`: what the optimizer holds in HBM
         beyond the dense array.  "momentum" adds momentum and nesterov, "adam"
-        beta1 and beta2."""
-        cfg, nbytes = _lib.PskvOptimizerEx(), ctypes.c_uint64()
-        check(lib.pskv_shard_get_optimizer_ex(self._h, ctypes.byref(cfg), ctypes.byref(nbytes)))
+        beta1 and beta2, "ftrl" l1, l2 and ftrl_beta."""
+        cfg, nbytes = _lib.PskvOptimizerCfg(), ctypes.c_uint64()
+        check(lib.pskv_shard_get_optimizer_cfg(self._h, ctypes.byref(cfg), ctypes.byref(nbytes)))
         d = {"kind": self._OPT_NAME[cfg.kind], "lr": cfg.lr, "weight_decay": cfg.weight_decay,
              "eps": cfg.eps, "init_accum": cfg.init_accum, "state_bytes": nbytes.value}
         if cfg.kind == _lib.PSKV_OPT_MOMENTUM:
             d.update(momentum=cfg.momentum, nesterov=bool(cfg.nesterov))
         elif cfg.kind == _lib.PSKV_OPT_ADAM:
             d.update(beta1=cfg.beta1, beta2=cfg.beta2)
+        elif cfg.kind == _lib.PSKV_OPT_FTRL:
+            d.update(l1=cfg.l1, l2=cfg.l2, ftrl_beta=cfg.ftrl_beta)
         return d
 
     def apply(self, keys, grads):
@@ -369,7 +383,7 @@ class Shard:
 
     def get_state(self, keys, out=None, slot: int = 0):
         """The rows of `keys` in state slot `slot` (pskv_get_state_slot; Adagrad
-        h, momentum v, Adam m and v), as get returns values."""
+        h, momentum v, Adam m and v, FTRL z and n), as get returns values."""
         if _is_torch(keys):
             import torch
 

@@ -110,8 +110,8 @@ class HipStorage(AbstractStorage):
     (driver/engine.hpp:100-109): the whole uint32 key space, assign semantics.
     width > 1: a row-valued storage, `width` values per key (the value frame
     of an Add holds keys * width values, row-major, and so does a Get reply).
-    optimizer: a dict for Shard.set_optimizer (kind "sgd", "adagrad", "momentum"
-    or "adam", lr, ...).  The storage then
+    optimizer: a dict for Shard.set_optimizer (kind "sgd", "adagrad", "momentum",
+    "adam" or "ftrl", lr, ...).  The storage then
     applies optimizer steps: an Add message carries GRADIENTS and is one step
     (pskv_apply); AddGrouped, a BSP flush, is one step over all its messages."""
 

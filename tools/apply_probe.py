@@ -5,9 +5,10 @@ WARMUP.  Every call is timed twice: by the library's own timers and by HIP
 events around the whole step (on the legacy default stream, which the shard's
 blocking stream orders against).
 
-  --leg apply      one pskv_apply per call; --kind adagrad (default), momentum
-                   or adam selects the rule (momentum 0.9, Adam's
-                   betas 0.9 / 0.999)
+  --leg apply      one pskv_apply per call; --kind adagrad (default), momentum,
+                   adam or ftrl selects the rule (momentum 0.9,
+                   Adam's betas 0.9 / 0.999; §8i: FTRL-Proximal with l1 0.5,
+                   l2 0.01, ftrl_beta 1)
                    --dups D: a call of the same size with D occurrences per
                    key (KEYS / D distinct keys, shuffled): prices the loser atomics
   --leg roundtrip  what a worker must do without optimizer steps for the same
@@ -40,6 +41,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LR, WD, EPS, INIT_ACCUM = 0.05, 0.0, 1e-8, 0.1
 MOMENTUM, BETA1, BETA2 = 0.9, 0.9, 0.999
+L1, L2, FTRL_BETA = 0.5, 0.01, 1.0
 
 
 def run_width(ps, torch, leg, w, rows, nkeys, steps, warmup, dups, kind="adagrad"):
@@ -62,6 +64,8 @@ def run_width(ps, torch, leg, w, rows, nkeys, steps, warmup, dups, kind="adagrad
             sh.set_optimizer("adagrad", lr=LR, weight_decay=WD, eps=EPS, init_accum=INIT_ACCUM)
         elif leg == "apply" and kind == "momentum":
             sh.set_optimizer("momentum", lr=LR, weight_decay=WD, momentum=MOMENTUM)
+        elif leg == "apply" and kind == "ftrl":
+            sh.set_optimizer("ftrl", lr=LR, weight_decay=WD, l1=L1, l2=L2, ftrl_beta=FTRL_BETA, init_accum=INIT_ACCUM)
         elif leg == "apply":
             sh.set_optimizer("adam", lr=LR, weight_decay=WD, eps=EPS, beta1=BETA1, beta2=BETA2)
         else:
@@ -169,6 +173,27 @@ def merge(paths):
                         w: round(doc["summary"][name][w]["event_ms"] / doc["summary"][base][w]["event_ms"], 3)
                         for w in legs[name]}
                     doc[k + "_model"] = round(streams / 6, 3)
+    if "apply_adam@parent" in legs and "apply_adam@new" in legs:
+        # the regression guard of DESIGN.md §8i: Adagrad (above) and Adam, parent build against this build
+        doc["adam_new_over_parent"] = {}
+        doc["adam_guard_met"] = True
+        for w in legs["apply_adam@new"]:
+            n, b = doc["summary"]["apply_adam@new"][w], doc["summary"]["apply_adam@parent"][w]
+            slack = max(n["event_ms_spread"], b["event_ms_spread"])
+            doc["adam_new_over_parent"][w] = round(n["event_ms"] / b["event_ms"], 3)
+            doc["adam_guard_met"] = doc["adam_guard_met"] and n["event_ms"] <= b["event_ms"] + slack
+        doc["condition_met"] = bool(doc["condition_met"]) and doc["adam_guard_met"]
+    if "apply_ftrl@new" in legs and "apply_adam@new" in legs:
+        # FTRL against Adam on one build: both move eight dense-sized streams of the touched rows (model 1);
+        # reported, not gated
+        doc["ftrl_over_adam"] = {}
+        doc["ftrl_model"] = 1.0
+        doc["ftrl_minus_adam_inside_spread"] = {}
+        for w in legs["apply_ftrl@new"]:
+            f, a = doc["summary"]["apply_ftrl@new"][w], doc["summary"]["apply_adam@new"][w]
+            doc["ftrl_over_adam"][w] = round(f["event_ms"] / a["event_ms"], 3)
+            doc["ftrl_minus_adam_inside_spread"][w] = bool(
+                abs(f["event_ms"] - a["event_ms"]) <= max(f["event_ms_spread"], a["event_ms_spread"]))
     if "apply" in legs and "roundtrip" in legs:
         doc["apply_over_roundtrip"] = {}
         for w in legs["apply"]:
@@ -193,7 +218,7 @@ def main():
     ap.add_argument("--rows", type=int, default=1 << 24)
     ap.add_argument("--keys", type=int, default=1 << 20)
     ap.add_argument("--dups", type=int, default=1)
-    ap.add_argument("--kind", choices=["adagrad", "momentum", "adam"], default="adagrad",
+    ap.add_argument("--kind", choices=["adagrad", "momentum", "adam", "ftrl"], default="adagrad",
                     help="the apply leg's optimizer")
     ap.add_argument("--label", default="", help="kept in the run document; --merge keeps labelled runs apart")
     ap.add_argument("--widths", default="4,16,64")
