@@ -294,28 +294,26 @@ struct OptArgs {
   };
   int nesterov;
 };
-// Behind launch_general_mark (stamp mode) over the same `ga` and epoch: every
-// in-range element that is NOT its key's winner adds its gradient row into
-// gsum (shaped as the dense array, zero between calls), one no-return atomic
-// per element (rs built with unit16 = false).  Out-of-range keys set
-// kErrRowOutOfRange.  d.param is not touched.
-hipError_t launch_row_grad_losers(int dtype, const GroupArgs& ga, uint32_t nwg, const DenseView& d, void* gsum,
-                                  const unsigned long long* owner, const Ovf& o, uint32_t epoch,
-                                  const RowShape& rs, hipStream_t st);
-// Each winner applies the rule (kind: pskv_optimizer_kind, 1 to 5) once to its
-// key's row from its own gradient row plus the gsum row, and writes zeros back
-// to the gsum units it read non-zero.  state[0]: slot 0 (Adagrad's h,
-// momentum's v, Adam's m, FTRL's z); state[1]: slot 1 (Adam's v, FTRL's n).
-hipError_t launch_row_apply(int dtype, int kind, const GroupArgs& ga, uint32_t nwg, const DenseView& d, void* gsum,
-                            void* const state[2], const unsigned long long* owner, uint32_t epoch,
-                            const RowShape& rs, const OptArgs<double>& hy, hipStream_t st);
-// Pooled push (pskv_apply_pooled): the two launches above with
-// the gradient row of key position i formed in registers,
-// weights[i] * bag_grads[bag(i)] (one multiplication rounded to the value
-// type; weights null: the bag's row itself).  One batch of n <= kMaxPiece
-// keys behind launch_general_mark over {keys, n} with the same epoch; nbags
-// >= 1.  The bag of a position: pskv_plan.h (pool_bag_span, pool_bags_in);
-// whatever the offsets hold it is below nbags.
+// A step's two launches, behind launch_general_mark (stamp mode) with the same
+// epoch, over one of three argument blocks `a` of nwg virtual workgroups of
+// kGeneralChunk positions (nwg == 0: nothing is launched):
+//   GroupArgs      a launch group with its gradient rows (b[j].vals), as the
+//                  mark took it.
+//   PoolPushArgs   pooled push (pskv_apply_pooled): one batch of
+//                  1 to kMaxPiece keys, the mark over {keys, n}.  The gradient
+//                  row of key position i is formed in registers, weights[i] *
+//                  bag_grads[bag(i)] (one multiplication rounded to the value
+//                  type; weights null: the bag's row itself); nbags >= 1.  The
+//                  bag of a position: pskv_plan.h (pool_bag_span,
+//                  pool_bags_in); whatever the offsets hold it is below nbags.
+//   PoolGroupArgs  grouped pooled push (pskv_apply_pooled_grouped, DESIGN.md
+//                  §8h; pskv_plan.h): a launch group of such batches, the mark
+//                  over the GroupArgs of the same batches (keys and n).  A
+//                  virtual workgroup belongs to one batch; a position's tag
+//                  carries the keys of the batches before it.  When some batch
+//                  has weights, one without them contributes its bag rows
+//                  unmultiplied.
+// A pooled block that is not as described is refused (hipErrorInvalidValue).
 struct PoolPushArgs {
   const uint32_t* keys;     // n
   const void* weights;      // n values, or null
@@ -323,29 +321,23 @@ struct PoolPushArgs {
   uint64_t n, nbags;
   const void* bag_grads;    // nbags rows
 };
-// rs built with unit16 = false.
-hipError_t launch_row_pooled_grad_losers(int dtype, const PoolPushArgs& a, const DenseView& d, void* gsum,
-                                         const unsigned long long* owner, const Ovf& o, uint32_t epoch,
-                                         const RowShape& rs, hipStream_t st);
-// unit16 also wants bag_grads 16-byte aligned.
-hipError_t launch_row_pooled_apply(int dtype, int kind, const PoolPushArgs& a, const DenseView& d, void* gsum,
-                                   void* const state[2], const unsigned long long* owner, uint32_t epoch,
-                                   const RowShape& rs, const OptArgs<double>& hy, hipStream_t st);
-// Grouped pooled push (pskv_apply_pooled_grouped): the two
-// launches above over a launch group of pooled batches (PoolGroupArgs,
-// pskv_plan.h), behind launch_general_mark over the GroupArgs of the same
-// batches (keys and n) with the same epoch.  A virtual workgroup belongs to
-// one batch; a position's tag carries the keys of the batches before it.
-// weighted: some batch of the group has weights (a batch without them then
-// contributes its bag rows unmultiplied).  rs built with unit16 = false.
-hipError_t launch_row_pooled_group_grad_losers(int dtype, const PoolGroupArgs& ga, uint32_t nwg, bool weighted,
-                                               const DenseView& d, void* gsum, const unsigned long long* owner,
-                                               const Ovf& o, uint32_t epoch, const RowShape& rs, hipStream_t st);
-// unit16 also wants every batch's bag_grads 16-byte aligned.
-hipError_t launch_row_pooled_group_apply(int dtype, int kind, const PoolGroupArgs& ga, uint32_t nwg, bool weighted,
-                                         const DenseView& d, void* gsum, void* const state[2],
-                                         const unsigned long long* owner, uint32_t epoch, const RowShape& rs,
-                                         const OptArgs<double>& hy, hipStream_t st);
+// Every in-range position that is NOT its key's winner adds its gradient row
+// into gsum (shaped as the dense array, zero between calls), one no-return
+// atomic per element (rs built with unit16 = false).  Out-of-range keys set
+// kErrRowOutOfRange.  d.param is not touched.
+template <typename Args>
+hipError_t launch_row_step_losers(int dtype, const Args& a, uint32_t nwg, const DenseView& d, void* gsum,
+                                  const unsigned long long* owner, const Ovf& o, uint32_t epoch, const RowShape& rs,
+                                  hipStream_t st);
+// Each winner applies the rule (kind: pskv_optimizer_kind, 1 to 5) once to its
+// key's row from its own gradient row plus the gsum row, and writes zeros back
+// to the gsum units it read non-zero.  state[0]: slot 0 (Adagrad's h,
+// momentum's v, Adam's m, FTRL's z); state[1]: slot 1 (Adam's v, FTRL's n).
+// unit16 also wants every batch's rows (vals, bag_grads) 16-byte aligned.
+template <typename Args>
+hipError_t launch_row_step_apply(int dtype, int kind, const Args& a, uint32_t nwg, const DenseView& d, void* gsum,
+                                 void* const state[2], const unsigned long long* owner, uint32_t epoch,
+                                 const RowShape& rs, const OptArgs<double>& hy, hipStream_t st);
 // p[0..n) = v (float or double by dtype): the accumulator's initial value.
 hipError_t launch_fill(int dtype, void* p, uint64_t n, double v, hipStream_t st);
 

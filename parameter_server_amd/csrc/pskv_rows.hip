@@ -4,12 +4,10 @@
 //   k_row_gather      Get: out[i] = row(keys[i]), zeros for a key outside the range
 //   k_row_commit      assign Add: the stamped winner of each key copies its whole row
 //   k_row_accumulate  accumulate Add: one no-return atomic add per element
-//   k_row_grad_losers optimizer step: gradient rows of non-winners summed into gsum
-//   k_row_apply       optimizer step: each key's winner applies SGD / Adagrad / momentum / Adam / FTRL once
-//   k_row_pooled_grad_losers  pooled push: k_row_grad_losers with rows weight * bag_grads[bag]
-//   k_row_pooled_apply        pooled push: k_row_apply with the winner's row formed the same way
-//   k_row_pooled_group_grad_losers  grouped pooled push: k_row_pooled_grad_losers over a launch group of batches
-//   k_row_pooled_group_apply        grouped pooled push: k_row_pooled_apply over a launch group of batches
+//   k_row_step_losers optimizer step: gradient rows of non-winners summed into gsum
+//   k_row_step_apply  optimizer step: each key's winner applies SGD / Adagrad / momentum / Adam / FTRL once
+//                     (both over GroupArgs: rows given; PoolPushArgs, PoolGroupArgs: a pooled push's
+//                     or a group of pooled pushes' rows weight * bag_grads[bag], formed in registers)
 //   k_row_pooled      pooled pull: out[b] = sum over bag b's keys of weight * row(key)
 //   k_row_pooled_chunks  pooled pull: the chunks of bags longer than kPoolChunk, into partial rows
 //
@@ -30,6 +28,8 @@
 // group g of the workgroup's G = kBlock / L groups takes the chunk's elements
 // g, g + G, ...; `li` below is the element's index inside the chunk, the same
 // number K4a folds into its stamps.
+#include <type_traits>
+
 #include "pskv_internal.h"
 
 namespace pskv {
@@ -217,10 +217,27 @@ __global__ __launch_bounds__(kBlock) void k_row_accumulate(GroupArgs ga, DenseVi
 }
 
 // ------------------------------------------------------- optimizer steps
-// One pskv_apply call is one step: behind K4a's stamps,
-// k_row_grad_losers sums the gradient rows of every element that is not its
-// key's winner into `gsum` (zero between calls), then k_row_apply lets each
-// winner apply the rule once to its key's row and put the gsum row back to zero.
+// One call is one step: behind K4a's stamps, k_row_step_losers
+// sums the gradient row of every position that is not its key's winner into
+// `gsum` (zero between calls), then k_row_step_apply lets each winner apply the
+// rule once to its key's row and put the gsum row back to zero.  Both are
+// written once over the argument block, which says where a virtual workgroup's
+// batch and a position's gradient row come from:
+//   GroupArgs      pskv_apply[_grouped]: a launch group of batches; position
+//                  i's row is vals[i].
+//   PoolPushArgs   pskv_apply_pooled: one batch, so a position
+//                  is its own stamp index; its row is formed here, weights[i] *
+//                  bag_grads[bag(i)] (the bag of a position: pskv_plan.h).
+//   PoolGroupArgs  pskv_apply_pooled_grouped: a launch group of
+//                  pooled batches.  A virtual workgroup of kGeneralChunk
+//                  positions belongs to ONE batch (the wg_prefix search); its
+//                  bags are looked up in that batch's offsets, its span ends
+//                  at that batch's last position, and its tags carry the keys
+//                  of the batches before it: the index K4a stamped when given
+//                  the same batches as a GroupArgs.
+// WEIGHTED (pooled blocks): the batch has weights; for a group, some batch of
+// it has, and one without them (uniform over the workgroup) adds its bag rows
+// unmultiplied.
 
 // A unit of V consecutive elements: V = 1, or 16 bytes' worth.
 template <typename T, int V>
@@ -258,28 +275,116 @@ __device__ __forceinline__ void store_opt_unit(T* p, uint64_t unit, const OptUni
 __device__ __forceinline__ bool nonzero_bits(float x) { return __float_as_uint(x) != 0u; }
 __device__ __forceinline__ bool nonzero_bits(double x) { return __double_as_longlong(x) != 0ll; }
 
-// One element per lane, as k_row_accumulate.  `tag` of an element as in
-// k_row_commit; an in-range element whose tag is not its key's stamp is a loser.
-template <typename AT>
-__global__ __launch_bounds__(kBlock) void k_row_grad_losers(GroupArgs ga, DenseView d, AT* __restrict__ gsum,
+// One multiplication rounded to T: the empty statement keeps the product out
+// of a contraction with the addition that follows, so a weighted term is the
+// same value in gsum, in a winner's step and in a host-expanded pskv_apply.
+__device__ __forceinline__ float rounded_mul(float w, float x) {
+  float r = w * x;
+  asm("" : "+v"(r));
+  return r;
+}
+__device__ __forceinline__ double rounded_mul(double w, double x) {
+  double r = w * x;
+  asm("" : "+v"(r));
+  return r;
+}
+
+// A wave-uniform value held in vector registers from here on (PIN), or left
+// to the compiler.
+template <bool PIN, typename X>
+__device__ __forceinline__ X in_vgprs(X x) {
+  if constexpr (PIN) asm("" : "+v"(x));
+  return x;
+}
+
+// The argument blocks: virtual workgroups, the batch of one (its index j, the
+// batch, its first workgroup, the group-wide index of its first position: must
+// equal K4a's elem_prefix) and where the batch's gradient rows lie.
+template <typename Args>
+constexpr bool kStepPooled = !std::is_same<Args, GroupArgs>::value;
+template <typename Args>
+constexpr bool kStepPoolGroup = std::is_same<Args, PoolGroupArgs>::value;
+
+template <typename GA>
+__device__ __forceinline__ uint32_t step_nvwg(const GA& ga) { return ga.wg_prefix[ga.nb]; }
+__device__ __forceinline__ uint32_t step_nvwg(const PoolPushArgs& a) {
+  return (uint32_t)((a.n + kGeneralChunk - 1) / kGeneralChunk);
+}
+__device__ __forceinline__ int step_batch_of(const GroupArgs& ga, uint32_t wg) { return row_batch_of(ga, wg); }
+__device__ __forceinline__ int step_batch_of(const PoolGroupArgs& ga, uint32_t wg) {
+  return pool_group_batch_of(ga, wg);
+}
+__device__ __forceinline__ int step_batch_of(const PoolPushArgs&, uint32_t) { return 0; }
+__device__ __forceinline__ DevBatch step_batch(const GroupArgs& ga, int j) { return ga.b[j]; }
+__device__ __forceinline__ const PoolBatchDesc& step_batch(const PoolGroupArgs& ga, int j) { return ga.b[j]; }
+__device__ __forceinline__ const PoolPushArgs& step_batch(const PoolPushArgs& a, int) { return a; }
+template <typename GA>
+__device__ __forceinline__ uint32_t step_first_wg(const GA& ga, int j) { return ga.wg_prefix[j]; }
+__device__ __forceinline__ uint32_t step_first_wg(const PoolPushArgs&, int) { return 0; }
+__device__ __forceinline__ uint64_t step_elem_prefix(const GroupArgs& ga, int j) { return row_elem_prefix(ga, j); }
+__device__ __forceinline__ uint64_t step_elem_prefix(const PoolGroupArgs& ga, int j) {
+  return pool_group_elem_prefix(ga, j);
+}
+__device__ __forceinline__ uint64_t step_elem_prefix(const PoolPushArgs&, int) { return 0; }
+template <typename B>
+__device__ __forceinline__ const void* step_rows(const B& b) { return b.bag_grads; }
+__device__ __forceinline__ const void* step_rows(const DevBatch& b) { return b.vals; }
+
+// The span of the bags of the workgroup at position `base` of pooled batch
+// `a` (LOOKUP; else none yet), held in vector registers (PIN) or not.
+template <bool LOOKUP, bool PIN, typename B>
+__device__ __forceinline__ PoolSpan step_span(const B& a, uint64_t base) {
+  PoolSpan sp{0, 0};
+  if constexpr (LOOKUP) {
+    const uint64_t end = base + kGeneralChunk < a.n ? base + kGeneralChunk : a.n;  // base < n of THIS batch
+    sp = pool_bag_span(a.offsets, a.nbags, base, end - 1);
+    sp.lo = in_vgprs<PIN>(sp.lo);
+    sp.hi = in_vgprs<PIN>(sp.hi);
+  }
+  return sp;
+}
+
+// The bags of a step's wanted rows in pooled batch `a`; the workgroup's span
+// is looked up at the first step that wants one (`have`), so a lane group of
+// winners only (k_row_step_losers, distinct keys) reads no offset.
+template <typename B>
+__device__ __forceinline__ void step_bags(const B& a, const uint64_t* offsets, uint64_t base, PoolSpan& sp, bool& have,
+                                          const RowStep& s, const bool (&want)[kRowsInFlight],
+                                          uint64_t (&bag)[kRowsInFlight]) {
+  if (!have) {
+    sp = step_span<true, false>(a, base);
+    have = true;
+  }
+  pool_bags_in<kRowsInFlight>(offsets, sp, s.i, want, bag);
+}
+
+// One element per lane, as k_row_accumulate.  `tag` of a position as in
+// k_row_commit; an in-range position whose tag is not its key's stamp is a loser.
+template <typename AT, typename Args, bool WEIGHTED>
+__global__ __launch_bounds__(kBlock) void k_row_step_losers(Args ga, DenseView d, AT* __restrict__ gsum,
                                                             const unsigned long long* __restrict__ owner,
                                                             uint32_t* err, uint32_t epoch, RowShape rs) {
+  static_assert(kStepPooled<Args> || !WEIGHTED, "only bag rows are weighted");
   const uint32_t lane = threadIdx.x & (rs.lanes - 1u);
   const uint32_t grp = threadIdx.x >> rs.lshift;
   const uint32_t G = (uint32_t)kBlock >> rs.lshift;
   const uint32_t U = rs.units;
-  const uint32_t nvwg = ga.wg_prefix[ga.nb];
+  const uint32_t nvwg = step_nvwg(ga);
   for (uint32_t wg = blockIdx.x; wg < nvwg; wg += gridDim.x) {
-    const int j = row_batch_of(ga, wg);
-    const uint32_t* __restrict__ keys = ga.b[j].keys;
-    const AT* __restrict__ vals = reinterpret_cast<const AT*>(ga.b[j].vals);
-    const uint64_t n = ga.b[j].n;
-    const uint64_t base = (uint64_t)(wg - ga.wg_prefix[j]) * kGeneralChunk;
-    const uint64_t gbase = row_elem_prefix(ga, j) + base;
+    const int j = step_batch_of(ga, wg);
+    decltype(auto) a = step_batch(ga, j);  // (by value or by reference: k_row_step_apply)
+    const AT* __restrict__ weights = nullptr;
+    if constexpr (kStepPooled<Args>) weights = reinterpret_cast<const AT*>(a.weights);
+    const AT* __restrict__ rows = reinterpret_cast<const AT*>(step_rows(a));
+    const bool mul = WEIGHTED && (!kStepPoolGroup<Args> || weights != nullptr);
+    const uint64_t base = (uint64_t)(wg - step_first_wg(ga, j)) * kGeneralChunk;
+    const uint64_t gbase = step_elem_prefix(ga, j) + base;
+    PoolSpan sp{0, 0};
+    bool have = false;
     for (uint32_t r0 = grp; r0 < (uint32_t)kGeneralChunk; r0 += kRowsInFlight * G) {
-      if (base + r0 >= n) break;
+      if (base + r0 >= a.n) break;
       RowStep s;
-      load_step(s, keys, n, base, r0, G, d);
+      load_step(s, a.keys, a.n, base, r0, G, d);
       bool lose[kRowsInFlight];
       bool any = false;
 #pragma unroll
@@ -290,22 +395,31 @@ __global__ __launch_bounds__(kBlock) void k_row_grad_losers(GroupArgs ga, DenseV
         if (s.live[r] && !s.in[r] && lane == 0) atomicOr(err, kErrRowOutOfRange);
       }
       if (!any) continue;  // distinct keys: only keys and stamps were read
+      // a position's gradient row: its own of `rows`, or its bag's times w[r] where mul
+      uint64_t bag[kRowsInFlight];
+      AT w[kRowsInFlight];
+      if constexpr (kStepPooled<Args>) {
+        step_bags(a, a.offsets, base, sp, have, s, lose, bag);
+#pragma unroll
+        for (int r = 0; r < kRowsInFlight; ++r) w[r] = (mul && lose[r]) ? weights[s.i[r]] : AT(1);
+      }
       for (uint32_t u = lane; u < U; u += rs.lanes) {
         AT v[kRowsInFlight];
 #pragma unroll
-        for (int r = 0; r < kRowsInFlight; ++r) v[r] = lose[r] ? vals[s.i[r] * U + u] : AT(0);
+        for (int r = 0; r < kRowsInFlight; ++r)
+          v[r] = lose[r] ? rows[(kStepPooled<Args> ? bag[r] : s.i[r]) * U + u] : AT(0);
 #pragma unroll
         for (int r = 0; r < kRowsInFlight; ++r)
-          if (lose[r]) (void)atomicAdd(gsum + (uint64_t)s.off[r] * U + u, v[r]);
+          if (lose[r]) (void)atomicAdd(gsum + (uint64_t)s.off[r] * U + u, mul ? rounded_mul(w[r], v[r]) : v[r]);
       }
     }
   }
 }
 
-// The rule on one unit, written once for k_row_apply and k_row_pooled_apply:
-// g the winner's own gradient unit, gs the key's gsum unit (set to zero), p
-// and the state units h (slot 0), h2 (slot 1) stepped in place.  Returns
-// whether gs held a non-zero bit (then its zeros are to be written back).
+// The rule on one unit: g the winner's own gradient unit, gs the key's gsum
+// unit (set to zero), p and the state units h (slot 0), h2 (slot 1) stepped in
+// place.  Returns whether gs held a non-zero bit (then its zeros are to be
+// written back).
 template <typename T, int KIND, int V>
 __device__ __forceinline__ bool opt_step_unit(const OptUnit<T, V>& g, OptUnit<T, V>& gs, OptUnit<T, V>& p,
                                               OptUnit<T, V>& h, OptUnit<T, V>& h2, const OptArgs<T>& o) {
@@ -344,313 +458,30 @@ __device__ __forceinline__ bool opt_step_unit(const OptUnit<T, V>& g, OptUnit<T,
 }
 
 // KIND: 1 = SGD, 2 = Adagrad, 3 = momentum, 4 = Adam, 5 = FTRL-Proximal
-// (pskv_optimizer_kind).  One writer per row.  `state` is slot 0 (h / v / m /
-// z), `state2` slot 1 (Adam's v, FTRL's n).  No instantiation spills with
-// kRowsInFlight rows in flight (DESIGN.md §8d and §8i have the resource
-// tables), Adam's and FTRL's five units per row included.
-template <typename T, int KIND, int V>
-__global__ __launch_bounds__(kBlock) void k_row_apply(GroupArgs ga, DenseView d, T* __restrict__ gsum,
-                                                      T* __restrict__ state, T* __restrict__ state2,
-                                                      const unsigned long long* __restrict__ owner,
-                                                      uint32_t epoch, RowShape rs, OptArgs<T> o) {
+// (pskv_optimizer_kind).  Winners only, one writer per row.  `state` is slot 0
+// (h / v / m / z), `state2` slot 1 (Adam's v, FTRL's n).  No instantiation
+// spills with kRowsInFlight rows in flight (DESIGN.md §8d, §8h and §8i have
+// the resource tables), Adam's and FTRL's five units per row included.
+template <typename T, int KIND, int V, typename Args, bool WEIGHTED>
+__global__ __launch_bounds__(kBlock) void k_row_step_apply(Args ga, DenseView d, T* __restrict__ gsum,
+                                                           T* __restrict__ state, T* __restrict__ state2,
+                                                           const unsigned long long* __restrict__ owner,
+                                                           uint32_t epoch, RowShape rs, OptArgs<T> o) {
+  static_assert(kStepPooled<Args> || !WEIGHTED, "only bag rows are weighted");
   const uint32_t lane = threadIdx.x & (rs.lanes - 1u);
   const uint32_t grp = threadIdx.x >> rs.lshift;
   const uint32_t G = (uint32_t)kBlock >> rs.lshift;
   const uint32_t U = rs.units;
   T* __restrict__ param = reinterpret_cast<T*>(d.param);
-  const uint32_t nvwg = ga.wg_prefix[ga.nb];
+  const uint32_t nvwg = step_nvwg(ga);
   for (uint32_t wg = blockIdx.x; wg < nvwg; wg += gridDim.x) {
-    const int j = row_batch_of(ga, wg);
-    const uint32_t* __restrict__ keys = ga.b[j].keys;
-    const T* __restrict__ vals = reinterpret_cast<const T*>(ga.b[j].vals);
-    const uint64_t n = ga.b[j].n;
-    const uint64_t base = (uint64_t)(wg - ga.wg_prefix[j]) * kGeneralChunk;
-    const uint64_t gbase = row_elem_prefix(ga, j) + base;
-    for (uint32_t r0 = grp; r0 < (uint32_t)kGeneralChunk; r0 += kRowsInFlight * G) {
-      if (base + r0 >= n) break;
-      RowStep s;
-      load_step(s, keys, n, base, r0, G, d);
-      bool win[kRowsInFlight];
-      bool any = false;
-#pragma unroll
-      for (int r = 0; r < kRowsInFlight; ++r) {
-        const unsigned long long tag = row_tag(epoch, gbase + r0 + (uint32_t)r * G);
-        win[r] = s.in[r] && owner[s.off[r]] == tag;
-        any |= win[r];
-      }
-      if (!any) continue;
-      for (uint32_t u = lane; u < U; u += rs.lanes) {
-        OptUnit<T, V> g[kRowsInFlight], gs[kRowsInFlight], p[kRowsInFlight], h[kRowsInFlight], h2[kRowsInFlight];
-#pragma unroll
-        for (int r = 0; r < kRowsInFlight; ++r) {
-          if (!win[r]) continue;
-          const uint64_t at = (uint64_t)s.off[r] * U + u;
-          g[r] = load_opt_unit<T, V>(vals, s.i[r] * U + u);
-          gs[r] = load_opt_unit<T, V>(gsum, at);
-          p[r] = load_opt_unit<T, V>(param, at);
-          if (KIND >= 2) h[r] = load_opt_unit<T, V>(state, at);
-          if (KIND >= 4) h2[r] = load_opt_unit<T, V>(state2, at);
-        }
-#pragma unroll
-        for (int r = 0; r < kRowsInFlight; ++r) {
-          if (!win[r]) continue;
-          const uint64_t at = (uint64_t)s.off[r] * U + u;
-          const bool dirty = opt_step_unit<T, KIND, V>(g[r], gs[r], p[r], h[r], h2[r], o);
-          store_opt_unit<T, V>(param, at, p[r]);
-          if (KIND >= 2) store_opt_unit<T, V>(state, at, h[r]);
-          if (KIND >= 4) store_opt_unit<T, V>(state2, at, h2[r]);
-          if (dirty) store_opt_unit<T, V>(gsum, at, gs[r]);
-        }
-      }
-    }
-  }
-}
-
-// ----------------------------------------------------------- pooled pushes
-// pskv_apply_pooled: pskv_apply's step with the gradient row of
-// key position i formed here, weights[i] * bag_grads[bag(i)].  One batch, so a
-// position is its own stamp index.  Position-major, k_row_grad_losers' and
-// k_row_apply's work split; the bag of a position: pskv_plan.h.
-
-// One multiplication rounded to T: the empty statement keeps the product out
-// of a contraction with the addition that follows, so a weighted term is the
-// same value in gsum, in a winner's step and in a host-expanded pskv_apply.
-__device__ __forceinline__ float rounded_mul(float w, float x) {
-  float r = w * x;
-  asm("" : "+v"(r));
-  return r;
-}
-__device__ __forceinline__ double rounded_mul(double w, double x) {
-  double r = w * x;
-  asm("" : "+v"(r));
-  return r;
-}
-
-// The bags of a step's wanted rows; the workgroup's span is looked up at the
-// first step that wants one (`have`), so a lane group of winners only
-// (k_row_pooled_grad_losers, distinct keys) reads no offset.
-__device__ __forceinline__ void push_bags(const PoolPushArgs& a, uint64_t base, PoolSpan& sp, bool& have,
-                                          const RowStep& s, const bool (&want)[kRowsInFlight],
-                                          uint64_t (&bag)[kRowsInFlight]) {
-  if (!have) {
-    const uint64_t end = base + kGeneralChunk < a.n ? base + kGeneralChunk : a.n;  // base < n
-    sp = pool_bag_span(a.offsets, a.nbags, base, end - 1);
-    have = true;
-  }
-  pool_bags_in<kRowsInFlight>(a.offsets, sp, s.i, want, bag);
-}
-
-// One element per lane, as k_row_grad_losers.
-template <typename AT, bool WEIGHTED>
-__global__ __launch_bounds__(kBlock) void k_row_pooled_grad_losers(PoolPushArgs a, DenseView d,
-                                                                   AT* __restrict__ gsum,
-                                                                   const unsigned long long* __restrict__ owner,
-                                                                   uint32_t* err, uint32_t epoch, RowShape rs) {
-  const uint32_t lane = threadIdx.x & (rs.lanes - 1u);
-  const uint32_t grp = threadIdx.x >> rs.lshift;
-  const uint32_t G = (uint32_t)kBlock >> rs.lshift;
-  const uint32_t U = rs.units;
-  const AT* __restrict__ weights = reinterpret_cast<const AT*>(a.weights);
-  const AT* __restrict__ bg = reinterpret_cast<const AT*>(a.bag_grads);
-  const uint32_t nvwg = (uint32_t)((a.n + kGeneralChunk - 1) / kGeneralChunk);
-  for (uint32_t wg = blockIdx.x; wg < nvwg; wg += gridDim.x) {
-    const uint64_t base = (uint64_t)wg * kGeneralChunk;
-    PoolSpan sp{0, 0};
-    bool have = false;
-    for (uint32_t r0 = grp; r0 < (uint32_t)kGeneralChunk; r0 += kRowsInFlight * G) {
-      if (base + r0 >= a.n) break;
-      RowStep s;
-      load_step(s, a.keys, a.n, base, r0, G, d);
-      bool lose[kRowsInFlight];
-      bool any = false;
-#pragma unroll
-      for (int r = 0; r < kRowsInFlight; ++r) {
-        const unsigned long long tag = row_tag(epoch, base + r0 + (uint32_t)r * G);
-        lose[r] = s.in[r] && owner[s.off[r]] != tag;
-        any |= lose[r];
-        if (s.live[r] && !s.in[r] && lane == 0) atomicOr(err, kErrRowOutOfRange);
-      }
-      if (!any) continue;  // distinct keys: only keys and stamps were read
-      uint64_t bag[kRowsInFlight];
-      push_bags(a, base, sp, have, s, lose, bag);
-      AT w[kRowsInFlight];
-#pragma unroll
-      for (int r = 0; r < kRowsInFlight; ++r) w[r] = (WEIGHTED && lose[r]) ? weights[s.i[r]] : AT(1);
-      for (uint32_t u = lane; u < U; u += rs.lanes) {
-        AT v[kRowsInFlight];
-#pragma unroll
-        for (int r = 0; r < kRowsInFlight; ++r) v[r] = lose[r] ? bg[bag[r] * U + u] : AT(0);
-#pragma unroll
-        for (int r = 0; r < kRowsInFlight; ++r)
-          if (lose[r]) (void)atomicAdd(gsum + (uint64_t)s.off[r] * U + u, WEIGHTED ? rounded_mul(w[r], v[r]) : v[r]);
-      }
-    }
-  }
-}
-
-// Winners only, one writer per row: k_row_apply with the winner's own gradient
-// unit weights[i] * (the bag row's unit).
-template <typename T, int KIND, int V, bool WEIGHTED>
-__global__ __launch_bounds__(kBlock) void k_row_pooled_apply(PoolPushArgs a, DenseView d, T* __restrict__ gsum,
-                                                             T* __restrict__ state, T* __restrict__ state2,
-                                                             const unsigned long long* __restrict__ owner,
-                                                             uint32_t epoch, RowShape rs, OptArgs<T> o) {
-  const uint32_t lane = threadIdx.x & (rs.lanes - 1u);
-  const uint32_t grp = threadIdx.x >> rs.lshift;
-  const uint32_t G = (uint32_t)kBlock >> rs.lshift;
-  const uint32_t U = rs.units;
-  T* __restrict__ param = reinterpret_cast<T*>(d.param);
-  const T* __restrict__ weights = reinterpret_cast<const T*>(a.weights);
-  const T* __restrict__ bg = reinterpret_cast<const T*>(a.bag_grads);
-  const uint32_t nvwg = (uint32_t)((a.n + kGeneralChunk - 1) / kGeneralChunk);
-  for (uint32_t wg = blockIdx.x; wg < nvwg; wg += gridDim.x) {
-    const uint64_t base = (uint64_t)wg * kGeneralChunk;
-    PoolSpan sp{0, 0};
-    bool have = false;
-    for (uint32_t r0 = grp; r0 < (uint32_t)kGeneralChunk; r0 += kRowsInFlight * G) {
-      if (base + r0 >= a.n) break;
-      RowStep s;
-      load_step(s, a.keys, a.n, base, r0, G, d);
-      bool win[kRowsInFlight];
-      bool any = false;
-#pragma unroll
-      for (int r = 0; r < kRowsInFlight; ++r) {
-        const unsigned long long tag = row_tag(epoch, base + r0 + (uint32_t)r * G);
-        win[r] = s.in[r] && owner[s.off[r]] == tag;
-        any |= win[r];
-      }
-      if (!any) continue;
-      uint64_t bag[kRowsInFlight];
-      push_bags(a, base, sp, have, s, win, bag);
-      T w[kRowsInFlight];
-#pragma unroll
-      for (int r = 0; r < kRowsInFlight; ++r) w[r] = (WEIGHTED && win[r]) ? weights[s.i[r]] : T(1);
-      for (uint32_t u = lane; u < U; u += rs.lanes) {
-        OptUnit<T, V> g[kRowsInFlight], gs[kRowsInFlight], p[kRowsInFlight], h[kRowsInFlight], h2[kRowsInFlight];
-#pragma unroll
-        for (int r = 0; r < kRowsInFlight; ++r) {
-          if (!win[r]) continue;
-          const uint64_t at = (uint64_t)s.off[r] * U + u;
-          g[r] = load_opt_unit<T, V>(bg, bag[r] * U + u);
-          gs[r] = load_opt_unit<T, V>(gsum, at);
-          p[r] = load_opt_unit<T, V>(param, at);
-          if (KIND >= 2) h[r] = load_opt_unit<T, V>(state, at);
-          if (KIND >= 4) h2[r] = load_opt_unit<T, V>(state2, at);
-        }
-#pragma unroll
-        for (int r = 0; r < kRowsInFlight; ++r) {
-          if (!win[r]) continue;
-          const uint64_t at = (uint64_t)s.off[r] * U + u;
-          if (WEIGHTED) {
-#pragma unroll
-            for (int i = 0; i < V; ++i) g[r].e[i] = rounded_mul(w[r], g[r].e[i]);
-          }
-          const bool dirty = opt_step_unit<T, KIND, V>(g[r], gs[r], p[r], h[r], h2[r], o);
-          store_opt_unit<T, V>(param, at, p[r]);
-          if (KIND >= 2) store_opt_unit<T, V>(state, at, h[r]);
-          if (KIND >= 4) store_opt_unit<T, V>(state2, at, h2[r]);
-          if (dirty) store_opt_unit<T, V>(gsum, at, gs[r]);
-        }
-      }
-    }
-  }
-}
-
-// --------------------------------------------------- grouped pooled pushes
-// pskv_apply_pooled_grouped: the two kernels above over a
-// launch group of pooled batches.  A virtual workgroup of kGeneralChunk
-// positions belongs to ONE batch (the wg_prefix search); its bags are looked
-// up in that batch's offsets, its span ends at that batch's last position, and
-// its tags carry the keys of the batches before it: the index K4a stamped when
-// given the same batches as a GroupArgs.  WEIGHTED: some batch of the group
-// has weights; one without them (uniform over the workgroup) adds its bag
-// rows unmultiplied.
-
-// A wave-uniform value held in vector registers from here on (PIN), or left
-// to the compiler.
-template <bool PIN, typename X>
-__device__ __forceinline__ X in_vgprs(X x) {
-  if constexpr (PIN) asm("" : "+v"(x));
-  return x;
-}
-
-// push_bags for batch `a` of a group.
-__device__ __forceinline__ void group_push_bags(const PoolBatchDesc& a, uint64_t base, PoolSpan& sp, bool& have,
-                                                const RowStep& s, const bool (&want)[kRowsInFlight],
-                                                uint64_t (&bag)[kRowsInFlight]) {
-  if (!have) {
-    const uint64_t end = base + kGeneralChunk < a.n ? base + kGeneralChunk : a.n;  // base < n of THIS batch
-    sp = pool_bag_span(a.offsets, a.nbags, base, end - 1);
-    have = true;
-  }
-  pool_bags_in<kRowsInFlight>(a.offsets, sp, s.i, want, bag);
-}
-
-template <typename AT, bool WEIGHTED>
-__global__ __launch_bounds__(kBlock) void k_row_pooled_group_grad_losers(PoolGroupArgs ga, DenseView d,
-                                                                         AT* __restrict__ gsum,
-                                                                         const unsigned long long* __restrict__ owner,
-                                                                         uint32_t* err, uint32_t epoch, RowShape rs) {
-  const uint32_t lane = threadIdx.x & (rs.lanes - 1u);
-  const uint32_t grp = threadIdx.x >> rs.lshift;
-  const uint32_t G = (uint32_t)kBlock >> rs.lshift;
-  const uint32_t U = rs.units;
-  const uint32_t nvwg = ga.wg_prefix[ga.nb];
-  for (uint32_t wg = blockIdx.x; wg < nvwg; wg += gridDim.x) {
-    const int j = pool_group_batch_of(ga, wg);
-    const PoolBatchDesc& a = ga.b[j];
-    const AT* __restrict__ weights = reinterpret_cast<const AT*>(a.weights);
-    const AT* __restrict__ bg = reinterpret_cast<const AT*>(a.bag_grads);
-    const bool mul = WEIGHTED && weights != nullptr;
-    const uint64_t base = (uint64_t)(wg - ga.wg_prefix[j]) * kGeneralChunk;
-    const uint64_t gbase = pool_group_elem_prefix(ga, j) + base;
-    PoolSpan sp{0, 0};
-    bool have = false;
-    for (uint32_t r0 = grp; r0 < (uint32_t)kGeneralChunk; r0 += kRowsInFlight * G) {
-      if (base + r0 >= a.n) break;
-      RowStep s;
-      load_step(s, a.keys, a.n, base, r0, G, d);
-      bool lose[kRowsInFlight];
-      bool any = false;
-#pragma unroll
-      for (int r = 0; r < kRowsInFlight; ++r) {
-        const unsigned long long tag = row_tag(epoch, gbase + r0 + (uint32_t)r * G);
-        lose[r] = s.in[r] && owner[s.off[r]] != tag;
-        any |= lose[r];
-        if (s.live[r] && !s.in[r] && lane == 0) atomicOr(err, kErrRowOutOfRange);
-      }
-      if (!any) continue;  // distinct keys: only keys and stamps were read
-      uint64_t bag[kRowsInFlight];
-      group_push_bags(a, base, sp, have, s, lose, bag);
-      AT w[kRowsInFlight];
-#pragma unroll
-      for (int r = 0; r < kRowsInFlight; ++r) w[r] = (mul && lose[r]) ? weights[s.i[r]] : AT(1);
-      for (uint32_t u = lane; u < U; u += rs.lanes) {
-        AT v[kRowsInFlight];
-#pragma unroll
-        for (int r = 0; r < kRowsInFlight; ++r) v[r] = lose[r] ? bg[bag[r] * U + u] : AT(0);
-#pragma unroll
-        for (int r = 0; r < kRowsInFlight; ++r)
-          if (lose[r]) (void)atomicAdd(gsum + (uint64_t)s.off[r] * U + u, mul ? rounded_mul(w[r], v[r]) : v[r]);
-      }
-    }
-  }
-}
-
-template <typename T, int KIND, int V, bool WEIGHTED>
-__global__ __launch_bounds__(kBlock) void k_row_pooled_group_apply(PoolGroupArgs ga, DenseView d,
-                                                                   T* __restrict__ gsum, T* __restrict__ state,
-                                                                   T* __restrict__ state2,
-                                                                   const unsigned long long* __restrict__ owner,
-                                                                   uint32_t epoch, RowShape rs, OptArgs<T> o) {
-  const uint32_t lane = threadIdx.x & (rs.lanes - 1u);
-  const uint32_t grp = threadIdx.x >> rs.lshift;
-  const uint32_t G = (uint32_t)kBlock >> rs.lshift;
-  const uint32_t U = rs.units;
-  T* __restrict__ param = reinterpret_cast<T*>(d.param);
-  const uint32_t nvwg = ga.wg_prefix[ga.nb];
-  for (uint32_t wg = blockIdx.x; wg < nvwg; wg += gridDim.x) {
-    const int j = pool_group_batch_of(ga, wg);
+    const int j = step_batch_of(ga, wg);
+    decltype(auto) a = step_batch(ga, j);
+    // (a plain batch is copied, so its three words are loaded here, up front; a
+    // pooled descriptor is read where it is used.  This and the order of the
+    // reads below are what the compiler's schedule hangs on: DESIGN.md §8j)
+    //
+    // A pooled group:
     // The descriptor's fields come from a computed place in the kernel
     // arguments, so unlike the single-batch kernel's they cannot be loaded
     // again where they are used, and held in scalar registers across the unit
@@ -658,21 +489,25 @@ __global__ __launch_bounds__(kBlock) void k_row_pooled_group_apply(PoolGroupArgs
     // Where that happens -- every kind with state, but for float rows taken
     // one element at a time -- what only the per-lane arithmetic in front of
     // the unit loop reads is kept in vector registers instead.
-    constexpr bool kPin = KIND >= 2 && (V > 1 || sizeof(T) > 4);
-    const uint32_t* keys = in_vgprs<kPin>(ga.b[j].keys);
-    const T* weights = reinterpret_cast<const T*>(ga.b[j].weights);
-    const uint64_t* offsets = in_vgprs<kPin>(ga.b[j].offsets);
-    const T* __restrict__ bg = reinterpret_cast<const T*>(ga.b[j].bag_grads);
-    const uint64_t n = ga.b[j].n;
-    const uint64_t base = (uint64_t)(wg - ga.wg_prefix[j]) * kGeneralChunk;
-    // the tag of the workgroup's first position; a group holds fewer than 2^32
+    constexpr bool kPin = kStepPoolGroup<Args> && KIND >= 2 && (V > 1 || sizeof(T) > 4);
+    const uint32_t* keys = in_vgprs<kPin>(a.keys);
+    const T* weights = nullptr;
+    const uint64_t* offsets = nullptr;
+    if constexpr (kStepPooled<Args>) {
+      weights = reinterpret_cast<const T*>(a.weights);
+      offsets = in_vgprs<kPin>(a.offsets);
+    }
+    const T* __restrict__ rows = reinterpret_cast<const T*>(step_rows(a));
+    const uint64_t n = a.n;
+    const uint64_t base = (uint64_t)(wg - step_first_wg(ga, j)) * kGeneralChunk;
+    const uint64_t gbase = step_elem_prefix(ga, j) + base;
+    // A pooled group: the tag of the workgroup's first position; a group holds fewer than 2^32
     // keys, so adding a position's offset never carries into the epoch
-    const unsigned long long tag0 = in_vgprs<kPin>(row_tag(epoch, pool_group_elem_prefix(ga, j) + base));
+    const unsigned long long tag0 = kStepPoolGroup<Args> ? in_vgprs<kPin>(row_tag(epoch, gbase)) : 0;
     // nearly every workgroup holds a winner: the span is looked up at once
-    const uint64_t end = base + kGeneralChunk < n ? base + kGeneralChunk : n;  // base < n of THIS batch
-    PoolSpan sp = pool_bag_span(ga.b[j].offsets, ga.b[j].nbags, base, end - 1);
-    sp.lo = in_vgprs<kPin>(sp.lo);
-    sp.hi = in_vgprs<kPin>(sp.hi);
+    // (in its declaration: assigned in a block of its own it is scheduled otherwise)
+    bool have = kStepPoolGroup<Args>;
+    PoolSpan sp = step_span<kStepPoolGroup<Args>, kPin>(a, base);
     for (uint32_t r0 = grp; r0 < (uint32_t)kGeneralChunk; r0 += kRowsInFlight * G) {
       if (base + r0 >= n) break;
       RowStep s;
@@ -681,23 +516,28 @@ __global__ __launch_bounds__(kBlock) void k_row_pooled_group_apply(PoolGroupArgs
       bool any = false;
 #pragma unroll
       for (int r = 0; r < kRowsInFlight; ++r) {
-        const unsigned long long tag = tag0 + (r0 + (uint32_t)r * G);
+        const unsigned long long tag =
+            kStepPoolGroup<Args> ? tag0 + (r0 + (uint32_t)r * G) : row_tag(epoch, gbase + r0 + (uint32_t)r * G);
         win[r] = s.in[r] && owner[s.off[r]] == tag;
         any |= win[r];
       }
       if (!any) continue;
+      // the winner's gradient row: its own of `rows`, or its bag's times w[r] where WEIGHTED
       uint64_t bag[kRowsInFlight];
-      pool_bags_in<kRowsInFlight>(offsets, sp, s.i, win, bag);
       T w[kRowsInFlight];
+      if constexpr (kStepPooled<Args>) {
+        step_bags(a, offsets, base, sp, have, s, win, bag);
 #pragma unroll
-      for (int r = 0; r < kRowsInFlight; ++r) w[r] = (WEIGHTED && weights && win[r]) ? weights[s.i[r]] : T(1);
+        for (int r = 0; r < kRowsInFlight; ++r)
+          w[r] = (WEIGHTED && (kStepPoolGroup<Args> ? weights != nullptr : true) && win[r]) ? weights[s.i[r]] : T(1);
+      }
       for (uint32_t u = lane; u < U; u += rs.lanes) {
         OptUnit<T, V> g[kRowsInFlight], gs[kRowsInFlight], p[kRowsInFlight], h[kRowsInFlight], h2[kRowsInFlight];
 #pragma unroll
         for (int r = 0; r < kRowsInFlight; ++r) {
           if (!win[r]) continue;
           const uint64_t at = (uint64_t)s.off[r] * U + u;
-          g[r] = load_opt_unit<T, V>(bg, bag[r] * U + u);
+          g[r] = load_opt_unit<T, V>(rows, (kStepPooled<Args> ? bag[r] : s.i[r]) * U + u);
           gs[r] = load_opt_unit<T, V>(gsum, at);
           p[r] = load_opt_unit<T, V>(param, at);
           if (KIND >= 2) h[r] = load_opt_unit<T, V>(state, at);
@@ -707,7 +547,7 @@ __global__ __launch_bounds__(kBlock) void k_row_pooled_group_apply(PoolGroupArgs
         for (int r = 0; r < kRowsInFlight; ++r) {
           if (!win[r]) continue;
           const uint64_t at = (uint64_t)s.off[r] * U + u;
-          if (WEIGHTED) {  // (a batch without weights: times one, exact)
+          if (WEIGHTED) {  // (a batch of a group without weights: times one, exact)
 #pragma unroll
             for (int i = 0; i < V; ++i) g[r].e[i] = rounded_mul(w[r], g[r].e[i]);
           }
@@ -761,61 +601,60 @@ OptArgs<T> round_opt_args(const OptArgs<double>& h) {
   return o;
 }
 
-template <typename T, int V>
-void launch_row_apply_kind(int kind, uint32_t grid, const GroupArgs& ga, const DenseView& d, void* gsum,
-                           void* const state[2], const unsigned long long* owner, uint32_t epoch, const RowShape& rs,
-                           const OptArgs<T>& o, hipStream_t st) {
-  T* g = static_cast<T*>(gsum);
-  T* s1 = static_cast<T*>(state[0]);
-  T* s2 = static_cast<T*>(state[1]);
+// f(K) with K the std::integral_constant of optimizer kind `kind` (1 to 5:
+// opt_kind_ok), so that a kind reaches the kernels as a template argument in
+// one place.
+template <typename F>
+void with_opt_kind(int kind, F&& f) {
   if (kind == 5)
-    k_row_apply<T, 5, V><<<grid, kBlock, 0, st>>>(ga, d, g, s1, s2, owner, epoch, rs, o);
+    f(std::integral_constant<int, 5>());
   else if (kind == 4)
-    k_row_apply<T, 4, V><<<grid, kBlock, 0, st>>>(ga, d, g, s1, s2, owner, epoch, rs, o);
+    f(std::integral_constant<int, 4>());
   else if (kind == 3)
-    k_row_apply<T, 3, V><<<grid, kBlock, 0, st>>>(ga, d, g, s1, s2, owner, epoch, rs, o);
+    f(std::integral_constant<int, 3>());
   else if (kind == 2)
-    k_row_apply<T, 2, V><<<grid, kBlock, 0, st>>>(ga, d, g, s1, s2, owner, epoch, rs, o);
+    f(std::integral_constant<int, 2>());
   else
-    k_row_apply<T, 1, V><<<grid, kBlock, 0, st>>>(ga, d, g, s1, s2, owner, epoch, rs, o);
+    f(std::integral_constant<int, 1>());
 }
 
-template <typename T, int V, bool WEIGHTED>
-void launch_row_pooled_apply_kind(int kind, uint32_t grid, const PoolPushArgs& a, const DenseView& d, void* gsum,
-                                  void* const state[2], const unsigned long long* owner, uint32_t epoch,
-                                  const RowShape& rs, const OptArgs<T>& o, hipStream_t st) {
-  T* g = static_cast<T*>(gsum);
-  T* s1 = static_cast<T*>(state[0]);
-  T* s2 = static_cast<T*>(state[1]);
-  if (kind == 5)
-    k_row_pooled_apply<T, 5, V, WEIGHTED><<<grid, kBlock, 0, st>>>(a, d, g, s1, s2, owner, epoch, rs, o);
-  else if (kind == 4)
-    k_row_pooled_apply<T, 4, V, WEIGHTED><<<grid, kBlock, 0, st>>>(a, d, g, s1, s2, owner, epoch, rs, o);
-  else if (kind == 3)
-    k_row_pooled_apply<T, 3, V, WEIGHTED><<<grid, kBlock, 0, st>>>(a, d, g, s1, s2, owner, epoch, rs, o);
-  else if (kind == 2)
-    k_row_pooled_apply<T, 2, V, WEIGHTED><<<grid, kBlock, 0, st>>>(a, d, g, s1, s2, owner, epoch, rs, o);
-  else
-    k_row_pooled_apply<T, 1, V, WEIGHTED><<<grid, kBlock, 0, st>>>(a, d, g, s1, s2, owner, epoch, rs, o);
+// A known kind with the state slots it steps.
+bool opt_kind_ok(int kind, void* const state[2]) {
+  return kind >= 1 && kind <= 5 && (kind < 2 || state[0]) && (kind < 4 || state[1]);
 }
 
-template <typename T, int V, bool WEIGHTED>
-void launch_row_pooled_group_apply_kind(int kind, uint32_t grid, const PoolGroupArgs& ga, const DenseView& d,
-                                        void* gsum, void* const state[2], const unsigned long long* owner,
-                                        uint32_t epoch, const RowShape& rs, const OptArgs<T>& o, hipStream_t st) {
-  T* g = static_cast<T*>(gsum);
-  T* s1 = static_cast<T*>(state[0]);
-  T* s2 = static_cast<T*>(state[1]);
-  if (kind == 5)
-    k_row_pooled_group_apply<T, 5, V, WEIGHTED><<<grid, kBlock, 0, st>>>(ga, d, g, s1, s2, owner, epoch, rs, o);
-  else if (kind == 4)
-    k_row_pooled_group_apply<T, 4, V, WEIGHTED><<<grid, kBlock, 0, st>>>(ga, d, g, s1, s2, owner, epoch, rs, o);
-  else if (kind == 3)
-    k_row_pooled_group_apply<T, 3, V, WEIGHTED><<<grid, kBlock, 0, st>>>(ga, d, g, s1, s2, owner, epoch, rs, o);
-  else if (kind == 2)
-    k_row_pooled_group_apply<T, 2, V, WEIGHTED><<<grid, kBlock, 0, st>>>(ga, d, g, s1, s2, owner, epoch, rs, o);
-  else
-    k_row_pooled_group_apply<T, 1, V, WEIGHTED><<<grid, kBlock, 0, st>>>(ga, d, g, s1, s2, owner, epoch, rs, o);
+// f(W) with W whether the block's kernels multiply by weights: for a group,
+// some batch of it has them.  Rows given by value have none.
+template <typename F>
+void with_step_weights(const GroupArgs&, F&& f) {
+  f(std::false_type());
+}
+template <typename F>
+void with_step_weights(const PoolPushArgs& a, F&& f) {
+  a.weights ? f(std::true_type()) : f(std::false_type());
+}
+template <typename F>
+void with_step_weights(const PoolGroupArgs& ga, F&& f) {
+  bool weighted = false;
+  for (int j = 0; j < ga.nb; ++j) weighted |= ga.b[j].weights != nullptr;
+  weighted ? f(std::true_type()) : f(std::false_type());
+}
+
+// An argument block as the step kernels assume it, nwg its virtual workgroups
+// (> 0).  GroupArgs: as make_group built it.  PoolPushArgs: one batch of 1 to
+// kMaxPiece keys and at least one bag.  PoolGroupArgs: 1 to kMaxPoolBatches
+// such batches.
+bool step_args_ok(const GroupArgs&, uint32_t) { return true; }
+bool step_args_ok(const PoolPushArgs& a, uint32_t nwg) {
+  return a.n != 0 && a.n <= kMaxPiece && a.nbags != 0 && nwg == (a.n + kGeneralChunk - 1) / kGeneralChunk;
+}
+bool step_args_ok(const PoolGroupArgs& ga, uint32_t nwg) {
+  if (ga.nb < 1 || ga.nb > kMaxPoolBatches || ga.wg_prefix[ga.nb] != nwg) return false;
+  for (int j = 0; j < ga.nb; ++j)
+    if (ga.b[j].n == 0 || ga.b[j].n > kMaxPiece || ga.b[j].nbags == 0 ||
+        ga.wg_prefix[j + 1] - ga.wg_prefix[j] != (ga.b[j].n + kGeneralChunk - 1) / kGeneralChunk)
+      return false;
+  return true;
 }
 
 // ----------------------------------------------------------- pooled pulls
@@ -1097,136 +936,61 @@ hipError_t launch_row_accumulate(int dtype, const GroupArgs& ga, uint32_t nwg, c
   return hipGetLastError();
 }
 
-hipError_t launch_row_grad_losers(int dtype, const GroupArgs& ga, uint32_t nwg, const DenseView& d, void* gsum,
-                                  const unsigned long long* owner, const Ovf& o, uint32_t epoch,
-                                  const RowShape& rs, hipStream_t st) {
+template <typename Args>
+hipError_t launch_row_step_losers(int dtype, const Args& a, uint32_t nwg, const DenseView& d, void* gsum,
+                                  const unsigned long long* owner, const Ovf& o, uint32_t epoch, const RowShape& rs,
+                                  hipStream_t st) {
   if (nwg == 0) return hipSuccess;
+  if (!step_args_ok(a, nwg)) return hipErrorInvalidValue;
   const uint32_t grid = row_grid(nwg);
   uint32_t* err = &o.c->stat[1];
   return with_float_type(dtype, [&](auto z) {
     using T = decltype(z);
-    k_row_grad_losers<T><<<grid, kBlock, 0, st>>>(ga, d, static_cast<T*>(gsum), owner, err, epoch, rs);
+    with_step_weights(a, [&](auto w) {
+      k_row_step_losers<T, Args, decltype(w)::value>
+          <<<grid, kBlock, 0, st>>>(a, d, static_cast<T*>(gsum), owner, err, epoch, rs);
+    });
   });
 }
 
-hipError_t launch_row_apply(int dtype, int kind, const GroupArgs& ga, uint32_t nwg, const DenseView& d, void* gsum,
-                            void* const state[2], const unsigned long long* owner, uint32_t epoch,
-                            const RowShape& rs, const OptArgs<double>& hy, hipStream_t st) {
+template <typename Args>
+hipError_t launch_row_step_apply(int dtype, int kind, const Args& a, uint32_t nwg, const DenseView& d, void* gsum,
+                                 void* const state[2], const unsigned long long* owner, uint32_t epoch,
+                                 const RowShape& rs, const OptArgs<double>& hy, hipStream_t st) {
   if (nwg == 0) return hipSuccess;
-  if (kind < 1 || kind > 5 || (kind >= 2 && !state[0]) || (kind >= 4 && !state[1])) return hipErrorInvalidValue;
+  if (!step_args_ok(a, nwg) || !opt_kind_ok(kind, state)) return hipErrorInvalidValue;
   const uint32_t grid = row_grid(nwg);
   return with_float_type(dtype, [&](auto z) {
     using T = decltype(z);
     const OptArgs<T> o = round_opt_args<T>(hy);
-    if (rs.unit_bytes == 16)
-      launch_row_apply_kind<T, 16 / sizeof(T)>(kind, grid, ga, d, gsum, state, owner, epoch, rs, o, st);
-    else
-      launch_row_apply_kind<T, 1>(kind, grid, ga, d, gsum, state, owner, epoch, rs, o, st);
+    T* g = static_cast<T*>(gsum);
+    T* s1 = static_cast<T*>(state[0]);
+    T* s2 = static_cast<T*>(state[1]);
+    with_opt_kind(kind, [&](auto k) {
+      with_step_weights(a, [&](auto w) {
+        constexpr int K = decltype(k)::value;
+        constexpr bool W = decltype(w)::value;
+        constexpr int V16 = 16 / sizeof(T);
+        if (rs.unit_bytes == 16)
+          k_row_step_apply<T, K, V16, Args, W><<<grid, kBlock, 0, st>>>(a, d, g, s1, s2, owner, epoch, rs, o);
+        else
+          k_row_step_apply<T, K, 1, Args, W><<<grid, kBlock, 0, st>>>(a, d, g, s1, s2, owner, epoch, rs, o);
+      });
+    });
   });
 }
 
-// Virtual workgroups of a pooled push: kGeneralChunk positions each, as the
-// mark's over the same single batch (n <= kMaxPiece).
-static uint32_t push_grid(const PoolPushArgs& a) {
-  return row_grid((uint32_t)((a.n + kGeneralChunk - 1) / kGeneralChunk));
-}
-
-hipError_t launch_row_pooled_grad_losers(int dtype, const PoolPushArgs& a, const DenseView& d, void* gsum,
-                                         const unsigned long long* owner, const Ovf& o, uint32_t epoch,
-                                         const RowShape& rs, hipStream_t st) {
-  if (a.n == 0) return hipSuccess;
-  if (a.n > kMaxPiece || a.nbags == 0) return hipErrorInvalidValue;
-  const uint32_t grid = push_grid(a);
-  uint32_t* err = &o.c->stat[1];
-  return with_float_type(dtype, [&](auto z) {
-    using T = decltype(z);
-    if (a.weights)
-      k_row_pooled_grad_losers<T, true><<<grid, kBlock, 0, st>>>(a, d, static_cast<T*>(gsum), owner, err, epoch, rs);
-    else
-      k_row_pooled_grad_losers<T, false><<<grid, kBlock, 0, st>>>(a, d, static_cast<T*>(gsum), owner, err, epoch, rs);
-  });
-}
-
-hipError_t launch_row_pooled_apply(int dtype, int kind, const PoolPushArgs& a, const DenseView& d, void* gsum,
-                                   void* const state[2], const unsigned long long* owner, uint32_t epoch,
-                                   const RowShape& rs, const OptArgs<double>& hy, hipStream_t st) {
-  if (a.n == 0) return hipSuccess;
-  if (a.n > kMaxPiece || a.nbags == 0) return hipErrorInvalidValue;
-  if (kind < 1 || kind > 5 || (kind >= 2 && !state[0]) || (kind >= 4 && !state[1])) return hipErrorInvalidValue;
-  const uint32_t grid = push_grid(a);
-  return with_float_type(dtype, [&](auto z) {
-    using T = decltype(z);
-    const OptArgs<T> o = round_opt_args<T>(hy);
-    constexpr int V16 = 16 / sizeof(T);
-    if (rs.unit_bytes == 16) {
-      if (a.weights)
-        launch_row_pooled_apply_kind<T, V16, true>(kind, grid, a, d, gsum, state, owner, epoch, rs, o, st);
-      else
-        launch_row_pooled_apply_kind<T, V16, false>(kind, grid, a, d, gsum, state, owner, epoch, rs, o, st);
-    } else {
-      if (a.weights)
-        launch_row_pooled_apply_kind<T, 1, true>(kind, grid, a, d, gsum, state, owner, epoch, rs, o, st);
-      else
-        launch_row_pooled_apply_kind<T, 1, false>(kind, grid, a, d, gsum, state, owner, epoch, rs, o, st);
-    }
-  });
-}
-
-// A launch group of pooled batches as the kernels assume it: 1 to
-// kMaxPoolBatches batches, each of 1 to kMaxPiece keys and at least one bag,
-// nwg the group's virtual workgroups.
-static bool pool_group_ok(const PoolGroupArgs& ga, uint32_t nwg) {
-  if (ga.nb < 1 || ga.nb > kMaxPoolBatches || ga.wg_prefix[ga.nb] != nwg) return false;
-  for (int j = 0; j < ga.nb; ++j)
-    if (ga.b[j].n == 0 || ga.b[j].n > kMaxPiece || ga.b[j].nbags == 0 ||
-        ga.wg_prefix[j + 1] - ga.wg_prefix[j] != (ga.b[j].n + kGeneralChunk - 1) / kGeneralChunk)
-      return false;
-  return true;
-}
-
-hipError_t launch_row_pooled_group_grad_losers(int dtype, const PoolGroupArgs& ga, uint32_t nwg, bool weighted,
-                                               const DenseView& d, void* gsum, const unsigned long long* owner,
-                                               const Ovf& o, uint32_t epoch, const RowShape& rs, hipStream_t st) {
-  if (nwg == 0) return hipSuccess;
-  if (!pool_group_ok(ga, nwg)) return hipErrorInvalidValue;
-  const uint32_t grid = row_grid(nwg);
-  uint32_t* err = &o.c->stat[1];
-  return with_float_type(dtype, [&](auto z) {
-    using T = decltype(z);
-    if (weighted)
-      k_row_pooled_group_grad_losers<T, true>
-          <<<grid, kBlock, 0, st>>>(ga, d, static_cast<T*>(gsum), owner, err, epoch, rs);
-    else
-      k_row_pooled_group_grad_losers<T, false>
-          <<<grid, kBlock, 0, st>>>(ga, d, static_cast<T*>(gsum), owner, err, epoch, rs);
-  });
-}
-
-hipError_t launch_row_pooled_group_apply(int dtype, int kind, const PoolGroupArgs& ga, uint32_t nwg, bool weighted,
-                                         const DenseView& d, void* gsum, void* const state[2],
-                                         const unsigned long long* owner, uint32_t epoch, const RowShape& rs,
-                                         const OptArgs<double>& hy, hipStream_t st) {
-  if (nwg == 0) return hipSuccess;
-  if (!pool_group_ok(ga, nwg)) return hipErrorInvalidValue;
-  if (kind < 1 || kind > 5 || (kind >= 2 && !state[0]) || (kind >= 4 && !state[1])) return hipErrorInvalidValue;
-  const uint32_t grid = row_grid(nwg);
-  return with_float_type(dtype, [&](auto z) {
-    using T = decltype(z);
-    const OptArgs<T> o = round_opt_args<T>(hy);
-    constexpr int V16 = 16 / sizeof(T);
-    if (rs.unit_bytes == 16) {
-      if (weighted)
-        launch_row_pooled_group_apply_kind<T, V16, true>(kind, grid, ga, d, gsum, state, owner, epoch, rs, o, st);
-      else
-        launch_row_pooled_group_apply_kind<T, V16, false>(kind, grid, ga, d, gsum, state, owner, epoch, rs, o, st);
-    } else {
-      if (weighted)
-        launch_row_pooled_group_apply_kind<T, 1, true>(kind, grid, ga, d, gsum, state, owner, epoch, rs, o, st);
-      else
-        launch_row_pooled_group_apply_kind<T, 1, false>(kind, grid, ga, d, gsum, state, owner, epoch, rs, o, st);
-    }
-  });
-}
+#define PSKV_STEP_LAUNCHERS(Args)                                                                                \
+  template hipError_t launch_row_step_losers<Args>(int, const Args&, uint32_t, const DenseView&, void*,         \
+                                                   const unsigned long long*, const Ovf&, uint32_t,             \
+                                                   const RowShape&, hipStream_t);                               \
+  template hipError_t launch_row_step_apply<Args>(int, int, const Args&, uint32_t, const DenseView&, void*,     \
+                                                  void* const[2], const unsigned long long*, uint32_t,          \
+                                                  const RowShape&, const OptArgs<double>&, hipStream_t)
+PSKV_STEP_LAUNCHERS(GroupArgs);
+PSKV_STEP_LAUNCHERS(PoolPushArgs);
+PSKV_STEP_LAUNCHERS(PoolGroupArgs);
+#undef PSKV_STEP_LAUNCHERS
 
 hipError_t launch_fill(int dtype, void* p, uint64_t n, double v, hipStream_t st) {
   if (n == 0) return hipSuccess;

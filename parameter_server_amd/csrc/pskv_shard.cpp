@@ -1760,6 +1760,35 @@ int rows_get(pskv_shard* s, const std::vector<pskv_batch>& in, int flags) {
   return rows_get_from(s, in, flags, s->dview(), "pskv_get", &s->n_get);
 }
 
+// Host pooled batches -> device staging through pinned staging, batch after
+// batch (pool_stage_layout): keys, weights where the batch has them and
+// offsets -- and, with_rows, the bag rows of a push -- are copied in and
+// queued for DMA; a pull's rows get room behind them.  Returns the device-side
+// batches in `dv`; the pinned copy of a range lies at the same offset of
+// hstage.
+int stage_pool_batches(pskv_shard* s, const std::vector<pskv_pool_batch>& v, bool with_rows, HstageHold& hold,
+                       std::vector<pskv_pool_batch>* dv) {
+  const size_t rb = row_bytes(s);
+  const PoolStageLayout lay = pool_stage_layout(v, (size_t)s->vb, rb);
+  int rc = ensure_hstage(s, lay.total);
+  if (rc || (rc = ensure_dstage(s, lay.total))) return rc;
+  char* h = static_cast<char*>(s->hstage);
+  char* d = static_cast<char*>(s->dstage);
+  std::vector<Piece> pieces;
+  dv->resize(v.size());
+  for (size_t i = 0; i < v.size(); ++i) {
+    const pskv_pool_batch& b = v[i];
+    const PoolStageSlot& at = lay.at[i];
+    add_pieces(pieces, b.keys, h + at.keys, b.n * 4, -1);
+    if (b.weights) add_pieces(pieces, b.weights, h + at.weights, b.n * (size_t)s->vb, -1);
+    add_pieces(pieces, b.offsets, h + at.offsets, (b.nbags + 1) * sizeof(uint64_t), -1);
+    if (with_rows) add_pieces(pieces, b.bag_grads, h + at.rows, b.nbags * rb, -1);
+    (*dv)[i] = pskv_pool_batch{reinterpret_cast<const uint32_t*>(d + at.keys), b.weights ? d + at.weights : nullptr,
+                               reinterpret_cast<const uint64_t*>(d + at.offsets), d + at.rows, b.n, b.nbags};
+  }
+  return pipelined_h2d(s, pieces, h, d, hold);
+}
+
 // ------------------------------------------------------------ pooled pulls
 // pskv_get_pooled (pskv.h "Pooled pulls"), at any width, 1
 // included.  One or two launches, timed as one operation (kTimePooled):
@@ -1810,30 +1839,20 @@ int pooled_impl(pskv_shard* s, const PoolCall& call, int flags) {
     if ((rc = use_device(s)) || (rc = srv_stop(s))) return rc;
   }
   if (flags & PSKV_DEVICE) return pooled_device(s, call);
-  // host buffers: keys, weights, offsets into the pinned staging and on to the
-  // device staging, 16-byte aligned, the pooled rows behind them
+  // host buffers: through the staging, the pooled rows behind keys, weights and offsets
   const size_t rb = row_bytes(s);
-  const size_t wo = round16(call.n * 4);
-  const size_t oo = wo + (call.weights ? round16(call.n * (size_t)s->vb) : 0);
-  const size_t ro = oo + round16((call.nbags + 1) * sizeof(uint64_t));
-  const size_t total = ro + round16(call.nbags * rb);
   HstageHold hold(s);
-  if ((rc = ensure_hstage(s, total)) || (rc = ensure_dstage(s, total))) return rc;
-  char* h = static_cast<char*>(s->hstage);
-  char* d = static_cast<char*>(s->dstage);
-  std::vector<Piece> pieces;
-  add_pieces(pieces, call.keys, h, call.n * 4, -1);
-  if (call.weights) add_pieces(pieces, call.weights, h + wo, call.n * (size_t)s->vb, -1);
-  add_pieces(pieces, call.offsets, h + oo, (call.nbags + 1) * sizeof(uint64_t), -1);
-  if ((rc = pipelined_h2d(s, pieces, h, d, hold))) return rc;
-  const PoolCall dc{reinterpret_cast<const uint32_t*>(d), call.n, call.weights ? d + wo : nullptr,
-                    reinterpret_cast<const uint64_t*>(d + oo), call.nbags, d + ro};
-  if ((rc = pooled_device(s, dc))) return rc;
-  PSKV_HIP(hipMemcpyAsync(h + ro, d + ro, call.nbags * rb, hipMemcpyDeviceToHost, s->stream));
+  std::vector<pskv_pool_batch> dv;
+  const pskv_pool_batch one{call.keys, call.weights, call.offsets, call.out, call.n, call.nbags};
+  if ((rc = stage_pool_batches(s, {one}, /*with_rows=*/false, hold, &dv))) return rc;
+  char* d = static_cast<char*>(const_cast<void*>(dv[0].bag_grads));  // the rows' room in dstage
+  char* h = static_cast<char*>(s->hstage) + (d - static_cast<char*>(s->dstage));
+  if ((rc = pooled_device(s, PoolCall{dv[0].keys, call.n, dv[0].weights, dv[0].offsets, call.nbags, d}))) return rc;
+  PSKV_HIP(hipMemcpyAsync(h, d, call.nbags * rb, hipMemcpyDeviceToHost, s->stream));
   if ((rc = wait_stream(s, s->stream, "shard stream (pooled pull to host)"))) return rc;
   hold.dismiss();
   std::vector<Piece> back;
-  add_pieces(back, h + ro, static_cast<char*>(call.out), call.nbags * rb, -1);
+  add_pieces(back, h, static_cast<char*>(call.out), call.nbags * rb, -1);
   run_copies(s, back, 0, back.size());
   return PSKV_OK;
 }
@@ -1841,10 +1860,10 @@ int pooled_impl(pskv_shard* s, const PoolCall& call, int flags) {
 // -------------------------------------------------------- optimizer steps
 // pskv_apply (pskv.h): one call is one step.  Any width, 1
 // included: a width-1 shard's step runs on these row kernels, not on the
-// scalar paths.  Launches per call of G launch groups (split_groups):
+// scalar paths.  Launches per call of G launch groups (step_device):
 //   G x K4a (stamp mode, one epoch per group)   the winner element of each key
-//   G x k_row_grad_losers                       every other element's row -> gsum
-//   G x k_row_apply                             each winner steps its key's row
+//   G x k_row_step_losers                       every other element's row -> gsum
+//   G x k_row_step_apply                        each winner steps its key's row
 // All marks come first: a key's stamp then belongs to the last group that
 // holds it, the key's elements in earlier groups all see a foreign stamp and
 // go to gsum, and exactly one element of the call applies the rule.
@@ -1899,20 +1918,34 @@ int opt_reset_state(pskv_shard* s) {
   return PSKV_OK;
 }
 
-int apply_device(pskv_shard* s, const std::vector<pskv_batch>& v) {
+// One step, timed as one operation (kTimeApply).  `marks`: the call's batches
+// as the mark takes them (keys and n; vals: where the kernels read the batch's
+// rows), `spans` their launch groups; args_of(mark group, span): the argument
+// block of a group's loser and apply passes (GroupArgs, PoolPushArgs or
+// PoolGroupArgs, pskv_internal.h).
+template <typename Args, typename ArgsOf>
+int step_device(pskv_shard* s, const std::vector<pskv_batch>& marks, const std::vector<Span>& spans,
+                const ArgsOf& args_of) {
   if (int rc = ensure_owner(s)) return rc;
-  const bool vec = rows_unit16(s, {s->dense, s->opt_gsum, s->opt_slot[0], s->opt_slot[1]}, v);
-  const std::vector<Span> spans = split_groups(v);
-  std::vector<LaunchGroup> groups;
-  std::vector<uint32_t> epochs;
+  // 16-byte units for the whole call or for none of it
+  const bool vec = rows_unit16(s, {s->dense, s->opt_gsum, s->opt_slot[0], s->opt_slot[1]}, marks);
+  struct Group {
+    LaunchGroup mark;
+    Args a;
+    uint32_t epoch;
+  };
+  std::vector<Group> groups(spans.size());
   uint64_t elems = 0;
   // the call's epochs must not straddle a wrap-around (next_epoch resets the
-  // stamps there): take the wrap first
+  // stamps there): take the wrap first.  (One group: nothing to do here,
+  // next_epoch takes a wrap-around itself.)
   if (0xFFFFFFFFu - s->epoch < spans.size()) s->epoch = 0xFFFFFFFFu;
-  for (const Span& sp : spans) {
-    groups.push_back(make_group(v, sp.first, sp.second, kGeneralChunk));
-    epochs.push_back(next_epoch(s));
-    elems += groups.back().elems;
+  for (size_t i = 0; i < spans.size(); ++i) {
+    Group& g = groups[i];
+    g.mark = make_group(marks, spans[i].first, spans[i].second, kGeneralChunk);
+    g.a = args_of(g.mark, spans[i]);
+    g.epoch = next_epoch(s);
+    elems += g.mark.elems;
   }
   // one step number for the whole call, whatever its launch groups
   const OptArgs<double> hy = opt_args(s->opt, ++s->opt_step);
@@ -1920,18 +1953,22 @@ int apply_device(pskv_shard* s, const std::vector<pskv_batch>& v) {
   const RowShape rsv = row_shape(s->width, s->vb, vec);
   LaunchTimer t(s, kTimeApply, elems);
   t.count = groups.size();
-  for (size_t i = 0; i < groups.size(); ++i)
-    PSKV_HIP(launch_general_mark(s->dtype, PSKV_ASSIGN, groups[i].ga, groups[i].nwg, s->dview(), s->flag + 1,
-                                 s->owner, nullptr, epochs[i], s->stream));
-  for (size_t i = 0; i < groups.size(); ++i)
-    PSKV_HIP(launch_row_grad_losers(s->dtype, groups[i].ga, groups[i].nwg, s->dview(), s->opt_gsum, s->owner, s->ovf,
-                                    epochs[i], rs1, s->stream));
-  for (size_t i = 0; i < groups.size(); ++i)
-    PSKV_HIP(launch_row_apply(s->dtype, s->opt.kind, groups[i].ga, groups[i].nwg, s->dview(), s->opt_gsum,
-                              s->opt_slot, s->owner, epochs[i], rsv, hy, s->stream));
+  for (const Group& g : groups)
+    PSKV_HIP(launch_general_mark(s->dtype, PSKV_ASSIGN, g.mark.ga, g.mark.nwg, s->dview(), s->flag + 1, s->owner,
+                                 nullptr, g.epoch, s->stream));
+  for (const Group& g : groups)
+    PSKV_HIP(launch_row_step_losers(s->dtype, g.a, g.mark.nwg, s->dview(), s->opt_gsum, s->owner, s->ovf, g.epoch, rs1,
+                                    s->stream));
+  for (const Group& g : groups)
+    PSKV_HIP(launch_row_step_apply(s->dtype, s->opt.kind, g.a, g.mark.nwg, s->dview(), s->opt_gsum, s->opt_slot,
+                                   s->owner, g.epoch, rsv, hy, s->stream));
   t.done();
   s->n_general += 3 * groups.size();
   return PSKV_OK;
+}
+
+int apply_device(pskv_shard* s, const std::vector<pskv_batch>& v) {
+  return step_device<GroupArgs>(s, v, split_groups(v), [](const LaunchGroup& mark, const Span&) { return mark.ga; });
 }
 
 int apply_impl(pskv_shard* s, const std::vector<pskv_batch>& in, int flags) {
@@ -1953,145 +1990,62 @@ int apply_impl(pskv_shard* s, const std::vector<pskv_batch>& in, int flags) {
 // ----------------------------------------------------------- pooled pushes
 // pskv_apply_pooled (pskv.h "Pooled pushes"): pskv_apply's step
 // for one batch whose gradient rows the kernels form themselves,
-// weights[i] * bag_grads[bag(i)].  One launch group (n <= kMaxPiece), three
-// launches, timed as one operation in pskv_apply's slot (kTimeApply):
-//   K4a (stamp mode, unchanged: it reads keys only)   the winner element of each key
-//   k_row_pooled_grad_losers                          every other element's row -> gsum
-//   k_row_pooled_apply                                each winner steps its key's row
+// weights[i] * bag_grads[bag(i)].  One launch group (n <= kMaxPiece) of
+// step_device, its passes over a PoolPushArgs; K4a is unchanged, it reads keys
+// only.  pskv_apply_pooled_grouped (pskv.h "Grouped pooled pushes", DESIGN.md
+// §8h): the pooled pushes of several workers as ONE step, the live batches cut
+// into launch groups (pool_split_groups), the passes over a PoolGroupArgs each.
 // The offsets stay where the caller has them: a device call's launches do not
 // depend on them, the kernels' bag lookup stays below nbags whatever they hold.
-struct PoolPush {
-  const uint32_t* keys;
-  uint64_t n;
-  const void* weights;  // or null
-  const uint64_t* offsets;
-  uint64_t nbags;
-  const void* bag_grads;
-};
+// `v`: live batches where the kernels read them.
+int apply_pooled_device(pskv_shard* s, const pskv_pool_batch& c) {
+  return step_device<PoolPushArgs>(s, pool_mark_batches({c}), {Span{0, 1}}, [&](const LaunchGroup&, const Span&) {
+    return PoolPushArgs{c.keys, c.weights, c.offsets, c.n, c.nbags, c.bag_grads};
+  });
+}
 
-int apply_pooled_device(pskv_shard* s, const PoolPush& c) {
-  if (int rc = ensure_owner(s)) return rc;
-  const std::vector<pskv_batch> v{pskv_batch{c.keys, const_cast<void*>(c.bag_grads), c.n}};
-  const bool vec = rows_unit16(s, {s->dense, s->opt_gsum, s->opt_slot[0], s->opt_slot[1]}, v);
-  const LaunchGroup g = make_group(v, 0, 1, kGeneralChunk);
-  const uint32_t epoch = next_epoch(s);  // one epoch: next_epoch takes a wrap-around itself
-  const OptArgs<double> hy = opt_args(s->opt, ++s->opt_step);
-  const PoolPushArgs a{c.keys, c.weights, c.offsets, c.n, c.nbags, c.bag_grads};
-  LaunchTimer t(s, kTimeApply, c.n);
-  PSKV_HIP(launch_general_mark(s->dtype, PSKV_ASSIGN, g.ga, g.nwg, s->dview(), s->flag + 1, s->owner, nullptr, epoch,
-                               s->stream));
-  PSKV_HIP(launch_row_pooled_grad_losers(s->dtype, a, s->dview(), s->opt_gsum, s->owner, s->ovf, epoch,
-                                         row_shape(s->width, s->vb, false), s->stream));
-  PSKV_HIP(launch_row_pooled_apply(s->dtype, s->opt.kind, a, s->dview(), s->opt_gsum, s->opt_slot, s->owner, epoch,
-                                   row_shape(s->width, s->vb, vec), hy, s->stream));
-  t.done();
-  s->n_general += 3;
-  return PSKV_OK;
+int apply_pooled_grouped_device(pskv_shard* s, const std::vector<pskv_pool_batch>& v) {
+  return step_device<PoolGroupArgs>(s, pool_mark_batches(v), pool_split_groups(v),
+                                    [&](const LaunchGroup&, const Span& sp) {
+                                      uint32_t nwg = 0;
+                                      uint64_t elems = 0;
+                                      return make_pool_group(v, sp.first, sp.second, kGeneralChunk, &nwg, &elems);
+                                    });
+}
+
+// Why the shard takes no pooled step (behind the call's name), or null.
+const char* pooled_step_refusal(const pskv_shard* s) {
+  if (s->dtype != PSKV_F32 && s->dtype != PSKV_F64)
+    return ": float shards only (an int32 shard takes no optimizer step)";
+  if (s->opt.kind == PSKV_OPT_NONE) return ": the shard has no optimizer (pskv_shard_set_optimizer)";
+  return nullptr;
 }
 
 // The arguments hold (pskv_apply_pooled checked them, a host call's offsets included).
-int apply_pooled_impl(pskv_shard* s, const PoolPush& call, int flags) {
-  if (s->dtype != PSKV_F32 && s->dtype != PSKV_F64)
-    return fail(PSKV_EINVAL, "pskv_apply_pooled: float shards only (an int32 shard takes no optimizer step)");
-  if (s->opt.kind == PSKV_OPT_NONE)
-    return fail(PSKV_EINVAL, "pskv_apply_pooled: the shard has no optimizer (pskv_shard_set_optimizer)");
+int apply_pooled_impl(pskv_shard* s, const pskv_pool_batch& call, int flags) {
+  if (const char* why = pooled_step_refusal(s)) return fail(PSKV_EINVAL, std::string("pskv_apply_pooled") + why);
   if (call.n == 0 || call.nbags == 0) return PSKV_OK;  // no key, or no bag to take a row from: no step
   // rows_front's checks on the keys (apply_impl's: the request server ends, a
   // host call refuses an out-of-range key); the bag rows stand in for the
   // values, which the checks only want non-null
   RowCall c;
-  const std::vector<pskv_batch> in{pskv_batch{call.keys, const_cast<void*>(call.bag_grads), call.n}};
-  int rc = rows_front_checks(s, in, flags,
+  int rc = rows_front_checks(s, pool_mark_batches({call}), flags,
                              RowFront{"pskv_apply_pooled", nullptr, /*stop_server=*/true, "key",
                                       "an optimizer step takes no out-of-range keys", /*with_values=*/false},
                              &c);
   if (rc) return rc;
   if (flags & PSKV_DEVICE) return apply_pooled_device(s, call);
-  // host buffers: pooled_impl's staging layout (keys, weights, offsets, 16-byte
-  // aligned) with the bag rows as an input behind them
-  const size_t rb = row_bytes(s);
-  const size_t wo = round16(call.n * 4);
-  const size_t oo = wo + (call.weights ? round16(call.n * (size_t)s->vb) : 0);
-  const size_t ro = oo + round16((call.nbags + 1) * sizeof(uint64_t));
-  const size_t total = ro + round16(call.nbags * rb);
   HstageHold hold(s);  // the call returns before its DMA: the hold stays armed
-  if ((rc = ensure_hstage(s, total)) || (rc = ensure_dstage(s, total))) return rc;
-  char* h = static_cast<char*>(s->hstage);
-  char* d = static_cast<char*>(s->dstage);
-  std::vector<Piece> pieces;
-  add_pieces(pieces, call.keys, h, call.n * 4, -1);
-  if (call.weights) add_pieces(pieces, call.weights, h + wo, call.n * (size_t)s->vb, -1);
-  add_pieces(pieces, call.offsets, h + oo, (call.nbags + 1) * sizeof(uint64_t), -1);
-  add_pieces(pieces, call.bag_grads, h + ro, call.nbags * rb, -1);
-  if ((rc = pipelined_h2d(s, pieces, h, d, hold))) return rc;
-  return apply_pooled_device(s, PoolPush{reinterpret_cast<const uint32_t*>(d), call.n,
-                                         call.weights ? d + wo : nullptr, reinterpret_cast<const uint64_t*>(d + oo),
-                                         call.nbags, d + ro});
-}
-
-// --------------------------------------------------- grouped pooled pushes
-// pskv_apply_pooled_grouped (pskv.h "Grouped pooled pushes"):
-// the pooled pushes of several workers as ONE step.  The live batches are cut
-// into G launch groups (pool_split_groups); as apply_device, all marks first,
-// then all loser passes, then all apply passes, one epoch per group and one
-// step number for the call:
-//   G x K4a (stamp mode, over the groups' keys)   the winner position of each key
-//   G x k_row_pooled_group_grad_losers            every other position's row -> gsum
-//   G x k_row_pooled_group_apply                  each winner steps its key's row
-// `v`: live batches where the kernels read them.
-int apply_pooled_grouped_device(pskv_shard* s, const std::vector<pskv_pool_batch>& v) {
-  if (int rc = ensure_owner(s)) return rc;
-  const std::vector<pskv_batch> marks = pool_mark_batches(v);
-  // 16-byte units for the whole call or for none of it
-  const bool vec = rows_unit16(s, {s->dense, s->opt_gsum, s->opt_slot[0], s->opt_slot[1]}, marks);
-  const std::vector<Span> spans = pool_split_groups(v);
-  struct PoolLaunch {
-    LaunchGroup mark;
-    PoolGroupArgs ga;
-    uint32_t nwg;
-    bool weighted;
-    uint32_t epoch;
-  };
-  std::vector<PoolLaunch> groups(spans.size());
-  uint64_t elems = 0;
-  // the call's epochs must not straddle a wrap-around (apply_device)
-  if (0xFFFFFFFFu - s->epoch < spans.size()) s->epoch = 0xFFFFFFFFu;
-  for (size_t i = 0; i < spans.size(); ++i) {
-    PoolLaunch& g = groups[i];
-    g.mark = make_group(marks, spans[i].first, spans[i].second, kGeneralChunk);
-    uint64_t el = 0;
-    g.ga = make_pool_group(v, spans[i].first, spans[i].second, kGeneralChunk, &g.nwg, &el);
-    g.weighted = false;
-    for (size_t j = spans[i].first; j < spans[i].second; ++j) g.weighted |= v[j].weights != nullptr;
-    g.epoch = next_epoch(s);
-    elems += el;
-  }
-  const OptArgs<double> hy = opt_args(s->opt, ++s->opt_step);
-  const RowShape rs1 = row_shape(s->width, s->vb, false);
-  const RowShape rsv = row_shape(s->width, s->vb, vec);
-  LaunchTimer t(s, kTimeApply, elems);
-  t.count = groups.size();
-  for (const PoolLaunch& g : groups)
-    PSKV_HIP(launch_general_mark(s->dtype, PSKV_ASSIGN, g.mark.ga, g.mark.nwg, s->dview(), s->flag + 1, s->owner,
-                                 nullptr, g.epoch, s->stream));
-  for (const PoolLaunch& g : groups)
-    PSKV_HIP(launch_row_pooled_group_grad_losers(s->dtype, g.ga, g.nwg, g.weighted, s->dview(), s->opt_gsum, s->owner,
-                                                 s->ovf, g.epoch, rs1, s->stream));
-  for (const PoolLaunch& g : groups)
-    PSKV_HIP(launch_row_pooled_group_apply(s->dtype, s->opt.kind, g.ga, g.nwg, g.weighted, s->dview(), s->opt_gsum,
-                                           s->opt_slot, s->owner, g.epoch, rsv, hy, s->stream));
-  t.done();
-  s->n_general += 3 * groups.size();
-  return PSKV_OK;
+  std::vector<pskv_pool_batch> dv;
+  if ((rc = stage_pool_batches(s, {call}, /*with_rows=*/true, hold, &dv))) return rc;
+  return apply_pooled_device(s, dv[0]);
 }
 
 // The arguments hold (pskv_apply_pooled_grouped checked every batch, a host
 // call's offsets included).
 int apply_pooled_grouped_impl(pskv_shard* s, const pskv_pool_batch* batches, uint64_t nb, int flags) {
-  if (s->dtype != PSKV_F32 && s->dtype != PSKV_F64)
-    return fail(PSKV_EINVAL, "pskv_apply_pooled_grouped: float shards only (an int32 shard takes no optimizer step)");
-  if (s->opt.kind == PSKV_OPT_NONE)
-    return fail(PSKV_EINVAL, "pskv_apply_pooled_grouped: the shard has no optimizer (pskv_shard_set_optimizer)");
+  if (const char* why = pooled_step_refusal(s))
+    return fail(PSKV_EINVAL, std::string("pskv_apply_pooled_grouped") + why);
   std::vector<uint64_t> index;
   const std::vector<pskv_pool_batch> live = pool_live_batches(batches, nb, &index);
   if (live.empty()) return PSKV_OK;  // no batch with a key and a bag: no step
@@ -2099,34 +2053,15 @@ int apply_pooled_grouped_impl(pskv_shard* s, const pskv_pool_batch* batches, uin
   if (rc || (rc = srv_stop(s))) return rc;
   if (flags & PSKV_DEVICE) return apply_pooled_grouped_device(s, live);
   for (size_t i = 0; i < live.size(); ++i) {
-    const std::vector<pskv_batch> one{pskv_batch{live[i].keys, const_cast<void*>(live[i].bag_grads), live[i].n}};
-    if (const uint32_t* k = first_key_outside(one, s->key_begin, s->range))
+    if (const uint32_t* k = first_key_outside(pool_mark_batches({live[i]}), s->key_begin, s->range))
       return fail(PSKV_EINVAL, "pskv_apply_pooled_grouped: batch " + std::to_string(index[i]) + ": key " +
                                    std::to_string(*k) +
                                    " is outside [key_begin, key_end); an optimizer step takes no out-of-range keys "
                                    "(nothing was applied)");
   }
-  // host buffers: one staging block, every live batch's keys, weights, offsets
-  // and bag rows (pool_stage_layout), apply_pooled_impl's path
-  const size_t rb = row_bytes(s);
-  const PoolStageLayout lay = pool_stage_layout(live, (size_t)s->vb, rb);
   HstageHold hold(s);  // the call returns before its DMA: the hold stays armed
-  if ((rc = ensure_hstage(s, lay.total)) || (rc = ensure_dstage(s, lay.total))) return rc;
-  char* h = static_cast<char*>(s->hstage);
-  char* d = static_cast<char*>(s->dstage);
-  std::vector<Piece> pieces;
-  std::vector<pskv_pool_batch> dv(live.size());
-  for (size_t i = 0; i < live.size(); ++i) {
-    const pskv_pool_batch& b = live[i];
-    const PoolStageSlot& at = lay.at[i];
-    add_pieces(pieces, b.keys, h + at.keys, b.n * 4, -1);
-    if (b.weights) add_pieces(pieces, b.weights, h + at.weights, b.n * (size_t)s->vb, -1);
-    add_pieces(pieces, b.offsets, h + at.offsets, (b.nbags + 1) * sizeof(uint64_t), -1);
-    add_pieces(pieces, b.bag_grads, h + at.rows, b.nbags * rb, -1);
-    dv[i] = pskv_pool_batch{reinterpret_cast<const uint32_t*>(d + at.keys), b.weights ? d + at.weights : nullptr,
-                            reinterpret_cast<const uint64_t*>(d + at.offsets), d + at.rows, b.n, b.nbags};
-  }
-  if ((rc = pipelined_h2d(s, pieces, h, d, hold))) return rc;
+  std::vector<pskv_pool_batch> dv;
+  if ((rc = stage_pool_batches(s, live, /*with_rows=*/true, hold, &dv))) return rc;
   return apply_pooled_grouped_device(s, dv);
 }
 
@@ -3008,24 +2943,33 @@ int pskv_apply_grouped(pskv_shard* s, const pskv_batch* batches, uint64_t nb, in
   return apply_impl(s, std::vector<pskv_batch>(batches, batches + nb), flags);
 }
 
-// Flags, pointers, the size limit and a host call's offsets are checked before
-// the handle is looked at, as pskv_get_pooled checks its arguments.
+// What is wrong with a pooled push's batch, or "": pointers, the size limit
+// (`one`: what a batch of at most 2^31 keys is to the call) and a host call's
+// offsets, in that order.  who: the call, and in a grouped one the batch.
+static std::string pool_batch_error(const std::string& who, const pskv_pool_batch& b, int flags, const char* one) {
+  if (b.n && !b.keys) return who + "null keys with n > 0";
+  if (b.nbags && !b.offsets) return who + "null offsets with nbags > 0";
+  if (b.nbags && !b.bag_grads) return who + "null bag_grads with nbags > 0";
+  if (b.n > kMaxPiece) return who + "n = " + std::to_string(b.n) + " exceeds 2^31 keys (" + one + ")";
+  if (!(flags & PSKV_DEVICE)) {
+    uint64_t bad = 0;
+    if (const char* why = pool_offsets_error(b.offsets, b.nbags, b.n, &bad))
+      return who + "offsets: bag " + std::to_string(bad) + ": " + why + " (n = " + std::to_string(b.n) +
+             ", nbags = " + std::to_string(b.nbags) + ")";
+  }
+  return "";
+}
+
+// Flags and the batch (pool_batch_error) are checked before the handle is
+// looked at, as pskv_get_pooled checks its arguments.
 int pskv_apply_pooled(pskv_shard* s, const uint32_t* keys, uint64_t n, const void* weights, const uint64_t* offsets,
                       uint64_t nbags, const void* bag_grads, int flags) {
   if (bad_flags(flags)) return fail(PSKV_EINVAL, "pskv_apply_pooled: unknown flags");
-  if (n && !keys) return fail(PSKV_EINVAL, "pskv_apply_pooled: null keys with n > 0");
-  if (nbags && !offsets) return fail(PSKV_EINVAL, "pskv_apply_pooled: null offsets with nbags > 0");
-  if (nbags && !bag_grads) return fail(PSKV_EINVAL, "pskv_apply_pooled: null bag_grads with nbags > 0");
-  if (n > kMaxPiece)
-    return fail(PSKV_EINVAL, "pskv_apply_pooled: n = " + std::to_string(n) + " exceeds 2^31 keys (a pooled push is one launch group)");
-  if (!(flags & PSKV_DEVICE)) {
-    uint64_t bad = 0;
-    if (const char* why = pool_offsets_error(offsets, nbags, n, &bad))
-      return fail(PSKV_EINVAL, "pskv_apply_pooled: offsets: bag " + std::to_string(bad) + ": " + why + " (n = " +
-                                   std::to_string(n) + ", nbags = " + std::to_string(nbags) + ")");
-  }
+  const pskv_pool_batch b{keys, weights, offsets, bag_grads, n, nbags};
+  const std::string err = pool_batch_error("pskv_apply_pooled: ", b, flags, "a pooled push is one launch group");
+  if (!err.empty()) return fail(PSKV_EINVAL, err);
   if (!s) return fail(PSKV_EINVAL, "pskv_apply_pooled: null shard");
-  return apply_pooled_impl(s, PoolPush{keys, n, weights, offsets, nbags, bag_grads}, flags);
+  return apply_pooled_impl(s, b, flags);
 }
 
 // Every batch gets pskv_apply_pooled's checks, before the handle is looked at;
@@ -3034,19 +2978,9 @@ int pskv_apply_pooled_grouped(pskv_shard* s, const pskv_pool_batch* batches, uin
   if (bad_flags(flags)) return fail(PSKV_EINVAL, "pskv_apply_pooled_grouped: unknown flags");
   if (nb && !batches) return fail(PSKV_EINVAL, "pskv_apply_pooled_grouped: null batches with nb > 0");
   for (uint64_t i = 0; i < nb; ++i) {
-    const pskv_pool_batch& b = batches[i];
-    const std::string who = "pskv_apply_pooled_grouped: batch " + std::to_string(i) + ": ";
-    if (b.n && !b.keys) return fail(PSKV_EINVAL, who + "null keys with n > 0");
-    if (b.nbags && !b.offsets) return fail(PSKV_EINVAL, who + "null offsets with nbags > 0");
-    if (b.nbags && !b.bag_grads) return fail(PSKV_EINVAL, who + "null bag_grads with nbags > 0");
-    if (b.n > kMaxPiece)
-      return fail(PSKV_EINVAL, who + "n = " + std::to_string(b.n) + " exceeds 2^31 keys (a batch lies in one launch group)");
-    if (!(flags & PSKV_DEVICE)) {
-      uint64_t bad = 0;
-      if (const char* why = pool_offsets_error(b.offsets, b.nbags, b.n, &bad))
-        return fail(PSKV_EINVAL, who + "offsets: bag " + std::to_string(bad) + ": " + why + " (n = " +
-                                     std::to_string(b.n) + ", nbags = " + std::to_string(b.nbags) + ")");
-    }
+    const std::string err = pool_batch_error("pskv_apply_pooled_grouped: batch " + std::to_string(i) + ": ", batches[i],
+                                             flags, "a batch lies in one launch group");
+    if (!err.empty()) return fail(PSKV_EINVAL, err);
   }
   if (!s) return fail(PSKV_EINVAL, "pskv_apply_pooled_grouped: null shard");
   return apply_pooled_grouped_impl(s, batches, nb, flags);

@@ -136,6 +136,32 @@ static void test_staging() {
   EXPECT(pool_stage_layout(std::vector<pskv_pool_batch>(), 4, 16).total == 0);
 }
 
+// One batch: the layout a single pooled push and a pooled pull stage by, which
+// was once computed by hand in their host paths.  Those formulas are the
+// expectation: keys at 0, then weights (where present), offsets of nbags + 1,
+// rows of nbags * rb, each range rounded up to 16 bytes.
+static void test_staging_one_batch() {
+  for (uint64_t n : {1u, 3u, 4u, 5u})
+    for (uint64_t nbags : {1u, 2u})
+      for (bool weighted : {false, true})
+        for (size_t vb : {4u, 8u})
+          for (size_t rb : {4u, 12u, 16u, 24u}) {
+            const float w = 0;
+            const pskv_pool_batch call{nullptr, weighted ? &w : nullptr, nullptr, nullptr, n, nbags};
+            const size_t wo = round16(call.n * 4);
+            const size_t oo = wo + (call.weights ? round16(call.n * vb) : 0);
+            const size_t ro = oo + round16((call.nbags + 1) * sizeof(uint64_t));
+            const size_t total = ro + round16(call.nbags * rb);
+            const PoolStageLayout lay = pool_stage_layout(std::vector<pskv_pool_batch>(1, call), vb, rb);
+            EXPECT(lay.at.size() == 1);
+            EXPECT(lay.at[0].keys == 0);
+            EXPECT(!weighted || lay.at[0].weights == wo);
+            EXPECT(lay.at[0].offsets == oo);
+            EXPECT(lay.at[0].rows == ro);
+            EXPECT(lay.total == total);
+          }
+}
+
 // ------------------------------------- the kernels' lookup, on the host
 // K4a's index of element i of batch j of a plain group over the same batches.
 static uint64_t mark_index(const std::vector<pskv_batch>& marks, size_t b, size_t j, uint64_t i) {
@@ -212,6 +238,7 @@ int main() {
     test_split(n);
   test_split_by_elements();
   test_staging();
+  test_staging_one_batch();
   for (size_t n : {(size_t)1, (size_t)3, (size_t)5, (size_t)kMaxPoolBatches + 1})
     for (uint64_t stride : {1ull, 64ull, 256ull}) test_lookup(n, stride);
   std::printf("%d passed, %d failed\n", passed, failed);

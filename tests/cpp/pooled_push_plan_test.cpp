@@ -28,7 +28,7 @@ static const uint64_t kChunk = 2048;  // kGeneralChunk (pskv_internal.h, a HIP h
 static const int kRows = 4;           // kRowsInFlight (pskv_rows.hip)
 static const uint64_t C = kPoolChunk;
 
-// The lookup as k_row_pooled_grad_losers / k_row_pooled_apply run it: bag of
+// The lookup as k_row_step_losers / k_row_step_apply run it for a pooled push: bag of
 // every position of [0, n), `stride` apart inside a step (a lane group's rows
 // in flight are G positions apart), every other row of a step unwanted.
 static std::vector<uint64_t> lookup(const std::vector<uint64_t>& off, uint64_t n, uint64_t stride, bool skip_odd) {
