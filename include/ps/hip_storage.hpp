@@ -40,11 +40,18 @@
 // expanded in the shard inside one optimizer step; SubApplyPooledGrouped
 // (pskv_apply_pooled_grouped) makes ONE step of several workers' pooled pushes,
 // the BSP flush, as AddGrouped does of their plain pushes.
+// Sparse storage (HipStorage<Val>::Sparse, pskv_shard_create_sparse): the
+// storage owns EVERY key and holds at most `capacity` distinct ones, `width`
+// values each, in memory that follows capacity -- the storage of a server under
+// consistent hashing, or of a table of hashed feature ids (pskv.h "Sparse
+// shards").  Every method above works unchanged on it; a key
+// that finds no room is dropped and FinishIter aborts ("sparse shard full").
 #pragma once
 
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <memory>
 #include <vector>
 
 #include "pskv.h"
@@ -104,6 +111,32 @@ class HipStorage : public AbstractStorage {
       : width_(width), stepping_(optimizer != nullptr && optimizer->kind != PSKV_OPT_NONE) {
     Create(device, key_begin, key_end, mode, overflow_slots);
     if (optimizer) pskv_check(pskv_shard_set_optimizer_cfg(shard_, optimizer), "pskv_shard_set_optimizer_cfg");
+  }
+  // A sparse storage of at most `capacity` distinct keys; optimizer: null, or
+  // any of the three configuration structs, as the constructors take them.
+  static std::unique_ptr<HipStorage> Sparse(int device, uint64_t capacity, int mode = PSKV_ASSIGN, uint32_t width = 1) {
+    return std::unique_ptr<HipStorage>(new HipStorage(SparseTag(), device, capacity, mode, width));
+  }
+  static std::unique_ptr<HipStorage> Sparse(int device, uint64_t capacity, int mode, uint32_t width,
+                                            const pskv_optimizer* optimizer) {
+    auto st = Sparse(device, capacity, mode, width);
+    if (optimizer) pskv_check(pskv_shard_set_optimizer(st->shard_, optimizer), "pskv_shard_set_optimizer");
+    st->stepping_ = optimizer != nullptr && optimizer->kind != PSKV_OPT_NONE;
+    return st;
+  }
+  static std::unique_ptr<HipStorage> Sparse(int device, uint64_t capacity, int mode, uint32_t width,
+                                            const pskv_optimizer_ex* optimizer) {
+    auto st = Sparse(device, capacity, mode, width);
+    if (optimizer) pskv_check(pskv_shard_set_optimizer_ex(st->shard_, optimizer), "pskv_shard_set_optimizer_ex");
+    st->stepping_ = optimizer != nullptr && optimizer->kind != PSKV_OPT_NONE;
+    return st;
+  }
+  static std::unique_ptr<HipStorage> Sparse(int device, uint64_t capacity, int mode, uint32_t width,
+                                            const pskv_optimizer_cfg* optimizer) {
+    auto st = Sparse(device, capacity, mode, width);
+    if (optimizer) pskv_check(pskv_shard_set_optimizer_cfg(st->shard_, optimizer), "pskv_shard_set_optimizer_cfg");
+    st->stepping_ = optimizer != nullptr && optimizer->kind != PSKV_OPT_NONE;
+    return st;
   }
   ~HipStorage() override { pskv_shard_destroy(shard_); }
   HipStorage(const HipStorage&) = delete;
@@ -243,6 +276,11 @@ class HipStorage : public AbstractStorage {
   uint32_t width() const { return width_; }
 
  private:
+  struct SparseTag {};
+  HipStorage(SparseTag, int device, uint64_t capacity, int mode, uint32_t width) : width_(width) {
+    pskv_check(pskv_shard_create_sparse(device, capacity, PskvDtype<Val>::value, mode, width_, &shard_),
+               "pskv_shard_create_sparse");
+  }
   // Both constructors' shard.
   void Create(int device, uint32_t key_begin, uint64_t key_end, int mode, uint64_t overflow_slots) {
     pskv_check(pskv_shard_create_rows(device, key_begin, key_end, PskvDtype<Val>::value, mode, width_,

@@ -111,15 +111,31 @@ std::vector<AbstractStorage*> CreateTable(std::vector<std::unique_ptr<ServerThre
 
 // Consistent hashing (the reference default, driver/engine.hpp:143-150): any
 // server may receive any key below key_end, so every storage covers
-// [0, key_end).
+// [0, key_end) -- N times the table's memory over N servers.  sparse_capacity
+// > 0 (StorageType::Hip only) gives every server a sparse storage of that many
+// distinct keys instead (HipStorage::Sparse): it takes whatever keys the hash
+// sends it, and its memory follows the keys it holds.
 template <typename Val>
 std::vector<AbstractStorage*> CreateTable(std::vector<std::unique_ptr<ServerThread>>& threads,
                                           const ConsistentHashShardMap& map, uint64_t key_end,
                                           uint32_t model_id, ModelType model_type,
                                           StorageType storage_type, int staleness, ReplyQueue* replies,
                                           int mode = PSKV_ASSIGN,
-                                          const CpuStorageMaker& cpu = nullptr, uint32_t width = 1) {
+                                          const CpuStorageMaker& cpu = nullptr, uint32_t width = 1,
+                                          uint64_t sparse_capacity = 0) {
   PS_CHECK(threads.size() == map.GetNumServers());
+  if (sparse_capacity > 0) {
+    PS_CHECK(storage_type == StorageType::Hip);
+    const int ndev = pskv_device_count();
+    PS_CHECK(ndev > 0);
+    std::vector<AbstractStorage*> out;
+    for (size_t i = 0; i < threads.size(); ++i) {
+      std::unique_ptr<AbstractStorage> st = HipStorage<Val>::Sparse((int)(i % (size_t)ndev), sparse_capacity, mode, width);
+      out.push_back(st.get());
+      threads[i]->RegisterModel(model_id, MakeModel(model_type, model_id, std::move(st), staleness, replies));
+    }
+    return out;
+  }
   std::vector<KeyRange> ranges(threads.size(), KeyRange(0, key_end));
   return CreateTable<Val>(threads, ranges, model_id, model_type, storage_type, staleness, replies, mode,
                           cpu, width);

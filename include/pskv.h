@@ -55,7 +55,8 @@
  * PSKV_SORTED_HINT and the tuning options are accepted and change nothing;
  * PSKV_HOST_FRAME buffers are treated as plain host memory.
  * ONE LIMIT: a row shard stores no key outside [key_begin, key_end) (the
- * overflow table holds one value per slot).  It refuses such keys loudly: a
+ * overflow table holds one value per slot; a sparse shard, below, takes every
+ * key).  It refuses such keys loudly: a
  * host Add that contains one returns PSKV_EINVAL naming the first and applies
  * nothing; a device Add applies its in-range rows, drops the others, and the
  * next pskv_sync returns PSKV_ESTATE ("row shard ... out-of-range"; pskv_clear
@@ -283,6 +284,62 @@
  *     slot, one operation per launch group, elements = the sum of n;
  *   - not provided: a grouped pooled PULL (it would save launches only).
  *
+ * Sparse shards (pskv_shard_create_sparse): a shard whose memory
+ * follows the number of keys it holds, not the span of the key space -- the
+ * storage of a server under consistent hashing (a scattered 1/N of the keys),
+ * of a table of hashed feature ids or embedding ids.  It owns EVERY uint32 key,
+ * 0 and 0xFFFFFFFF included, and holds at most `capacity` distinct keys, W
+ * values each, any W (1 included; width 1 runs on the row kernels).  In HBM:
+ * the row array, one array of the same shape per optimizer state slot and the
+ * stamp array, over capacity slots as a row shard has them over its range, and
+ * a hash index from keys to slots (pskv_sparse_info.index_bytes).
+ *   - unchanged meaning, stated by relabelling: take any call sequence and any
+ *     injective map `rank` from its keys to [0, capacity).  The sparse shard fed
+ *     keys K returns what a row shard [0, capacity) of the same dtype, mode,
+ *     width and optimizer returns when fed rank(K) -- every call of this
+ *     header, and the step counter.  Where the row shard's result is specified
+ *     bit for bit (assign; optimizer steps and pooled pushes with distinct keys;
+ *     pooled pulls; state round trips) so is the sparse shard's; where a
+ *     summation order is left open the same bound holds.  One difference, for a
+ *     key that was never written: see "reading calls" below;
+ *   - writing calls insert: pskv_add, pskv_add_grouped, the Add half of
+ *     pskv_add_get_grouped, pskv_apply, pskv_apply_grouped, pskv_apply_pooled,
+ *     pskv_apply_pooled_grouped and pskv_put_state give a key that has no slot
+ *     one.  A new key starts with a row of zeros and the optimizer's start state
+ *     (init_accum for Adagrad's h and FTRL's n, else 0);
+ *   - reading calls never insert: pskv_get, pskv_get_grouped, pskv_get_pooled,
+ *     pskv_get_state, pskv_get_state_slot.  A key that is not stored reads as a
+ *     row of zeros (the reference's map semantics) from the parameters AND from
+ *     every state array (where a row shard's untouched key shows init_accum);
+ *     in a pooled pull, from device buffers too, it is legal and sets no error;
+ *   - no key is refused: the host-side refusal of out-of-range keys does not
+ *     apply.  int32, float and double for Add and Get; optimizer steps keep
+ *     their float-only rule.  PSKV_SORTED_HINT and PSKV_HOST_FRAME are accepted
+ *     and change nothing; the tuning options are accepted and echoed,
+ *     pskv_info.resident_bytes is 0;
+ *   - a full shard: when a writing call meets a new key and capacity keys are
+ *     stored, that key is dropped whole -- every occurrence in the call, every
+ *     element of its row -- and the rest of the call is applied; the next
+ *     pskv_sync returns PSKV_ESTATE ("sparse shard full"; pskv_clear resets
+ *     it), host and device calls alike.  Keys already stored are always served
+ *     and count never exceeds capacity; when a call holds more new keys than
+ *     there is room for, which of them are dropped is unspecified; the step
+ *     counter advances as for a device call that drops keys.  A key dropped
+ *     once stays dropped until pskv_clear;
+ *   - pskv_info keeps its layout: key_begin 0, key_end 2^32, dense_bytes the
+ *     row array (capacity + 1 rows: the last one is the zero row absent keys
+ *     read), an empty overflow table.  pskv_dense_ptr returns the row array,
+ *     whose row order is unspecified (pskv_sparse_keys lists the keys, pskv_get
+ *     reads them);
+ *   - pskv_clear empties the index (count 0), zeroes the rows and resets the
+ *     state and the step counter; setting or changing an optimizer keeps the
+ *     index and follows the rules above for the state;
+ *   - timing: the index launches of a call (insert, translate) are one
+ *     operation of pskv_index_time's slot (PSKV_TIME_INDEX), elements = keys;
+ *   - not provided: growth, deletion or eviction, 64-bit keys, a sparse scalar
+ *     fast path (the resident request server and inline messages serve scalar
+ *     range shards only).
+ *
  * Threading: one shard handle is used by one host thread at a time (the
  * reference calls a storage only from its ServerThread, server_thread.cpp:20-50);
  * distinct handles may be used concurrently.  Every call selects the shard's
@@ -407,6 +464,27 @@ int pskv_shard_create_rows(int device, uint32_t key_begin, uint64_t key_end, int
 /* Values per key of this shard (1 for every shard made by the older
  * constructors); 0 for a null shard. */
 uint32_t pskv_shard_width(pskv_shard* s);
+/* A sparse shard (semantics: the header comment, "Sparse shards"): it owns
+ * every uint32 key and holds at most `capacity` distinct keys, `width` values
+ * each; its memory follows capacity, not the key space.  Validated before the
+ * device is looked at, PSKV_EINVAL naming the field: capacity 0 or above
+ * 2^31 - 2, width 0 or above PSKV_MAX_WIDTH, a bad dtype or mode, row arrays
+ * of more than 2^46 bytes. */
+int pskv_shard_create_sparse(int device, uint64_t capacity, int dtype, int mode, uint32_t width,
+                             pskv_shard** out);
+typedef struct pskv_sparse_info {
+  uint32_t size;          /* sizeof(pskv_sparse_info); any other value is PSKV_EINVAL naming "size" */
+  uint64_t capacity;      /* distinct keys the shard can hold */
+  uint64_t count;         /* distinct keys held, after everything queued so far */
+  uint64_t table_slots;   /* entries of the hash index (a power of two, >= 2 * capacity) */
+  uint64_t index_bytes;   /* HBM held by the index beyond the row arrays */
+} pskv_sparse_info;
+/* Waits for the shard's stream.  PSKV_EINVAL for a shard that is not sparse. */
+int pskv_sparse_info_get(pskv_shard* s, pskv_sparse_info* out);
+/* The stored keys, in unspecified order: at most cap of them into out (host
+ * memory, or device memory with PSKV_DEVICE), *n = the number stored (it may
+ * exceed cap: nothing past cap is written).  Waits for the shard's stream. */
+int pskv_sparse_keys(pskv_shard* s, uint32_t* out, uint64_t cap, uint64_t* n, int flags);
 int pskv_shard_destroy(pskv_shard* s);
 
 /* Push: apply n (key, value) pairs.  Asynchronous on the shard's stream for
@@ -652,6 +730,10 @@ int pskv_apply_time(pskv_shard* s, uint64_t* launches, double* total_ms, uint64_
  * own; elements counts keys. */
 #define PSKV_TIME_POOLED (1u << 15)
 int pskv_pooled_time(pskv_shard* s, uint64_t* launches, double* total_ms, uint64_t* elements);
+/* A sparse shard's index launches of one call (insert and translate) likewise:
+ * one operation per call; elements counts keys. */
+#define PSKV_TIME_INDEX (1u << 16)
+int pskv_index_time(pskv_shard* s, uint64_t* launches, double* total_ms, uint64_t* elements);
 
 /* Mirror of RangePartitionManager::Slice (base/range_partition_manager.hpp:19-46):
  * walk `keys` once; a key goes to the current range if it lies in it or the

@@ -44,6 +44,7 @@ PSKV_K_COUNT = 14
 PSKV_MAX_WIDTH = 4096
 PSKV_TIME_APPLY = 1 << 14
 PSKV_TIME_POOLED = 1 << 15
+PSKV_TIME_INDEX = 1 << 16
 PSKV_OPT_NONE, PSKV_OPT_SGD, PSKV_OPT_ADAGRAD = 0, 1, 2
 PSKV_OPT_MOMENTUM, PSKV_OPT_ADAM = 3, 4  # only through pskv_shard_set_optimizer_ex
 PSKV_OPT_FTRL = 5  # only through pskv_shard_set_optimizer_cfg
@@ -80,6 +81,7 @@ EXPORTED = [
     "pskv_get_pooled", "pskv_pooled_time",
     "pskv_apply_pooled", "pskv_apply_pooled_grouped",
     "pskv_shard_set_optimizer_cfg", "pskv_shard_get_optimizer_cfg",
+    "pskv_shard_create_sparse", "pskv_sparse_info_get", "pskv_sparse_keys", "pskv_index_time",
 ]
 
 
@@ -101,6 +103,11 @@ class PskvInfo(ctypes.Structure):
         ("n_get_calls", ctypes.c_uint64), ("n_sorted_launches", ctypes.c_uint64),
         ("n_general_launches", ctypes.c_uint64), ("resident_bytes", ctypes.c_uint64),
     ]
+
+
+class PskvSparseInfo(ctypes.Structure):
+    _fields_ = [("size", ctypes.c_uint32), ("capacity", ctypes.c_uint64), ("count", ctypes.c_uint64),
+                ("table_slots", ctypes.c_uint64), ("index_bytes", ctypes.c_uint64)]
 
 
 class PskvOptimizer(ctypes.Structure):
@@ -185,6 +192,10 @@ def _load():
         "pskv_apply_pooled_grouped": ([vp, ctypes.POINTER(PskvPoolBatch), u64, i32], i32),
         "pskv_shard_set_optimizer_cfg": ([vp, ctypes.POINTER(PskvOptimizerCfg)], i32),
         "pskv_shard_get_optimizer_cfg": ([vp, ctypes.POINTER(PskvOptimizerCfg), ctypes.POINTER(u64)], i32),
+        "pskv_shard_create_sparse": ([i32, u64, i32, i32, u32, ctypes.POINTER(vp)], i32),
+        "pskv_sparse_info_get": ([vp, ctypes.POINTER(PskvSparseInfo)], i32),
+        "pskv_sparse_keys": ([vp, vp, u64, ctypes.POINTER(u64), i32], i32),
+        "pskv_index_time": ([vp, ctypes.POINTER(u64), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(u64)], i32),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)

@@ -16,7 +16,7 @@ INCLUDE = os.path.join(ROOT, "include")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 
-LIB_SOURCES = ["pskv_kernels.hip", "pskv_rows.hip", "pskv_shard.cpp", "pskv_frames.cpp"]
+LIB_SOURCES = ["pskv_kernels.hip", "pskv_rows.hip", "pskv_index.hip", "pskv_shard.cpp", "pskv_frames.cpp"]
 LIB_OUT = os.path.join(PKG, "libpskv.so")
 CPP_TESTS = {  # program -> (source in tests/cpp, links the oracle checker)
     "hip_storage_test": ("hip_storage_test.cpp", False),
@@ -29,6 +29,7 @@ CPP_TESTS = {  # program -> (source in tests/cpp, links the oracle checker)
     "hip_storage_pooled_test": ("hip_storage_pooled_test.cpp", False),
     "hip_storage_pooled_push_test": ("hip_storage_pooled_push_test.cpp", False),
     "hip_storage_pooled_push_group_test": ("hip_storage_pooled_push_group_test.cpp", False),
+    "hip_storage_sparse_test": ("hip_storage_sparse_test.cpp", False),
     "pooled_push_group_plan_test": ("pooled_push_group_plan_test.cpp", False),  # host-only: the planner's arithmetic
 }
 ORACLE_DIR = os.path.join(ROOT, "oracle")

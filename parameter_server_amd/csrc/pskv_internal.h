@@ -15,6 +15,9 @@
 //   gsum, state slots   with an optimizer: gradient scratch and up to
 //                       two state arrays (Adagrad's h; momentum's v; Adam's m and v),
 //                       each shaped as dense
+//   A sparse shard: dense, gsum and the state slots hold capacity + 1
+//   rows (slots, then the zero row absent keys read), owner[capacity], and the index:
+//   table[table_slots] u64 entries and slot_keys[capacity] (SparseIndex below).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -49,6 +52,7 @@ constexpr uint32_t kEmpty32 = 0xFFFFFFFFu;
 // Error bits in ovf.stat[1].
 constexpr uint32_t kErrOverflowFull = 1u;
 constexpr uint32_t kErrRowOutOfRange = 2u;  // a row shard's device Add met a key outside its range (dropped)
+constexpr uint32_t kErrSparseFull = 4u;     // a sparse shard's writing call met a new key with no slot left (dropped)
 
 struct DevBatch {
   const uint32_t* keys;
@@ -360,5 +364,35 @@ hipError_t launch_row_pooled_chunks(int dtype, const PoolArgs& a, const DenseVie
                                     const RowShape& rs, hipStream_t st);
 hipError_t launch_row_pooled(int dtype, bool nt, const PoolArgs& a, const DenseView& d, const Ovf& o,
                              const RowShape& rs, hipStream_t st);
+
+// Sparse shards (pskv_index.hip): the hash index that maps a
+// uint32 key to a slot of the row arrays.  table: mask + 1 entries (a power of
+// two, >= 2 * capacity), linear probing from fmix32(key).  An entry is 0 when
+// empty; otherwise key + 1 sits in its low 33 bits and slot + 1 in its high
+// 31 bits, 0 there meaning "claimed, no slot yet or none granted".  Entries
+// are never emptied while work is queued (pskv_clear zeroes the table).
+// slot_keys[slot]: the key of a slot.  stat: the shard's OvfCtl::stat -- a
+// sparse shard keeps nothing in its overflow table, so [0] is the number of
+// slots handed out and [1] the sticky error word (kErrSparseFull).
+constexpr int kIndexKeyBits = 33;
+struct SparseIndex {
+  unsigned long long* table;
+  uint32_t* slot_keys;
+  uint32_t* stat;
+  uint64_t mask;
+  uint32_t capacity;  // slots, <= 2^31 - 2
+};
+// `ga` chunked by kGeneralChunk keys, nwg virtual workgroups (nwg == 0:
+// nothing is launched).  Insert reads b[j].keys only: every key of the group
+// that has no entry claims one, and the claimer takes a slot while one is left
+// (else the entry stays slotless and kErrSparseFull is set).  No lane waits for
+// another, and every probe loop ends after mask + 1 entries.
+hipError_t launch_index_insert(const GroupArgs& ga, uint32_t nwg, const SparseIndex& x, hipStream_t st);
+// Behind the insert in stream order: b[j].vals (uint32, may be b[j].keys itself)
+// receives a slot id per position: the key's slot; for a key without one,
+// `capacity` (the zero row) when reading, and when writing 0xFFFFFFFF, which the
+// row kernels drop, with kErrSparseFull set.
+hipError_t launch_index_translate(bool writing, const GroupArgs& ga, uint32_t nwg, const SparseIndex& x,
+                                  hipStream_t st);
 
 }  // namespace pskv

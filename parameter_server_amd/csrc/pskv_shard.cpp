@@ -106,9 +106,12 @@ struct TimedLaunch {
 // a whole pooled pull (pskv_pooled_time; PSKV_TIME_POOLED).
 constexpr int kTimeApply = PSKV_K_COUNT;
 constexpr int kTimePooled = PSKV_K_COUNT + 1;
-constexpr int kTimeSlots = PSKV_K_COUNT + 2;
+constexpr int kTimeIndex = PSKV_K_COUNT + 2;  // a sparse shard's index launches of one call (pskv_index_time)
+constexpr int kTimeSlots = PSKV_K_COUNT + 3;
 static_assert(PSKV_TIME_APPLY == (1u << kTimeApply), "the apply slot follows the kernel ids");
+static_assert(PSKV_TIME_APPLY == (1u << 14), "the apply slot's bit is part of the interface");
 static_assert(PSKV_TIME_POOLED == (1u << kTimePooled), "the pooled slot follows the apply slot");
+static_assert(PSKV_TIME_INDEX == (1u << kTimeIndex), "the index slot follows the pooled slot");
 
 // ---------------------------------------------------------------- host pool
 // A small persistent pool for the host side of the path: copying zmq-buffer
@@ -385,6 +388,27 @@ struct pskv_shard {
   void* opt_slot[2] = {nullptr, nullptr};  // the first opt_slots(opt.kind) are allocated
   uint64_t opt_step = 0;
 
+  // A sparse shard (pskv_shard_create_sparse): the row shard
+  // [0, range) over SLOT numbers, range = the capacity, behind a hash index
+  // from keys to slots (pskv_index.hip).  Every row-shaped array holds one row
+  // more than `range`: row `range` stays zero and is what an absent key reads.
+  // The slot counter and the full bit live in ovf.c->stat (SparseIndex).
+  bool sparse = false;
+  unsigned long long* sp_table = nullptr;
+  uint32_t* sp_slot_keys = nullptr;
+  uint64_t sp_table_slots = 0;
+  void* sp_ids = nullptr;  // a device call's slot ids (grown on demand, as the K5 scratch)
+  size_t sp_ids_bytes = 0;
+  uint64_t rows_held() const { return range + (sparse ? 1u : 0u); }  // rows of the dense array and of each state array
+  SparseIndex sindex() const {
+    return SparseIndex{sp_table, sp_slot_keys, ovf.c->stat, sp_table_slots - 1, (uint32_t)range};
+  }
+  // The array `arr` (the dense array or a state array) as a reading call sees
+  // it: a sparse shard's translate pass sends absent keys to the zero row.
+  DenseView read_view(void* arr) const {
+    return DenseView{arr, key_begin, rows_held(), arr == dense ? resident_bytes() / (uint64_t)vb : 0};
+  }
+
   // PSKV_RESIDENT_BYTES: the resident window, bytes of the dense
   // array from its start that K2g's dense mode and K1 / K1r keep in the
   // Infinity Cache (plain stores and loads inside, non-temporal ones outside).
@@ -397,7 +421,7 @@ struct pskv_shard {
   // anyway (at most the budget), else the budget.  Row shards have none (the
   // row kernels do not look at it).
   uint64_t resident_bytes() const {
-    if (width != 1) return 0;
+    if (width != 1 || sparse) return 0;
     const uint64_t bytes = range * (uint64_t)vb;
     if (tune_resident_bytes < 0) return bytes <= kResidentAutoBytes ? 0 : kResidentAutoBytes;
     return std::min<uint64_t>((uint64_t)tune_resident_bytes, bytes);
@@ -481,7 +505,8 @@ const char* const kKernelNames[kTimeSlots] = {
     "k_inline_get (K8)",          "k_replay (K4r)",                "k_row_gather (row Get)",
     "k_general_mark + k_row_commit (row assign Add)",              "k_row_accumulate (row accumulate Add)",
     "k_general_mark + k_row_grad_losers + k_row_apply (optimizer step)",
-    "k_row_pooled_chunks + k_row_pooled (pooled pull)"};
+    "k_row_pooled_chunks + k_row_pooled (pooled pull)",
+    "k_index_insert + k_index_translate (sparse index)"};
 
 std::string wait_report(const pskv_shard* s, const char* what, const void* handle, double ms) {
   char buf[384];
@@ -1626,6 +1651,57 @@ bool rows_unit16(const pskv_shard* s, std::initializer_list<const void*> arrays,
   return ok;
 }
 
+// A sparse shard's step between a call's front and its row kernels (DESIGN.md
+// §8k): the keys of `v` (vals are not looked at) become slot ids, and each
+// batch's keys pointer is redirected to them.  writing: the call inserts
+// (k_index_insert over every launch group first, then the translate passes: a
+// key repeated across groups finds the one slot it got).  in_place: the keys lie
+// in the device staging (a host call) and are overwritten; else the ids go to
+// the shard's scratch and the caller's keys are only read.  The launches are
+// one timed operation (kTimeIndex), elements = the keys.
+int sparse_ids(pskv_shard* s, std::vector<pskv_batch>& v, bool writing, bool in_place) {
+  std::vector<pskv_batch> io(v.size());  // vals: where the batch's ids go
+  uint64_t elems = 0;
+  size_t bytes = 0;
+  for (const auto& b : v) {
+    elems += b.n;
+    bytes += round16(b.n * sizeof(uint32_t));
+  }
+  if (elems == 0) return PSKV_OK;
+  if (!in_place)
+    if (int rc = ensure_scratch(s, &s->sp_ids, &s->sp_ids_bytes, bytes)) return rc;
+  size_t at = 0;
+  for (size_t i = 0; i < v.size(); ++i) {
+    void* ids = in_place ? static_cast<void*>(const_cast<uint32_t*>(v[i].keys)) : static_cast<char*>(s->sp_ids) + at;
+    io[i] = pskv_batch{v[i].keys, ids, v[i].n};
+    at += round16(v[i].n * sizeof(uint32_t));
+  }
+  const SparseIndex x = s->sindex();
+  const std::vector<Span> spans = split_groups(io);
+  LaunchTimer t(s, kTimeIndex, elems);
+  if (writing)
+    for (const Span& sp : spans) {
+      const LaunchGroup g = make_group(io, sp.first, sp.second, kGeneralChunk);
+      PSKV_HIP(launch_index_insert(g.ga, g.nwg, x, s->stream));
+    }
+  for (const Span& sp : spans) {
+    const LaunchGroup g = make_group(io, sp.first, sp.second, kGeneralChunk);
+    PSKV_HIP(launch_index_translate(writing, g.ga, g.nwg, x, s->stream));
+  }
+  t.done();
+  for (size_t i = 0; i < v.size(); ++i) v[i].keys = static_cast<const uint32_t*>(io[i].vals);
+  return PSKV_OK;
+}
+
+// The same for pooled batches.
+int sparse_pool_ids(pskv_shard* s, std::vector<pskv_pool_batch>& v, bool writing, bool in_place) {
+  std::vector<pskv_batch> k(v.size());
+  for (size_t i = 0; i < v.size(); ++i) k[i] = pskv_batch{v[i].keys, nullptr, v[i].n};
+  if (int rc = sparse_ids(s, k, writing, in_place)) return rc;
+  for (size_t i = 0; i < v.size(); ++i) v[i].keys = k[i].keys;
+  return PSKV_OK;
+}
+
 // The front of every row-shaped call: a row Add or Get, an optimizer step, a
 // read or write of optimizer state.
 struct RowFront {
@@ -1659,7 +1735,7 @@ int rows_front_checks(pskv_shard* s, const std::vector<pskv_batch>& in, int flag
   int rc = use_device(s);
   if (rc) return rc;
   if (f.stop_server && (rc = srv_stop(s))) return rc;
-  if (flags & PSKV_DEVICE) return PSKV_OK;
+  if ((flags & PSKV_DEVICE) || s->sparse) return PSKV_OK;  // (a sparse shard owns every key)
   if (f.refusal)
     if (const uint32_t* k = first_key_outside(c->v, s->key_begin, s->range))
       return fail(PSKV_EINVAL, std::string(f.what) + ": " + f.refusal + " " + std::to_string(*k) +
@@ -1673,10 +1749,16 @@ int rows_front_checks(pskv_shard* s, const std::vector<pskv_batch>& in, int flag
 int rows_front(pskv_shard* s, const std::vector<pskv_batch>& in, int flags, const RowFront& f, HstageHold& hold,
                RowCall* c) {
   if (int rc = rows_front_checks(s, in, flags, f, c)) return rc;
-  if (c->v.empty() || (flags & PSKV_DEVICE)) return PSKV_OK;
-  c->host = true;
-  c->lay = stage_layout(c->v, row_bytes(s), StageOrder::kKeysFirst);
-  return stage_keys_first(s, c->v, c->lay, row_bytes(s), f.with_values, hold, &c->dv);
+  if (c->v.empty()) return PSKV_OK;
+  if (!(flags & PSKV_DEVICE)) {
+    c->host = true;
+    c->lay = stage_layout(c->v, row_bytes(s), StageOrder::kKeysFirst);
+    if (int rc = stage_keys_first(s, c->v, c->lay, row_bytes(s), f.with_values, hold, &c->dv)) return rc;
+  }
+  // a sparse shard: what the kernels read carries slot ids from here on (the
+  // calls that bring values are the writing ones, and insert)
+  if (s->sparse) return sparse_ids(s, c->host ? c->dv : c->v, /*writing=*/f.with_values, /*in_place=*/c->host);
+  return PSKV_OK;
 }
 
 // `d`: the array written: the dense array in the shard's mode, or
@@ -1757,7 +1839,7 @@ int rows_get_from(pskv_shard* s, const std::vector<pskv_batch>& in, int flags, c
 }
 
 int rows_get(pskv_shard* s, const std::vector<pskv_batch>& in, int flags) {
-  return rows_get_from(s, in, flags, s->dview(), "pskv_get", &s->n_get);
+  return rows_get_from(s, in, flags, s->read_view(s->dense), "pskv_get", &s->n_get);
 }
 
 // Host pooled batches -> device staging through pinned staging, batch after
@@ -1815,8 +1897,8 @@ int pooled_device(pskv_shard* s, const PoolCall& c) {
   const bool unit16 = row_bytes(s) % 16 == 0 && aligned16(s->dense) && aligned16(c.out) && aligned16(a.part);
   const RowShape rs = row_shape(s->width, s->vb, unit16);
   LaunchTimer t(s, kTimePooled, c.n);
-  PSKV_HIP(launch_row_pooled_chunks(s->dtype, a, s->dview(), s->ovf, rs, s->stream));
-  PSKV_HIP(launch_row_pooled(s->dtype, s->tune_nt, a, s->dview(), s->ovf, rs, s->stream));
+  PSKV_HIP(launch_row_pooled_chunks(s->dtype, a, s->read_view(s->dense), s->ovf, rs, s->stream));
+  PSKV_HIP(launch_row_pooled(s->dtype, s->tune_nt, a, s->read_view(s->dense), s->ovf, rs, s->stream));
   t.done();
   return PSKV_OK;
 }
@@ -1838,13 +1920,19 @@ int pooled_impl(pskv_shard* s, const PoolCall& call, int flags) {
   if (c.v.empty()) {  // no key, but bags: rows of zeros
     if ((rc = use_device(s)) || (rc = srv_stop(s))) return rc;
   }
-  if (flags & PSKV_DEVICE) return pooled_device(s, call);
+  const pskv_pool_batch one{call.keys, call.weights, call.offsets, call.out, call.n, call.nbags};
+  if (flags & PSKV_DEVICE) {
+    if (!s->sparse) return pooled_device(s, call);
+    std::vector<pskv_pool_batch> ids{one};
+    if ((rc = sparse_pool_ids(s, ids, /*writing=*/false, /*in_place=*/false))) return rc;
+    return pooled_device(s, PoolCall{ids[0].keys, call.n, call.weights, call.offsets, call.nbags, call.out});
+  }
   // host buffers: through the staging, the pooled rows behind keys, weights and offsets
   const size_t rb = row_bytes(s);
   HstageHold hold(s);
   std::vector<pskv_pool_batch> dv;
-  const pskv_pool_batch one{call.keys, call.weights, call.offsets, call.out, call.n, call.nbags};
   if ((rc = stage_pool_batches(s, {one}, /*with_rows=*/false, hold, &dv))) return rc;
+  if (s->sparse && (rc = sparse_pool_ids(s, dv, /*writing=*/false, /*in_place=*/true))) return rc;
   char* d = static_cast<char*>(const_cast<void*>(dv[0].bag_grads));  // the rows' room in dstage
   char* h = static_cast<char*>(s->hstage) + (d - static_cast<char*>(s->dstage));
   if ((rc = pooled_device(s, PoolCall{dv[0].keys, call.n, dv[0].weights, dv[0].offsets, call.nbags, d}))) return rc;
@@ -1870,7 +1958,13 @@ int pooled_impl(pskv_shard* s, const PoolCall& call, int flags) {
 // Momentum and Adam add a second state array, the step
 // counter opt_step (one per call: Adam's bias corrections are computed from it
 // here, in double) and pskv_put_state, the row assign Add aimed at a state array.
-size_t opt_array_bytes(const pskv_shard* s) { return s->range * row_bytes(s); }
+size_t opt_array_bytes(const pskv_shard* s) { return s->rows_held() * row_bytes(s); }
+
+// A sparse shard's limits (pskv.h): slot + 1 fits an index entry's 31 bits and
+// 0xFFFFFFFF stays free as the id the row kernels drop; the index has at least
+// two entries per slot.
+constexpr uint64_t kSparseMaxCapacity = (1ull << 31) - 2;
+uint64_t sparse_table_slots(uint64_t capacity) { return std::max<uint64_t>(16, next_pow2(2 * capacity)); }
 
 // State slots per kind (pskv_optimizer_kind).
 int opt_slots(int kind) {
@@ -1910,9 +2004,12 @@ int opt_reset_state(pskv_shard* s) {
   s->opt_step = 0;
   if (s->opt_gsum) PSKV_HIP(hipMemsetAsync(s->opt_gsum, 0, opt_array_bytes(s), s->stream));
   for (int i = 0; i < opt_slots(s->opt.kind); ++i) {
-    if (s->opt.kind == PSKV_OPT_ADAGRAD || (s->opt.kind == PSKV_OPT_FTRL && i == 1))
+    if (s->opt.kind == PSKV_OPT_ADAGRAD || (s->opt.kind == PSKV_OPT_FTRL && i == 1)) {
       PSKV_HIP(launch_fill(s->dtype, s->opt_slot[i], s->range * (uint64_t)s->width, s->opt.init_accum, s->stream));
-    else
+      if (s->sparse)  // the zero row an absent key reads
+        PSKV_HIP(hipMemsetAsync(static_cast<char*>(s->opt_slot[i]) + s->range * row_bytes(s), 0, row_bytes(s),
+                                s->stream));
+    } else
       PSKV_HIP(hipMemsetAsync(s->opt_slot[i], 0, opt_array_bytes(s), s->stream));
   }
   return PSKV_OK;
@@ -2034,10 +2131,15 @@ int apply_pooled_impl(pskv_shard* s, const pskv_pool_batch& call, int flags) {
                                       "an optimizer step takes no out-of-range keys", /*with_values=*/false},
                              &c);
   if (rc) return rc;
-  if (flags & PSKV_DEVICE) return apply_pooled_device(s, call);
+  if (flags & PSKV_DEVICE) {
+    std::vector<pskv_pool_batch> one{call};
+    if (s->sparse && (rc = sparse_pool_ids(s, one, /*writing=*/true, /*in_place=*/false))) return rc;
+    return apply_pooled_device(s, one[0]);
+  }
   HstageHold hold(s);  // the call returns before its DMA: the hold stays armed
   std::vector<pskv_pool_batch> dv;
   if ((rc = stage_pool_batches(s, {call}, /*with_rows=*/true, hold, &dv))) return rc;
+  if (s->sparse && (rc = sparse_pool_ids(s, dv, /*writing=*/true, /*in_place=*/true))) return rc;
   return apply_pooled_device(s, dv[0]);
 }
 
@@ -2051,8 +2153,12 @@ int apply_pooled_grouped_impl(pskv_shard* s, const pskv_pool_batch* batches, uin
   if (live.empty()) return PSKV_OK;  // no batch with a key and a bag: no step
   int rc = use_device(s);
   if (rc || (rc = srv_stop(s))) return rc;
-  if (flags & PSKV_DEVICE) return apply_pooled_grouped_device(s, live);
-  for (size_t i = 0; i < live.size(); ++i) {
+  if (flags & PSKV_DEVICE) {
+    std::vector<pskv_pool_batch> ids = live;
+    if (s->sparse && (rc = sparse_pool_ids(s, ids, /*writing=*/true, /*in_place=*/false))) return rc;
+    return apply_pooled_grouped_device(s, ids);
+  }
+  for (size_t i = 0; i < live.size() && !s->sparse; ++i) {
     if (const uint32_t* k = first_key_outside(pool_mark_batches({live[i]}), s->key_begin, s->range))
       return fail(PSKV_EINVAL, "pskv_apply_pooled_grouped: batch " + std::to_string(index[i]) + ": key " +
                                    std::to_string(*k) +
@@ -2062,6 +2168,7 @@ int apply_pooled_grouped_impl(pskv_shard* s, const pskv_pool_batch* batches, uin
   HstageHold hold(s);  // the call returns before its DMA: the hold stays armed
   std::vector<pskv_pool_batch> dv;
   if ((rc = stage_pool_batches(s, live, /*with_rows=*/true, hold, &dv))) return rc;
+  if (s->sparse && (rc = sparse_pool_ids(s, dv, /*writing=*/true, /*in_place=*/true))) return rc;
   return apply_pooled_grouped_device(s, dv);
 }
 
@@ -2113,7 +2220,7 @@ const char* opt_config_error(const pskv_optimizer_cfg& c, OptAbi abi) {
 }
 
 int add_impl(pskv_shard* s, const std::vector<pskv_batch>& in, int flags) {
-  if (s->width > 1) return rows_add(s, in, flags);
+  if (s->width > 1 || s->sparse) return rows_add(s, in, flags);
   std::vector<pskv_batch> v;
   for (auto& b : in) {
     if (b.n == 0) continue;
@@ -2335,7 +2442,7 @@ int staged_get(pskv_shard* s, const std::vector<pskv_batch>& v) {
 // in-place zero copy, staged zero copy, DMA (page-locked, or pageable and
 // large), staged windowed.
 int get_impl(pskv_shard* s, const std::vector<pskv_batch>& in, int flags) {
-  if (s->width > 1) return rows_get(s, in, flags);
+  if (s->width > 1 || s->sparse) return rows_get(s, in, flags);
   std::vector<pskv_batch> v;
   for (auto& b : in) {
     if (b.n == 0) continue;
@@ -2384,7 +2491,7 @@ int get_impl(pskv_shard* s, const std::vector<pskv_batch>& in, int flags) {
 // kernel was removed; the call stays, as the two paths.
 int add_get_impl(pskv_shard* s, const std::vector<pskv_batch>& adds, const std::vector<pskv_batch>& gets,
                  int flags) {
-  if (s->width > 1) {
+  if (s->width > 1 || s->sparse) {
     const int rc = rows_add(s, adds, flags);
     return rc ? rc : rows_get(s, gets, flags);
   }
@@ -2631,8 +2738,10 @@ int pskv_device_count(void) {
   return n;
 }
 
-int pskv_shard_create_rows(int device, uint32_t key_begin, uint64_t key_end, int dtype, int mode,
-                           uint32_t width, uint64_t overflow_slots, pskv_shard** out) {
+// Every constructor ends here.  sparse: a sparse shard of key_end slots
+// (pskv_shard_create_sparse validated its arguments; key_begin is 0).
+static int create_impl(int device, uint32_t key_begin, uint64_t key_end, int dtype, int mode, uint32_t width,
+                       uint64_t overflow_slots, bool sparse, pskv_shard** out) {
   if (!out) return fail(PSKV_EINVAL, "pskv_shard_create: out is null");
   *out = nullptr;
   const int vb = value_bytes(dtype);
@@ -2656,6 +2765,7 @@ int pskv_shard_create_rows(int device, uint32_t key_begin, uint64_t key_end, int
   s->width = width;
   s->key_begin = key_begin;
   s->range = key_end - key_begin;
+  s->sparse = sparse;
   // tuning / path options: creation defaults from the environment (PSKV_<NAME>),
   // changeable later through pskv_set_option (kOptions below)
   if (int rc = apply_env_options(s)) {
@@ -2677,9 +2787,9 @@ int pskv_shard_create_rows(int device, uint32_t key_begin, uint64_t key_end, int
       hipEventCreateWithFlags(&s->h2d_done, hipEventDisableTiming | hipEventDisableSystemFence) !=
           hipSuccess)
     return bail(fail(PSKV_EHIP, "hipEventCreate failed"));
-  if (hipMalloc(&s->dense, s->range * (size_t)width * (size_t)vb) != hipSuccess)
+  if (hipMalloc(&s->dense, s->rows_held() * (size_t)width * (size_t)vb) != hipSuccess)
     return bail(fail(PSKV_ENOMEM, "dense parameter allocation failed"));
-  if (hipMemsetAsync(s->dense, 0, s->range * (size_t)width * (size_t)vb, s->stream) != hipSuccess)
+  if (hipMemsetAsync(s->dense, 0, s->rows_held() * (size_t)width * (size_t)vb, s->stream) != hipSuccess)
     return bail(fail(PSKV_EHIP, "hipMemsetAsync failed"));
   // flag[0]: the sorted path's verification tag
   // the verification tag (16 bytes), then K1r's replay table (add_get's folded replay)
@@ -2708,10 +2818,87 @@ int pskv_shard_create_rows(int device, uint32_t key_begin, uint64_t key_end, int
   init.mbox = s->mbox;
   if (hipMemcpyAsync(ctl, &init, sizeof(init), hipMemcpyHostToDevice, s->stream) != hipSuccess)
     return bail(fail(PSKV_EHIP, "hipMemcpyAsync failed"));
+  if (sparse) {  // the index: an empty table and the key of every slot
+    s->sp_table_slots = sparse_table_slots(s->range);
+    if (hipMalloc(&s->sp_table, s->sp_table_slots * sizeof(unsigned long long)) != hipSuccess ||
+        hipMalloc(&s->sp_slot_keys, s->range * sizeof(uint32_t)) != hipSuccess)
+      return bail(fail(PSKV_ENOMEM, "sparse index allocation failed"));
+    if (hipMemsetAsync(s->sp_table, 0, s->sp_table_slots * sizeof(unsigned long long), s->stream) != hipSuccess)
+      return bail(fail(PSKV_EHIP, "hipMemsetAsync failed"));
+  }
   if (int wrc = wait_stream(s, s->stream, "shard stream (creation)")) return bail(wrc);
   s->counted = g_queues.add_shard(device, 1);
   GrowService::get().add(s);
   *out = s;
+  return PSKV_OK;
+}
+
+int pskv_shard_create_rows(int device, uint32_t key_begin, uint64_t key_end, int dtype, int mode,
+                           uint32_t width, uint64_t overflow_slots, pskv_shard** out) {
+  return create_impl(device, key_begin, key_end, dtype, mode, width, overflow_slots, /*sparse=*/false, out);
+}
+
+int pskv_shard_create_sparse(int device, uint64_t capacity, int dtype, int mode, uint32_t width, pskv_shard** out) {
+  if (!out) return fail(PSKV_EINVAL, "pskv_shard_create_sparse: out is null");
+  *out = nullptr;
+  const int vb = value_bytes(dtype);
+  if (!vb) return fail(PSKV_EINVAL, "pskv_shard_create_sparse: bad dtype");
+  if (mode != PSKV_ASSIGN && mode != PSKV_ACCUMULATE) return fail(PSKV_EINVAL, "pskv_shard_create_sparse: bad mode");
+  if (capacity == 0 || capacity > kSparseMaxCapacity)
+    return fail(PSKV_EINVAL, "pskv_shard_create_sparse: capacity must be 1..2^31 - 2");
+  if (width == 0 || width > PSKV_MAX_WIDTH)
+    return fail(PSKV_EINVAL, "pskv_shard_create_sparse: width must be 1.." + std::to_string(PSKV_MAX_WIDTH));
+  if ((capacity + 1) * (uint64_t)width * (uint64_t)vb > (1ull << 46))
+    return fail(PSKV_EINVAL, "pskv_shard_create_sparse: (capacity + 1) * width * value bytes exceeds 2^46 bytes");
+  // (the overflow table is never used: its smallest size)
+  return create_impl(device, 0, capacity, dtype, mode, width, /*overflow_slots=*/64, /*sparse=*/true, out);
+}
+
+int pskv_sparse_info_get(pskv_shard* s, pskv_sparse_info* out) {
+  if (!out) return fail(PSKV_EINVAL, "pskv_sparse_info_get: null output");
+  if (out->size != sizeof(pskv_sparse_info))
+    return fail(PSKV_EINVAL, "pskv_sparse_info_get: size must be sizeof(pskv_sparse_info)");
+  if (!s) return fail(PSKV_EINVAL, "pskv_sparse_info_get: null shard");
+  if (!s->sparse) return fail(PSKV_EINVAL, "pskv_sparse_info_get: not a sparse shard (pskv_shard_create_sparse)");
+  int rc = use_device(s);
+  if (rc) return rc;
+  uint32_t cnt = 0, err = 0;
+  if ((rc = read_overflow_stat(s, &cnt, &err))) return rc;
+  out->capacity = s->range;
+  out->count = std::min<uint64_t>(cnt, s->range);
+  out->table_slots = s->sp_table_slots;
+  out->index_bytes = s->sp_table_slots * sizeof(unsigned long long) + s->range * sizeof(uint32_t);
+  return PSKV_OK;
+}
+
+int pskv_sparse_keys(pskv_shard* s, uint32_t* out, uint64_t cap, uint64_t* n, int flags) {
+  if (flags & ~PSKV_DEVICE) return fail(PSKV_EINVAL, "pskv_sparse_keys: unknown flags (PSKV_HOST or PSKV_DEVICE)");
+  if (!n) return fail(PSKV_EINVAL, "pskv_sparse_keys: null n");
+  if (cap && !out) return fail(PSKV_EINVAL, "pskv_sparse_keys: null out with cap > 0");
+  if (!s) return fail(PSKV_EINVAL, "pskv_sparse_keys: null shard");
+  if (!s->sparse) return fail(PSKV_EINVAL, "pskv_sparse_keys: not a sparse shard (pskv_shard_create_sparse)");
+  int rc = use_device(s);
+  if (rc) return rc;
+  uint32_t cnt = 0, err = 0;
+  if ((rc = read_overflow_stat(s, &cnt, &err))) return rc;  // (waits for the stream)
+  const uint64_t held = std::min<uint64_t>(cnt, s->range);
+  *n = held;
+  const uint64_t take = std::min(held, cap);
+  if (take == 0) return PSKV_OK;
+  PSKV_HIP(hipMemcpyAsync(out, s->sp_slot_keys, take * sizeof(uint32_t),
+                          (flags & PSKV_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s->stream));
+  return wait_stream(s, s->stream, "shard stream (sparse keys)");
+}
+
+int pskv_index_time(pskv_shard* s, uint64_t* launches, double* total_ms, uint64_t* elements) {
+  if (!s) return fail(PSKV_EINVAL, "pskv_index_time: null shard");
+  int rc = use_device(s);
+  if (rc) return rc;
+  rc = drain_timing(s);
+  if (rc) return rc;
+  if (launches) *launches = s->t_launches[kTimeIndex];
+  if (total_ms) *total_ms = s->t_ms[kTimeIndex];
+  if (elements) *elements = s->t_elems[kTimeIndex];
   return PSKV_OK;
 }
 
@@ -2788,6 +2975,9 @@ int pskv_shard_destroy(pskv_shard* s) {
   if (s->rb_loff) (void)hipFree(s->rb_loff);
   if (s->rb_ent) (void)hipFree(s->rb_ent);
   if (s->pool_part) (void)hipFree(s->pool_part);
+  if (s->sp_table) (void)hipFree(s->sp_table);
+  if (s->sp_slot_keys) (void)hipFree(s->sp_slot_keys);
+  if (s->sp_ids) (void)hipFree(s->sp_ids);
   if (s->hstage) (void)hipHostFree(s->hstage);
   if (s->ireply) (void)hipHostFree(s->ireply);
   if (s->stat_host) (void)hipHostFree(s->stat_host);
@@ -3003,7 +3193,7 @@ static int state_call(pskv_shard* s, const std::string& who, bool adagrad_only, 
   if (rc) return rc;
   const std::vector<pskv_batch> in{pskv_batch{keys, vals, n}};
   const DenseView d{arr, s->key_begin, s->range, 0};
-  if (!put) return rows_get_from(s, in, flags, d, who.c_str(), nullptr);
+  if (!put) return rows_get_from(s, in, flags, s->read_view(arr), who.c_str(), nullptr);
   return rows_add_to(s, in, flags, d, PSKV_ASSIGN,
                      RowFront{who.c_str(), nullptr, false, "key",
                               "optimizer state is kept for the shard's own keys only", /*with_values=*/true});
@@ -3054,6 +3244,13 @@ int pskv_sync(pskv_shard* s) {
   if (rc) return rc;
   rc = drain_timing(s);
   if (rc) return rc;
+  if (s->sparse) {  // (stat[0] is the slot counter; a dropped key is a key that found no slot)
+    if (err & (kErrSparseFull | kErrRowOutOfRange))
+      return fail(PSKV_ESTATE, "sparse shard full: a writing call met new keys with all " + std::to_string(s->range) +
+                                   " slots taken; those keys were dropped whole, the rest of the call was applied "
+                                   "(pskv_clear resets this)");
+    return PSKV_OK;
+  }
   if (err & kErrOverflowFull)
     return fail(PSKV_ESTATE,
                 "overflow table exhausted: out-of-range keys were dropped (the device-side growth "
@@ -3074,7 +3271,9 @@ int pskv_clear(pskv_shard* s) {
   uint32_t cnt = 0, err = 0;
   rc = read_overflow_stat(s, &cnt, &err);  // (adopts the current table; stops the server)
   if (rc) return rc;
-  PSKV_HIP(hipMemsetAsync(s->dense, 0, s->range * (size_t)s->width * (size_t)s->vb, s->stream));
+  PSKV_HIP(hipMemsetAsync(s->dense, 0, s->rows_held() * (size_t)s->width * (size_t)s->vb, s->stream));
+  // a sparse shard: an empty index (the slot counter and the full bit go with stat below)
+  if (s->sparse) PSKV_HIP(hipMemsetAsync(s->sp_table, 0, s->sp_table_slots * sizeof(unsigned long long), s->stream));
   PSKV_HIP(hipMemsetAsync(s->cur.keys, 0xFF, s->ocap * sizeof(unsigned long long), s->stream));
   PSKV_HIP(hipMemsetAsync(s->cur.vals, 0, s->ocap * (size_t)s->vb, s->stream));
   PSKV_HIP(hipMemsetAsync(s->ovf.c->stat, 0, 2 * sizeof(uint32_t), s->stream));
@@ -3107,10 +3306,10 @@ int pskv_shard_info(pskv_shard* s, pskv_info* info) {
   info->mode = s->mode;
   info->value_bytes = s->vb;
   info->key_begin = s->key_begin;
-  info->key_end = (uint64_t)s->key_begin + s->range;
-  info->dense_bytes = s->range * (uint64_t)s->width * (uint64_t)s->vb;
+  info->key_end = s->sparse ? (1ull << 32) : (uint64_t)s->key_begin + s->range;  // (a sparse shard owns every key)
+  info->dense_bytes = s->rows_held() * (uint64_t)s->width * (uint64_t)s->vb;
   info->overflow_capacity = s->ocap;
-  info->overflow_count = s->ocount_known;
+  info->overflow_count = s->sparse ? 0 : s->ocount_known;  // (its stat[0] counts slots, not overflow keys)
   info->n_add_calls = s->n_add;
   info->n_get_calls = s->n_get;
   info->n_sorted_launches = s->n_sorted;

@@ -47,11 +47,16 @@ class Shard:
     width > 1 makes a row shard: every key holds `width` values (an embedding
     row).  add takes values shaped (n, width) or flat n * width, get returns
     (n, width); counts stay in keys.  A row shard stores no key outside its
-    range (include/pskv.h: the one limit)."""
+    range (include/pskv.h: the one limit).
+
+    capacity > 0 (or Shard.sparse) makes a sparse shard instead: it owns every
+    uint32 key and holds at most `capacity` distinct ones, at any width, its
+    memory following capacity and not the key space (include/pskv.h, "Sparse
+    shards").  key_begin, key_end and overflow_slots are not used."""
 
     def __init__(self, key_begin: int = 0, key_end: int = 1 << 32, dtype=np.float32,
                  mode: str = "assign", device: int = 0, overflow_slots: int = 0, options=None,
-                 width: int = 1):
+                 width: int = 1, capacity: int = 0):
         self.dtype = np.dtype(dtype) if not _is_torch(dtype) else _NP_DTYPE[dtype_code(dtype)]
         self.code = dtype_code(self.dtype)
         self.mode = {"assign": _lib.PSKV_ASSIGN, "accumulate": _lib.PSKV_ACCUMULATE}[mode]
@@ -60,11 +65,28 @@ class Shard:
         if not 0 <= self.width < 1 << 32:
             raise ValueError(f"width {width} out of range")
         h = ctypes.c_void_p()
-        check(lib.pskv_shard_create_rows(self.device, self.key_begin, self.key_end, self.code,
-                                         self.mode, self.width, int(overflow_slots), ctypes.byref(h)))
+        self.capacity = int(capacity)
+        self.is_sparse = self.capacity != 0
+        if self.is_sparse:
+            if not 0 < self.capacity < 1 << 64:
+                raise ValueError(f"capacity {capacity} out of range")
+            self.key_begin, self.key_end = 0, 1 << 32
+            check(lib.pskv_shard_create_sparse(self.device, self.capacity, self.code, self.mode, self.width,
+                                               ctypes.byref(h)))
+        else:
+            check(lib.pskv_shard_create_rows(self.device, self.key_begin, self.key_end, self.code,
+                                             self.mode, self.width, int(overflow_slots), ctypes.byref(h)))
         self._h = h
         for name, value in (options or {}).items():
             self.set_option(name, value)
+
+    @classmethod
+    def sparse(cls, capacity: int, dtype=np.float32, mode: str = "assign", device: int = 0, width: int = 1,
+               options=None) -> "Shard":
+        """A sparse shard of at most `capacity` distinct keys (pskv_shard_create_sparse)."""
+        if int(capacity) == 0:
+            raise ValueError("Shard.sparse: capacity must be positive")
+        return cls(dtype=dtype, mode=mode, device=device, options=options, width=width, capacity=capacity)
 
     # ------------------------------------------------------------ lifetime
     def close(self):
@@ -430,16 +452,30 @@ class Shard:
 
     def state_dict(self) -> dict:
         """A checkpoint: the whole range's parameters, every state slot and the
-        step count, as host arrays."""
-        keys = np.arange(self.key_begin, self.key_end, dtype=np.int64).astype(np.uint32)
+        step count, as host arrays.  A sparse shard saves its stored keys
+        ("keys") and their rows."""
+        if self.is_sparse:
+            keys = self.keys()
+        else:
+            keys = np.arange(self.key_begin, self.key_end, dtype=np.int64).astype(np.uint32)
         o = self.optimizer()
-        return {"p": self.get(keys), "slots": [self.get_state(keys, slot=i) for i in range(self._OPT_SLOTS[o["kind"]])],
-                "t": self.step, "optimizer": o}
+        d = {"p": self.get(keys), "slots": [self.get_state(keys, slot=i) for i in range(self._OPT_SLOTS[o["kind"]])],
+             "t": self.step, "optimizer": o}
+        if self.is_sparse:
+            d["keys"] = keys
+        return d
 
     def load_state_dict(self, d: dict):
         """Restore state_dict()'s checkpoint into a shard of the same range,
-        width, dtype and optimizer kind."""
-        keys = np.arange(self.key_begin, self.key_end, dtype=np.int64).astype(np.uint32)
+        width, dtype and optimizer kind (a sparse shard's: into a sparse shard
+        with room for the saved keys)."""
+        if self.is_sparse != ("keys" in d):
+            raise ValueError("load_state_dict: a sparse shard's checkpoint goes into a sparse shard, a dense one's "
+                             "into a dense one")
+        if self.is_sparse:
+            keys = np.ascontiguousarray(d["keys"], dtype=np.uint32)
+        else:
+            keys = np.arange(self.key_begin, self.key_end, dtype=np.int64).astype(np.uint32)
         kind = self.optimizer()["kind"]
         if len(d["slots"]) != self._OPT_SLOTS[kind]:
             raise ValueError(f"load_state_dict: {len(d['slots'])} state slots for optimizer {kind!r}")
@@ -447,6 +483,27 @@ class Shard:
         for i, v in enumerate(d["slots"]):
             self.put_state(keys, v, slot=i)
         self.step = d["t"]
+
+    # ------------------------------------------------------------ sparse shards
+    def sparse_info(self) -> dict:
+        """pskv_sparse_info_get: capacity, count (distinct keys held), table_slots
+        and index_bytes of a sparse shard.  Waits for the shard's stream."""
+        i = _lib.PskvSparseInfo(ctypes.sizeof(_lib.PskvSparseInfo))
+        check(lib.pskv_sparse_info_get(self._h, ctypes.byref(i)))
+        return {f: getattr(i, f) for f, _ in _lib.PskvSparseInfo._fields_ if f != "size"}
+
+    def keys(self) -> np.ndarray:
+        """The keys a sparse shard holds, in unspecified order (pskv_sparse_keys)."""
+        n = ctypes.c_uint64()
+        out = np.empty(max(self.sparse_info()["count"], 1), dtype=np.uint32)
+        check(lib.pskv_sparse_keys(self._h, out.ctypes.data, out.size, ctypes.byref(n), _lib.PSKV_HOST))
+        return out[:min(n.value, out.size)]
+
+    def index_time(self):
+        """A sparse shard's index launches, one operation per call (pskv_index_time)."""
+        n, ms, el = ctypes.c_uint64(), ctypes.c_double(), ctypes.c_uint64()
+        check(lib.pskv_index_time(self._h, ctypes.byref(n), ctypes.byref(ms), ctypes.byref(el)))
+        return {"launches": n.value, "total_ms": ms.value, "elements": el.value}
 
     def apply_time(self):
         """Optimizer steps timed as one operation each (pskv_apply_time)."""
@@ -545,6 +602,8 @@ class Shard:
         """A torch tensor aliasing the dense HBM array (tests only; no copy)."""
         import torch
 
+        if self.is_sparse:
+            raise ValueError("dense_view: a sparse shard's row order is unspecified (use keys() and get())")
         n = self.key_end - self.key_begin
         ptr = self.dense_ptr()
         if self.width > 1:

@@ -113,15 +113,18 @@ class HipStorage(AbstractStorage):
     optimizer: a dict for Shard.set_optimizer (kind "sgd", "adagrad", "momentum",
     "adam" or "ftrl", lr, ...).  The storage then
     applies optimizer steps: an Add message carries GRADIENTS and is one step
-    (pskv_apply); AddGrouped, a BSP flush, is one step over all its messages."""
+    (pskv_apply); AddGrouped, a BSP flush, is one step over all its messages.
+    capacity > 0: a sparse storage (Shard.sparse) that owns every key and holds
+    at most `capacity` distinct ones; key_begin, key_end and overflow_slots are
+    not used."""
 
     def __init__(self, val_dtype=np.float32, key_begin: int = 0, key_end: int = 1 << 32,
                  device: int = 0, mode: str = "assign", overflow_slots: int = 0, width: int = 1,
-                 optimizer=None):
+                 optimizer=None, capacity: int = 0):
         self.val_dtype = np.dtype(val_dtype)
         self.width = int(width)
         self.shard = Shard(key_begin, key_end, self.val_dtype, mode=mode, device=device,
-                           overflow_slots=overflow_slots, width=self.width)
+                           overflow_slots=overflow_slots, width=self.width, capacity=capacity)
         self.optimizer = dict(optimizer) if optimizer else None
         if self.optimizer:
             try:
