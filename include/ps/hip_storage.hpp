@@ -46,6 +46,9 @@
 // consistent hashing, or of a table of hashed feature ids (pskv.h "Sparse
 // shards").  Every method above works unchanged on it; a key
 // that finds no room is dropped and FinishIter aborts ("sparse shard full").
+// Reserve grows it, SetGrowth lets the pushes grow it themselves up to a limit
+// (as the reference's std::map takes whatever keys arrive) and Erase forgets
+// keys, as std::map::erase does.
 #pragma once
 
 #include <cstdint>
@@ -265,6 +268,19 @@ class HipStorage : public AbstractStorage {
     }
     pskv_check(pskv_apply_pooled_grouped(shard_, batches.data(), batches.size(), PSKV_HOST | PSKV_HOST_FRAME),
                "pskv_apply_pooled_grouped");
+  }
+
+  // A sparse storage only (pskv.h "Sparse shards"; not part of AbstractStorage).
+  // Reserve: room for `capacity` distinct keys, every stored row kept.
+  // SetGrowth: pushes grow the storage themselves, up to max_capacity keys (0:
+  // fixed).  Erase: the keys are forgotten (absent keys are legal); a
+  // maintenance call whose cost follows the keys stored.
+  void Reserve(uint64_t capacity) { pskv_check(pskv_sparse_reserve(shard_, capacity), "pskv_sparse_reserve"); }
+  void SetGrowth(uint64_t max_capacity) {
+    pskv_check(pskv_sparse_set_growth(shard_, max_capacity), "pskv_sparse_set_growth");
+  }
+  void Erase(const third_party::SArray<Key>& typed_keys) {
+    pskv_check(pskv_sparse_erase(shard_, typed_keys.data(), typed_keys.size(), PSKV_HOST), "pskv_sparse_erase");
   }
 
   // The reference's FinishIter is a no-op (map_storage.hpp:47); here it is the

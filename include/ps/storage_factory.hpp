@@ -114,7 +114,8 @@ std::vector<AbstractStorage*> CreateTable(std::vector<std::unique_ptr<ServerThre
 // [0, key_end) -- N times the table's memory over N servers.  sparse_capacity
 // > 0 (StorageType::Hip only) gives every server a sparse storage of that many
 // distinct keys instead (HipStorage::Sparse): it takes whatever keys the hash
-// sends it, and its memory follows the keys it holds.
+// sends it, and its memory follows the keys it holds.  sparse_max_capacity > 0
+// lets each grow itself up to that many keys (HipStorage::SetGrowth); 0: fixed.
 template <typename Val>
 std::vector<AbstractStorage*> CreateTable(std::vector<std::unique_ptr<ServerThread>>& threads,
                                           const ConsistentHashShardMap& map, uint64_t key_end,
@@ -122,7 +123,7 @@ std::vector<AbstractStorage*> CreateTable(std::vector<std::unique_ptr<ServerThre
                                           StorageType storage_type, int staleness, ReplyQueue* replies,
                                           int mode = PSKV_ASSIGN,
                                           const CpuStorageMaker& cpu = nullptr, uint32_t width = 1,
-                                          uint64_t sparse_capacity = 0) {
+                                          uint64_t sparse_capacity = 0, uint64_t sparse_max_capacity = 0) {
   PS_CHECK(threads.size() == map.GetNumServers());
   if (sparse_capacity > 0) {
     PS_CHECK(storage_type == StorageType::Hip);
@@ -130,7 +131,8 @@ std::vector<AbstractStorage*> CreateTable(std::vector<std::unique_ptr<ServerThre
     PS_CHECK(ndev > 0);
     std::vector<AbstractStorage*> out;
     for (size_t i = 0; i < threads.size(); ++i) {
-      std::unique_ptr<AbstractStorage> st = HipStorage<Val>::Sparse((int)(i % (size_t)ndev), sparse_capacity, mode, width);
+      auto st = HipStorage<Val>::Sparse((int)(i % (size_t)ndev), sparse_capacity, mode, width);
+      if (sparse_max_capacity > 0) st->SetGrowth(sparse_max_capacity);
       out.push_back(st.get());
       threads[i]->RegisterModel(model_id, MakeModel(model_type, model_id, std::move(st), staleness, replies));
     }

@@ -325,7 +325,8 @@
  *     and count never exceeds capacity; when a call holds more new keys than
  *     there is room for, which of them are dropped is unspecified; the step
  *     counter advances as for a device call that drops keys.  A key dropped
- *     once stays dropped until pskv_clear;
+ *     once stays dropped until pskv_clear, pskv_sparse_reserve, a growth or
+ *     pskv_sparse_erase (below);
  *   - pskv_info keeps its layout: key_begin 0, key_end 2^32, dense_bytes the
  *     row array (capacity + 1 rows: the last one is the zero row absent keys
  *     read), an empty overflow table.  pskv_dense_ptr returns the row array,
@@ -336,9 +337,71 @@
  *     index and follows the rules above for the state;
  *   - timing: the index launches of a call (insert, translate) are one
  *     operation of pskv_index_time's slot (PSKV_TIME_INDEX), elements = keys;
- *   - not provided: growth, deletion or eviction, 64-bit keys, a sparse scalar
- *     fast path (the resident request server and inline messages serve scalar
- *     range shards only).
+ *   - growth: pskv_sparse_reserve(capacity) makes room for
+ *     `capacity` distinct keys.  Checked before the handle: capacity 0 or above
+ *     2^31 - 2 is PSKV_EINVAL naming "capacity".  Then: a shard that is not
+ *     sparse, a capacity below the current one (no shrinking) or row arrays of
+ *     more than 2^46 bytes are PSKV_EINVAL; the current capacity is PSKV_OK and
+ *     does nothing.  Otherwise the call runs in stream order behind everything
+ *     queued and returns when it is done, as pskv_clear does.  Every stored key
+ *     keeps its row and every state slot bit for bit; count, the step counter,
+ *     the optimizer configuration and the options are unchanged; capacity is
+ *     the new value and table_slots = max(16, next_pow2(2 * capacity)).  Every
+ *     new array is allocated before anything is given up: PSKV_ENOMEM leaves the
+ *     shard exactly as it was.  A successful growing call clears the "sparse
+ *     shard full" condition: keys dropped earlier are forgotten and a later
+ *     writing call may insert them (the data they were pushed with is lost).
+ *     pskv_dense_ptr and pskv_shard_info.dense_bytes CHANGE with every growth
+ *     and every erase: a pointer taken before is dangling afterwards;
+ *   - automatic growth: pskv_sparse_set_growth(max_capacity) lets the writing
+ *     calls listed above grow the shard themselves.  max_capacity is 0 (fixed,
+ *     the default) or lies in [current capacity, 2^31 - 2] with row arrays of at
+ *     most 2^46 bytes at that size; anything else is PSKV_EINVAL, the range
+ *     check coming before the handle.  With a limit, a writing call first
+ *     looks at count, the keys stored after everything queued, and at n, its
+ *     key positions (all batches of a grouped call), and grows iff
+ *     count + n > capacity, to min(max_capacity, max(2 * capacity, count + n)),
+ *     before its first key is inserted.  The capacities a shard goes through so
+ *     depend on the call sequence alone, never on timing, and a key is dropped
+ *     only when the distinct stored keys would exceed max_capacity, exactly as
+ *     at a fixed shard of that capacity.  The library keeps a host-side upper
+ *     bound of count (the count at its last read-back plus the key positions of
+ *     every writing call since) and reads the true count, one bounded stream
+ *     wait, only when bound + n > capacity; a call that does not grow so queues
+ *     its work as before.  A call that GROWS waits for the shard's stream, a
+ *     device call too, and therefore cannot be captured into a graph: reserve
+ *     beforehand where calls are captured.  pskv_sparse_reserve beyond the limit
+ *     raises the limit to the new capacity.  pskv_sparse_get_growth returns the
+ *     limit and the number of rebuilds done so far (reserve, automatic growth
+ *     and erase each count one);
+ *   - erase: pskv_sparse_erase(keys, n, flags) forgets keys: their slots are
+ *     freed, their rows and optimizer state are gone.  Checked before the
+ *     handle: flags other than PSKV_HOST / PSKV_DEVICE, null keys with n > 0.
+ *     n == 0 is PSKV_OK and does nothing at all.  Keys that are not stored and
+ *     keys listed twice are legal and set no error; the call never inserts.  It
+ *     runs in stream order and returns when done.  Afterwards an erased key is
+ *     not stored: it reads a zero row from the parameters and from every state
+ *     array, is absent from pskv_sparse_keys, and count has dropped by the
+ *     number of distinct stored keys erased.  Every other stored key keeps its
+ *     row and every state slot bit for bit.  A later writing call that names an
+ *     erased key inserts it as a new key (a zero row, the optimizer's start
+ *     state), and freed slots are usable again: at a full shard, erasing k
+ *     stored keys makes room for exactly k new ones.  Capacity, the step
+ *     counter and the configuration are unchanged; the full condition is
+ *     cleared and dropped keys are forgotten, as for reserve.  By relabelling:
+ *     on the row-shard twin an erase is an assign Add of zero rows plus
+ *     pskv_put_state of the start values at rank(K), after which rank may be
+ *     re-drawn for those keys.  This is a MAINTENANCE call: it rebuilds the
+ *     index and moves every surviving row, so its cost follows the keys stored,
+ *     not n, and it holds a second set of row arrays while it runs
+ *     (PSKV_ENOMEM leaves the shard as it was);
+ *   - the launches of a growth or an erase are counted in no pskv_*_time slot;
+ *   - not provided: shrinking; growth requested from the device without a host
+ *     step; eviction policies such as LRU or "erase zero rows" (a caller builds
+ *     them from pskv_sparse_keys, pskv_get and pskv_sparse_erase); an erase
+ *     whose cost follows n (tombstones and a free list); 64-bit keys; a sparse
+ *     scalar fast path (the resident request server and inline messages serve
+ *     scalar range shards only).
  *
  * Threading: one shard handle is used by one host thread at a time (the
  * reference calls a storage only from its ServerThread, server_thread.cpp:20-50);
@@ -485,6 +548,18 @@ int pskv_sparse_info_get(pskv_shard* s, pskv_sparse_info* out);
  * memory, or device memory with PSKV_DEVICE), *n = the number stored (it may
  * exceed cap: nothing past cap is written).  Waits for the shard's stream. */
 int pskv_sparse_keys(pskv_shard* s, uint32_t* out, uint64_t cap, uint64_t* n, int flags);
+/* Growth and erase of a sparse shard (semantics: the header comment, "Sparse
+ * shards").  Grow to hold `capacity` distinct keys; returns when done. */
+int pskv_sparse_reserve(pskv_shard* s, uint64_t capacity);
+/* Let writing calls grow the shard themselves, up to max_capacity (0 = fixed,
+ * the default).  A call that grows waits for the shard's stream. */
+int pskv_sparse_set_growth(pskv_shard* s, uint64_t max_capacity);
+/* The limit and the rebuilds done so far; either output may be null. */
+int pskv_sparse_get_growth(pskv_shard* s, uint64_t* max_capacity, uint64_t* rebuilds);
+/* Forget keys (host memory, or device memory with PSKV_DEVICE): their slots
+ * are freed, their rows and optimizer state are gone.  A maintenance call whose
+ * cost follows the keys stored; returns when done. */
+int pskv_sparse_erase(pskv_shard* s, const uint32_t* keys, uint64_t n, int flags);
 int pskv_shard_destroy(pskv_shard* s);
 
 /* Push: apply n (key, value) pairs.  Asynchronous on the shard's stream for

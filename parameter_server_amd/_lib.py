@@ -82,6 +82,7 @@ EXPORTED = [
     "pskv_apply_pooled", "pskv_apply_pooled_grouped",
     "pskv_shard_set_optimizer_cfg", "pskv_shard_get_optimizer_cfg",
     "pskv_shard_create_sparse", "pskv_sparse_info_get", "pskv_sparse_keys", "pskv_index_time",
+    "pskv_sparse_reserve", "pskv_sparse_set_growth", "pskv_sparse_get_growth", "pskv_sparse_erase",
 ]
 
 
@@ -195,6 +196,10 @@ def _load():
         "pskv_shard_create_sparse": ([i32, u64, i32, i32, u32, ctypes.POINTER(vp)], i32),
         "pskv_sparse_info_get": ([vp, ctypes.POINTER(PskvSparseInfo)], i32),
         "pskv_sparse_keys": ([vp, vp, u64, ctypes.POINTER(u64), i32], i32),
+        "pskv_sparse_reserve": ([vp, u64], i32),
+        "pskv_sparse_set_growth": ([vp, u64], i32),
+        "pskv_sparse_get_growth": ([vp, ctypes.POINTER(u64), ctypes.POINTER(u64)], i32),
+        "pskv_sparse_erase": ([vp, vp, u64, i32], i32),
         "pskv_index_time": ([vp, ctypes.POINTER(u64), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(u64)], i32),
     }
     for name, (args, res) in sig.items():

@@ -30,6 +30,7 @@ CPP_TESTS = {  # program -> (source in tests/cpp, links the oracle checker)
     "hip_storage_pooled_push_test": ("hip_storage_pooled_push_test.cpp", False),
     "hip_storage_pooled_push_group_test": ("hip_storage_pooled_push_group_test.cpp", False),
     "hip_storage_sparse_test": ("hip_storage_sparse_test.cpp", False),
+    "hip_storage_sparse_grow_test": ("hip_storage_sparse_grow_test.cpp", False),
     "pooled_push_group_plan_test": ("pooled_push_group_plan_test.cpp", False),  # host-only: the planner's arithmetic
 }
 ORACLE_DIR = os.path.join(ROOT, "oracle")

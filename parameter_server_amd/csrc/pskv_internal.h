@@ -394,5 +394,17 @@ hipError_t launch_index_insert(const GroupArgs& ga, uint32_t nwg, const SparseIn
 // row kernels drop, with kErrSparseFull set.
 hipError_t launch_index_translate(bool writing, const GroupArgs& ga, uint32_t nwg, const SparseIndex& x,
                                   hipStream_t st);
+// Growth and erase, on a shard with nothing else queued.
+// Mark: dead[ids[i]] = 1 for every id <= capacity (`dead`: capacity + 1 zeroed
+// flags; ids from a reading translate).  Rebuild: the index of `x` -- its table
+// zeroed by the caller -- from old_keys[0 .. count), the keys of the old slots.
+// dead == nullptr: every slot keeps its number and x.stat[0] is left alone.
+// Else the slots without a flag are compacted in unspecified order: new numbers
+// are drawn from x.stat[0], which the caller zeroed and which ends at the
+// number of survivors, and survivors[new slot] = old slot.  Either way
+// x.slot_keys is written and the full bits of x.stat[1] are cleared.
+hipError_t launch_index_mark_dead(const uint32_t* ids, uint64_t n, uint32_t capacity, uint8_t* dead, hipStream_t st);
+hipError_t launch_index_rebuild(const uint32_t* old_keys, uint32_t count, const uint8_t* dead, const SparseIndex& x,
+                                uint32_t* survivors, hipStream_t st);
 
 }  // namespace pskv

@@ -399,6 +399,13 @@ struct pskv_shard {
   uint64_t sp_table_slots = 0;
   void* sp_ids = nullptr;  // a device call's slot ids (grown on demand, as the K5 scratch)
   size_t sp_ids_bytes = 0;
+  // Growth (pskv_sparse_set_growth).  sp_max_capacity: writing
+  // calls may grow the shard up to it (0: fixed).  sp_bound: an upper bound of
+  // the keys stored after everything queued -- the count at the last read-back
+  // plus the key positions of every writing call since (kept while growth is on).
+  uint64_t sp_max_capacity = 0;
+  uint64_t sp_bound = 0;
+  uint64_t sp_rebuilds = 0;  // rebuilds of the index done (reserve, automatic growth, erase)
   uint64_t rows_held() const { return range + (sparse ? 1u : 0u); }  // rows of the dense array and of each state array
   SparseIndex sindex() const {
     return SparseIndex{sp_table, sp_slot_keys, ovf.c->stat, sp_table_slots - 1, (uint32_t)range};
@@ -794,6 +801,7 @@ int read_overflow_stat(pskv_shard* s, uint32_t* count, uint32_t* err) {
   *count = st->stat[0];
   *err = st->stat[1];
   s->ocount_known = st->stat[0];
+  if (s->sparse) s->sp_bound = std::min<uint64_t>(st->stat[0], s->range);  // (the stream is idle: the true count)
   if (st->t.keys && st->t.keys != s->cur.keys) {
     s->cur = st->t;
     s->ocap = st->t.mask + 1;
@@ -1659,6 +1667,8 @@ bool rows_unit16(const pskv_shard* s, std::initializer_list<const void*> arrays,
 // in the device staging (a host call) and are overwritten; else the ids go to
 // the shard's scratch and the caller's keys are only read.  The launches are
 // one timed operation (kTimeIndex), elements = the keys.
+int sparse_autogrow(pskv_shard* s, uint64_t n);
+
 int sparse_ids(pskv_shard* s, std::vector<pskv_batch>& v, bool writing, bool in_place) {
   std::vector<pskv_batch> io(v.size());  // vals: where the batch's ids go
   uint64_t elems = 0;
@@ -1668,6 +1678,10 @@ int sparse_ids(pskv_shard* s, std::vector<pskv_batch>& v, bool writing, bool in_
     bytes += round16(b.n * sizeof(uint32_t));
   }
   if (elems == 0) return PSKV_OK;
+  // growth first, before any key of the call is inserted (and before sindex()
+  // is taken: a growth replaces the arrays it names)
+  if (writing && s->sp_max_capacity)
+    if (int rc = sparse_autogrow(s, elems)) return rc;
   if (!in_place)
     if (int rc = ensure_scratch(s, &s->sp_ids, &s->sp_ids_bytes, bytes)) return rc;
   size_t at = 0;
@@ -1790,16 +1804,21 @@ int rows_add_device(pskv_shard* s, const std::vector<pskv_batch>& v, const Dense
 }
 
 // A row shard has no request server, so neither this nor rows_get_from stops one.
-int rows_add_to(pskv_shard* s, const std::vector<pskv_batch>& in, int flags, const DenseView& d, int mode,
+// slot: the array written, -1 the dense array, else the optimizer's state slot
+// (looked up behind the front: a sparse shard's front may grow the shard, which
+// replaces every array).
+int rows_add_to(pskv_shard* s, const std::vector<pskv_batch>& in, int flags, int slot, int mode,
                 const RowFront& f) {
   HstageHold hold(s);  // the call returns before its DMA: the hold stays armed
   RowCall c;
   if (int rc = rows_front(s, in, flags, f, hold, &c)) return rc;
-  return c.v.empty() ? PSKV_OK : rows_add_device(s, c.views(), d, mode);
+  if (c.v.empty()) return PSKV_OK;
+  const DenseView d = slot < 0 ? s->dview() : DenseView{s->opt_slot[slot], s->key_begin, s->range, 0};
+  return rows_add_device(s, c.views(), d, mode);
 }
 
 int rows_add(pskv_shard* s, const std::vector<pskv_batch>& in, int flags) {
-  return rows_add_to(s, in, flags, s->dview(), s->mode,
+  return rows_add_to(s, in, flags, /*slot=*/-1, s->mode,
                      RowFront{"pskv_add", &s->n_add, false, "row shard: key", "a row shard stores no out-of-range keys",
                               /*with_values=*/true});
 }
@@ -2012,6 +2031,124 @@ int opt_reset_state(pskv_shard* s) {
     } else
       PSKV_HIP(hipMemsetAsync(s->opt_slot[i], 0, opt_array_bytes(s), s->stream));
   }
+  return PSKV_OK;
+}
+
+// ------------------------------------------- sparse shards: growth and erase
+// DESIGN.md §8l.  One routine behind pskv_sparse_reserve, automatic growth and
+// pskv_sparse_erase: every array of the shard is built again at `new_capacity`
+// slots from slot_keys[0 .. count) and swapped in.
+struct DevBuf {  // a device allocation that is freed unless it was swapped into the shard
+  void* p = nullptr;
+  ~DevBuf() {
+    if (p) (void)hipFree(p);
+  }
+  bool alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1) == hipSuccess; }
+};
+
+// dead: null (growth: every slot keeps its number and its rows move by plain
+// copies), or capacity + 1 flags set in stream order before this call (erase:
+// the slots without a flag are compacted, k_index_rebuild).  Waits for the
+// stream first and last; every new array is allocated before anything is
+// touched, so PSKV_ENOMEM leaves the shard as it was.  The launches are not
+// timed operations.
+int sparse_rebuild(pskv_shard* s, uint64_t new_capacity, const uint8_t* dead) {
+  uint32_t cnt = 0, err = 0;
+  if (int rc = read_overflow_stat(s, &cnt, &err)) return rc;
+  const uint32_t count = (uint32_t)std::min<uint64_t>(cnt, s->range);
+  const size_t rb = row_bytes(s);
+  const uint64_t table_slots = sparse_table_slots(new_capacity);
+  const int nslots = opt_slots(s->opt.kind);
+  // the row-shaped arrays: the parameters, then the state slots the kind has
+  void** old_rows[3] = {&s->dense, &s->opt_slot[0], &s->opt_slot[1]};
+  DevBuf rows[3], gsum, owner, slot_keys, table, survivors;
+  bool ok = true;
+  for (int a = 0; a < 1 + nslots; ++a) ok = ok && rows[a].alloc((new_capacity + 1) * rb);
+  if (s->opt_gsum) ok = ok && gsum.alloc((new_capacity + 1) * rb);
+  if (s->owner) ok = ok && owner.alloc(new_capacity * sizeof(unsigned long long));
+  ok = ok && slot_keys.alloc(new_capacity * sizeof(uint32_t)) && table.alloc(table_slots * sizeof(unsigned long long));
+  if (dead) ok = ok && survivors.alloc((size_t)count * sizeof(uint32_t));
+  if (!ok) {
+    (void)hipGetLastError();
+    return fail(PSKV_ENOMEM, "sparse shard rebuild: allocating the arrays of " + std::to_string(new_capacity) +
+                                 " slots failed (the shard is unchanged)");
+  }
+  // the index
+  PSKV_HIP(hipMemsetAsync(table.p, 0, table_slots * sizeof(unsigned long long), s->stream));
+  if (dead) PSKV_HIP(hipMemsetAsync(s->ovf.c->stat, 0, sizeof(uint32_t), s->stream));  // the new slot counter
+  const SparseIndex nx{static_cast<unsigned long long*>(table.p), static_cast<uint32_t*>(slot_keys.p), s->ovf.c->stat,
+                       table_slots - 1, (uint32_t)new_capacity};
+  PSKV_HIP(launch_index_rebuild(s->sp_slot_keys, count, dead, nx, static_cast<uint32_t*>(survivors.p), s->stream));
+  uint32_t kept = count;
+  if (dead) {  // how many survived: the gather below is sized by it
+    if (int rc = read_overflow_stat(s, &kept, &err)) return rc;
+    kept = std::min(kept, count);
+  }
+  // the rows of the survivors, then the start values behind them (opt_reset_state's)
+  for (int a = 0; a < 1 + nslots; ++a) {
+    char* fresh = static_cast<char*>(rows[a].p);
+    if (kept && !dead)
+      PSKV_HIP(hipMemcpyAsync(fresh, *old_rows[a], (size_t)kept * rb, hipMemcpyDeviceToDevice, s->stream));
+    if (kept && dead) {
+      const std::vector<pskv_batch> mv{pskv_batch{static_cast<const uint32_t*>(survivors.p), fresh, kept}};
+      const LaunchGroup g = make_group(mv, 0, 1, kGeneralChunk);
+      const DenseView from{*old_rows[a], 0, s->rows_held(), 0};
+      const RowShape rs = row_shape(s->width, s->vb, rows_unit16(s, {from.param}, mv));
+      PSKV_HIP(launch_row_gather(s->vb, s->tune_nt, g.ga, g.nwg, from, rs, s->stream));
+    }
+    const bool accum = a > 0 && (s->opt.kind == PSKV_OPT_ADAGRAD || (s->opt.kind == PSKV_OPT_FTRL && a == 2));
+    const uint64_t tail = new_capacity - kept;  // rows [kept, new_capacity), then the zero row
+    if (accum && tail) {
+      PSKV_HIP(launch_fill(s->dtype, fresh + (size_t)kept * rb, tail * (uint64_t)s->width, s->opt.init_accum,
+                           s->stream));
+      PSKV_HIP(hipMemsetAsync(fresh + new_capacity * rb, 0, rb, s->stream));
+    } else {
+      PSKV_HIP(hipMemsetAsync(fresh + (size_t)kept * rb, 0, (tail + 1) * rb, s->stream));
+    }
+  }
+  if (gsum.p) PSKV_HIP(hipMemsetAsync(gsum.p, 0, (new_capacity + 1) * rb, s->stream));
+  if (owner.p) PSKV_HIP(hipMemsetAsync(owner.p, 0, new_capacity * sizeof(unsigned long long), s->stream));
+  if (int rc = wait_stream(s, s->stream, "shard stream (sparse rebuild)")) return rc;
+  // nothing is queued: the new arrays take over and the old ones go with the DevBufs
+  for (int a = 0; a < 1 + nslots; ++a) std::swap(*old_rows[a], rows[a].p);
+  if (gsum.p) std::swap(s->opt_gsum, gsum.p);
+  if (owner.p) {
+    void* o = s->owner;
+    s->owner = static_cast<unsigned long long*>(owner.p);
+    owner.p = o;
+  }
+  {
+    void* k = s->sp_slot_keys;
+    s->sp_slot_keys = static_cast<uint32_t*>(slot_keys.p);
+    slot_keys.p = k;
+    void* t = s->sp_table;
+    s->sp_table = static_cast<unsigned long long*>(table.p);
+    table.p = t;
+  }
+  s->sp_table_slots = table_slots;
+  s->range = new_capacity;
+  s->sp_bound = kept;
+  s->ocount_known = kept;
+  ++s->sp_rebuilds;
+  return PSKV_OK;
+}
+
+// The growth rule of a writing call of n key positions (pskv.h "Sparse
+// shards"): grow iff count + n > capacity, to min(max, max(2 * capacity,
+// count + n)).  count is read -- one bounded stream wait -- only when the
+// host-side bound cannot rule the growth out; while bound + n <= capacity,
+// count + n <= capacity too, so both make the same decision.
+int sparse_autogrow(pskv_shard* s, uint64_t n) {
+  if (s->range < s->sp_max_capacity && s->sp_bound + n > s->range) {
+    uint32_t cnt = 0, err = 0;
+    if (int rc = read_overflow_stat(s, &cnt, &err)) return rc;  // (sp_bound = count)
+    const uint64_t count = s->sp_bound;
+    if (count + n > s->range) {
+      const uint64_t want = std::min(s->sp_max_capacity, std::max(2 * s->range, count + n));
+      if (int rc = sparse_rebuild(s, want, nullptr)) return rc;
+    }
+  }
+  s->sp_bound = std::min(s->sp_bound + n, s->range);  // (count never exceeds the capacity)
   return PSKV_OK;
 }
 
@@ -2890,6 +3027,81 @@ int pskv_sparse_keys(pskv_shard* s, uint32_t* out, uint64_t cap, uint64_t* n, in
   return wait_stream(s, s->stream, "shard stream (sparse keys)");
 }
 
+// What is wrong with `capacity` as a sparse shard's new capacity or growth limit, or null.
+static const char* sparse_capacity_refusal(const pskv_shard* s, uint64_t capacity) {
+  if (!s->sparse) return "not a sparse shard (pskv_shard_create_sparse)";
+  if (capacity < s->range) return "capacity is below the shard's current capacity (a sparse shard does not shrink)";
+  if ((capacity + 1) * (uint64_t)s->width * (uint64_t)s->vb > (1ull << 46))
+    return "(capacity + 1) * width * value bytes exceeds 2^46 bytes";
+  return nullptr;
+}
+
+int pskv_sparse_reserve(pskv_shard* s, uint64_t capacity) {
+  if (capacity == 0 || capacity > kSparseMaxCapacity)
+    return fail(PSKV_EINVAL, "pskv_sparse_reserve: capacity must be 1..2^31 - 2");
+  if (!s) return fail(PSKV_EINVAL, "pskv_sparse_reserve: null shard");
+  if (const char* why = sparse_capacity_refusal(s, capacity))
+    return fail(PSKV_EINVAL, std::string("pskv_sparse_reserve: ") + why);
+  if (capacity == s->range) return PSKV_OK;
+  int rc = use_device(s);
+  if (rc) return rc;
+  if ((rc = sparse_rebuild(s, capacity, nullptr))) return rc;
+  if (s->sp_max_capacity && s->sp_max_capacity < capacity) s->sp_max_capacity = capacity;  // (never below the capacity)
+  return PSKV_OK;
+}
+
+int pskv_sparse_set_growth(pskv_shard* s, uint64_t max_capacity) {
+  if (max_capacity > kSparseMaxCapacity)
+    return fail(PSKV_EINVAL, "pskv_sparse_set_growth: max_capacity must be 0 (fixed) or at most 2^31 - 2");
+  if (!s) return fail(PSKV_EINVAL, "pskv_sparse_set_growth: null shard");
+  if (const char* why = sparse_capacity_refusal(s, max_capacity ? max_capacity : s->range))
+    return fail(PSKV_EINVAL, std::string("pskv_sparse_set_growth: max_capacity: ") + why);
+  s->sp_max_capacity = max_capacity;
+  s->sp_bound = s->range;  // (no read-back yet: the first call that could grow makes one)
+  return PSKV_OK;
+}
+
+int pskv_sparse_get_growth(pskv_shard* s, uint64_t* max_capacity, uint64_t* rebuilds) {
+  if (!s) return fail(PSKV_EINVAL, "pskv_sparse_get_growth: null shard");
+  if (!s->sparse) return fail(PSKV_EINVAL, "pskv_sparse_get_growth: not a sparse shard (pskv_shard_create_sparse)");
+  if (max_capacity) *max_capacity = s->sp_max_capacity;
+  if (rebuilds) *rebuilds = s->sp_rebuilds;
+  return PSKV_OK;
+}
+
+int pskv_sparse_erase(pskv_shard* s, const uint32_t* keys, uint64_t n, int flags) {
+  if (flags & ~PSKV_DEVICE) return fail(PSKV_EINVAL, "pskv_sparse_erase: unknown flags (PSKV_HOST or PSKV_DEVICE)");
+  if (n && !keys) return fail(PSKV_EINVAL, "pskv_sparse_erase: null keys with n > 0");
+  if (!s) return fail(PSKV_EINVAL, "pskv_sparse_erase: null shard");
+  if (!s->sparse) return fail(PSKV_EINVAL, "pskv_sparse_erase: not a sparse shard (pskv_shard_create_sparse)");
+  if (n == 0) return PSKV_OK;
+  int rc = use_device(s);
+  if (rc) return rc;
+  // the list's slot ids (the reading translate: an absent key carries
+  // `capacity`), then one flag per id; the rebuild leaves the flagged slots out
+  DevBuf ids, dead;
+  if (!ids.alloc(n * sizeof(uint32_t)) || !dead.alloc(s->range + 1)) {
+    (void)hipGetLastError();
+    return fail(PSKV_ENOMEM, "pskv_sparse_erase: scratch allocation failed (the shard is unchanged)");
+  }
+  uint32_t* idp = static_cast<uint32_t*>(ids.p);
+  const uint32_t* from = keys;
+  if (!(flags & PSKV_DEVICE)) {  // host keys: into the scratch, translated in place
+    PSKV_HIP(hipMemcpyAsync(idp, keys, n * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
+    from = idp;
+  }
+  PSKV_HIP(hipMemsetAsync(dead.p, 0, s->range + 1, s->stream));
+  std::vector<pskv_batch> io;
+  push_pieces(io, pskv_batch{from, idp, n}, sizeof(uint32_t));
+  const SparseIndex x = s->sindex();
+  for (const Span& sp : split_groups(io)) {
+    const LaunchGroup g = make_group(io, sp.first, sp.second, kGeneralChunk);
+    PSKV_HIP(launch_index_translate(/*writing=*/false, g.ga, g.nwg, x, s->stream));
+  }
+  PSKV_HIP(launch_index_mark_dead(idp, n, (uint32_t)s->range, static_cast<uint8_t*>(dead.p), s->stream));
+  return sparse_rebuild(s, s->range, static_cast<const uint8_t*>(dead.p));
+}
+
 int pskv_index_time(pskv_shard* s, uint64_t* launches, double* total_ms, uint64_t* elements) {
   if (!s) return fail(PSKV_EINVAL, "pskv_index_time: null shard");
   int rc = use_device(s);
@@ -3192,9 +3404,8 @@ static int state_call(pskv_shard* s, const std::string& who, bool adagrad_only, 
   rc = srv_stop(s);
   if (rc) return rc;
   const std::vector<pskv_batch> in{pskv_batch{keys, vals, n}};
-  const DenseView d{arr, s->key_begin, s->range, 0};
   if (!put) return rows_get_from(s, in, flags, s->read_view(arr), who.c_str(), nullptr);
-  return rows_add_to(s, in, flags, d, PSKV_ASSIGN,
+  return rows_add_to(s, in, flags, slot, PSKV_ASSIGN,
                      RowFront{who.c_str(), nullptr, false, "key",
                               "optimizer state is kept for the shard's own keys only", /*with_values=*/true});
 }
@@ -3248,7 +3459,7 @@ int pskv_sync(pskv_shard* s) {
     if (err & (kErrSparseFull | kErrRowOutOfRange))
       return fail(PSKV_ESTATE, "sparse shard full: a writing call met new keys with all " + std::to_string(s->range) +
                                    " slots taken; those keys were dropped whole, the rest of the call was applied "
-                                   "(pskv_clear resets this)");
+                                   "(pskv_sparse_reserve, pskv_sparse_erase or pskv_clear resets this)");
     return PSKV_OK;
   }
   if (err & kErrOverflowFull)

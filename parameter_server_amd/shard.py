@@ -52,7 +52,9 @@ class Shard:
     capacity > 0 (or Shard.sparse) makes a sparse shard instead: it owns every
     uint32 key and holds at most `capacity` distinct ones, at any width, its
     memory following capacity and not the key space (include/pskv.h, "Sparse
-    shards").  key_begin, key_end and overflow_slots are not used."""
+    shards").  key_begin, key_end and overflow_slots are not used.  reserve,
+    set_growth and erase change what it holds room for; `capacity` follows
+    reserve and load_state_dict, sparse_info()["capacity"] is always current."""
 
     def __init__(self, key_begin: int = 0, key_end: int = 1 << 32, dtype=np.float32,
                  mode: str = "assign", device: int = 0, overflow_slots: int = 0, options=None,
@@ -82,11 +84,19 @@ class Shard:
 
     @classmethod
     def sparse(cls, capacity: int, dtype=np.float32, mode: str = "assign", device: int = 0, width: int = 1,
-               options=None) -> "Shard":
-        """A sparse shard of at most `capacity` distinct keys (pskv_shard_create_sparse)."""
+               options=None, max_capacity=None) -> "Shard":
+        """A sparse shard of at most `capacity` distinct keys (pskv_shard_create_sparse).
+        max_capacity: writing calls may grow it up to that many (set_growth)."""
         if int(capacity) == 0:
             raise ValueError("Shard.sparse: capacity must be positive")
-        return cls(dtype=dtype, mode=mode, device=device, options=options, width=width, capacity=capacity)
+        s = cls(dtype=dtype, mode=mode, device=device, options=options, width=width, capacity=capacity)
+        if max_capacity is not None:
+            try:
+                s.set_growth(max_capacity)
+            except Exception:
+                s.close()
+                raise
+        return s
 
     # ------------------------------------------------------------ lifetime
     def close(self):
@@ -479,6 +489,13 @@ class Shard:
         kind = self.optimizer()["kind"]
         if len(d["slots"]) != self._OPT_SLOTS[kind]:
             raise ValueError(f"load_state_dict: {len(d['slots'])} state slots for optimizer {kind!r}")
+        if self.is_sparse:
+            # a checkpoint of more keys than the capacity: one reserve, within
+            # the growth limit (a shard without growth drops what does not fit,
+            # as before; keys stored beside the checkpoint's grow it on the way)
+            limit, held = self.growth()["max_capacity"], int(np.unique(keys).size)
+            if limit and held > self.sparse_info()["capacity"]:
+                self.reserve(min(held, limit))
         self.add(keys, d["p"])
         for i, v in enumerate(d["slots"]):
             self.put_state(keys, v, slot=i)
@@ -498,6 +515,39 @@ class Shard:
         out = np.empty(max(self.sparse_info()["count"], 1), dtype=np.uint32)
         check(lib.pskv_sparse_keys(self._h, out.ctypes.data, out.size, ctypes.byref(n), _lib.PSKV_HOST))
         return out[:min(n.value, out.size)]
+
+    def reserve(self, capacity: int):
+        """Grow a sparse shard to hold `capacity` distinct keys (pskv_sparse_reserve):
+        every stored key keeps its row and state; returns when done."""
+        if not 0 <= int(capacity) < 1 << 64:
+            raise ValueError(f"capacity {capacity} out of range")
+        check(lib.pskv_sparse_reserve(self._h, int(capacity)))
+        self.capacity = max(self.capacity, int(capacity))
+
+    def set_growth(self, max_capacity: int):
+        """Let writing calls grow the shard themselves, up to max_capacity
+        distinct keys; 0 = fixed (pskv_sparse_set_growth).  A call that grows
+        waits for the shard's stream."""
+        if not 0 <= int(max_capacity) < 1 << 64:
+            raise ValueError(f"max_capacity {max_capacity} out of range")
+        check(lib.pskv_sparse_set_growth(self._h, int(max_capacity)))
+
+    def growth(self) -> dict:
+        """pskv_sparse_get_growth: max_capacity (0 = fixed) and the rebuilds done
+        so far (reserve, automatic growth and erase each count one)."""
+        m, r = ctypes.c_uint64(), ctypes.c_uint64()
+        check(lib.pskv_sparse_get_growth(self._h, ctypes.byref(m), ctypes.byref(r)))
+        return {"max_capacity": m.value, "rebuilds": r.value}
+
+    def erase(self, keys):
+        """Forget keys (pskv_sparse_erase): numpy keys or a device tensor, as get
+        takes them.  A maintenance call: its cost follows the keys stored."""
+        if _is_torch(keys):
+            self._check_dev(keys)
+            check(lib.pskv_sparse_erase(self._h, keys.data_ptr(), keys.numel(), _lib.PSKV_DEVICE))
+            return
+        k = self._host_keys(keys)
+        check(lib.pskv_sparse_erase(self._h, k.ctypes.data, k.size, _lib.PSKV_HOST))
 
     def index_time(self):
         """A sparse shard's index launches, one operation per call (pskv_index_time)."""
