@@ -4,10 +4,12 @@
 // key check of host inputs, K5's bucket rule, the bags, chunks and windows
 // of a pooled pull, the bag of a position of a pooled push, and the launch
 // groups, descriptors and staging of a grouped pooled push (the part the
-// kernels share is marked PSKV_HD).  No HIP and
+// kernels share is marked PSKV_HD), the optimizer's state slots and a sparse
+// shard's sizes and growth rule.  No HIP and
 // no shard state: everything here is a function of its arguments, so it is
 // tested on the CPU (tests/cpp/host_plan_test.cpp, tests/cpp/pooled_plan_test.cpp,
-// tests/cpp/pooled_push_plan_test.cpp, tests/cpp/pooled_push_group_plan_test.cpp).  Internal linkage throughout: libpskv.so
+// tests/cpp/pooled_push_plan_test.cpp, tests/cpp/pooled_push_group_plan_test.cpp,
+// tests/cpp/sparse_plan_test.cpp).  Internal linkage throughout: libpskv.so
 // exports nothing from this header (the types the kernels do not share are in
 // an unnamed namespace, so that no instantiation over them is exported either).
 #pragma once
@@ -536,6 +538,43 @@ static inline PoolStageLayout pool_stage_layout(const std::vector<pskv_pool_batc
   }
   l.total = o;
   return l;
+}
+
+// ------------------------------------- optimizer state slots, sparse shards
+// State slots per kind (pskv_optimizer_kind), and whether a slot starts at
+// init_accum (Adagrad's h, FTRL's n) or, as every other slot, at zero.
+static inline int opt_slots(int kind) {
+  return (kind == PSKV_OPT_ADAM || kind == PSKV_OPT_FTRL) ? 2
+         : (kind == PSKV_OPT_ADAGRAD || kind == PSKV_OPT_MOMENTUM) ? 1 : 0;
+}
+static inline bool opt_slot_is_accum(int kind, int slot) {
+  return (kind == PSKV_OPT_ADAGRAD && slot == 0) || (kind == PSKV_OPT_FTRL && slot == 1);
+}
+
+// A sparse shard's limits (pskv.h "Sparse shards"): slot + 1
+// fits an index entry's 31 bits and 0xFFFFFFFF stays free as the id the row
+// kernels drop; the index has at least two entries per slot.
+constexpr uint64_t kSparseMaxCapacity = (1ull << 31) - 2;
+static inline uint64_t sparse_table_slots(uint64_t capacity) { return std::max<uint64_t>(16, next_pow2(2 * capacity)); }
+
+// The capacity behind a writing call of n key positions at `capacity` slots
+// holding `count` keys, growth limit `max` (0: off): grown iff count + n >
+// capacity, to min(max, max(2 * capacity, count + n)).
+static inline uint64_t sparse_grown_capacity(uint64_t capacity, uint64_t count, uint64_t n, uint64_t max) {
+  if (capacity >= max || count + n <= capacity) return capacity;
+  return std::min(max, std::max(2 * capacity, count + n));
+}
+// Must the count be read to decide?  Not while this is false for a bound >= count.
+static inline bool sparse_may_grow(uint64_t bound, uint64_t n, uint64_t capacity, uint64_t max) {
+  return capacity < max && bound + n > capacity;
+}
+
+// What is wrong with `capacity` as the capacity or growth limit of a sparse
+// shard of `current` slots and rows of row_bytes, or null.
+static inline const char* sparse_capacity_error(uint64_t current, uint64_t capacity, uint64_t row_bytes) {
+  if (capacity < current) return "capacity is below the shard's current capacity (a sparse shard does not shrink)";
+  if ((capacity + 1) * row_bytes > (1ull << 46)) return "(capacity + 1) * width * value bytes exceeds 2^46 bytes";
+  return nullptr;
 }
 
 }  // namespace

@@ -32,6 +32,7 @@
 #include <cerrno>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
@@ -406,7 +407,19 @@ struct pskv_shard {
   uint64_t sp_max_capacity = 0;
   uint64_t sp_bound = 0;
   uint64_t sp_rebuilds = 0;  // rebuilds of the index done (reserve, automatic growth, erase)
-  uint64_t rows_held() const { return range + (sparse ? 1u : 0u); }  // rows of the dense array and of each state array
+  uint64_t rows_held() const { return range + (sparse ? 1u : 0u); }  // rows of every row-shaped array
+  // The row-shaped arrays, described once: the parameters, the two state
+  // slots, the gradient scratch.  `used`: the current kind has the array;
+  // `start`: the value a fresh row of it holds.
+  struct RowArray { void** p; bool used; double start; };
+  static constexpr int kRowArrays = 4;
+  RowArray row_array(int a) {
+    if (a == 0) return RowArray{&dense, true, 0.0};
+    if (a == 3) return RowArray{&opt_gsum, opt.kind != PSKV_OPT_NONE, 0.0};
+    return RowArray{&opt_slot[a - 1], a - 1 < opt_slots(opt.kind),
+                    opt_slot_is_accum(opt.kind, a - 1) ? opt.init_accum : 0.0};
+  }
+  RowArray row_array(int a) const { return const_cast<pskv_shard*>(this)->row_array(a); }  // (for readers of used / start)
   SparseIndex sindex() const {
     return SparseIndex{sp_table, sp_slot_keys, ovf.c->stat, sp_table_slots - 1, (uint32_t)range};
   }
@@ -798,15 +811,27 @@ int read_overflow_stat(pskv_shard* s, uint32_t* count, uint32_t* err) {
   std::memset(st, 0, sizeof(OvfCtl));
   PSKV_HIP(hipMemcpyAsync(st, s->ovf.c, sizeof(OvfCtl), hipMemcpyDeviceToHost, s->stream));
   if (int rc = wait_stream(s, s->stream, "shard stream (overflow count read-back)")) return rc;
-  *count = st->stat[0];
+  const uint32_t cnt = *count = st->stat[0];
   *err = st->stat[1];
-  s->ocount_known = st->stat[0];
-  if (s->sparse) s->sp_bound = std::min<uint64_t>(st->stat[0], s->range);  // (the stream is idle: the true count)
+  s->ocount_known = cnt;
+  // a sparse shard: stat[0] is the slot counter, which an overfull call runs
+  // past the capacity; the stream is idle, so this is the true count, and
+  // sp_bound, the host's upper bound of it, is refreshed here and nowhere else
+  if (s->sparse) s->sp_bound = std::min<uint64_t>(cnt, s->range);
   if (st->t.keys && st->t.keys != s->cur.keys) {
     s->cur = st->t;
     s->ocap = st->t.mask + 1;
   }
   free_stale_tables(s);
+  return PSKV_OK;
+}
+
+// The keys a sparse shard holds: one read-back (a bounded stream wait), which
+// clamps the slot counter to the capacity and leaves the result in sp_bound.
+int sparse_count(pskv_shard* s, uint64_t* count) {
+  uint32_t cnt = 0, err = 0;
+  if (int rc = read_overflow_stat(s, &cnt, &err)) return rc;
+  *count = s->sp_bound;
   return PSKV_OK;
 }
 
@@ -1707,15 +1732,6 @@ int sparse_ids(pskv_shard* s, std::vector<pskv_batch>& v, bool writing, bool in_
   return PSKV_OK;
 }
 
-// The same for pooled batches.
-int sparse_pool_ids(pskv_shard* s, std::vector<pskv_pool_batch>& v, bool writing, bool in_place) {
-  std::vector<pskv_batch> k(v.size());
-  for (size_t i = 0; i < v.size(); ++i) k[i] = pskv_batch{v[i].keys, nullptr, v[i].n};
-  if (int rc = sparse_ids(s, k, writing, in_place)) return rc;
-  for (size_t i = 0; i < v.size(); ++i) v[i].keys = k[i].keys;
-  return PSKV_OK;
-}
-
 // The front of every row-shaped call: a row Add or Get, an optimizer step, a
 // read or write of optimizer state.
 struct RowFront {
@@ -1734,11 +1750,19 @@ struct RowCall {
   const std::vector<pskv_batch>& views() const { return host ? dv : v; }  // what the kernels read
 };
 
-// The front's checks, without the staging (a pooled pull stages its own
-// layout): the pieces are in c->v (empty: the call holds no key and nothing
-// further was done), the call is counted, the device is selected, the server
-// stopped and a host call's keys are inside the range.
-int rows_front_checks(pskv_shard* s, const std::vector<pskv_batch>& in, int flags, const RowFront& f, RowCall* c) {
+// What a host call is told about the first key outside the range (both fronts).
+int refuse_key(const std::string& who, const char* refusal, uint32_t key, const char* why) {
+  return fail(PSKV_EINVAL, who + ": " + refusal + " " + std::to_string(key) + " is outside [key_begin, key_end); " + why +
+                               " (nothing was applied)");
+}
+
+// The pieces are in c->v (empty: the call holds no key and nothing further was
+// done), the call is counted, the device is selected and the server stopped.
+// A host call's keys are checked before anything is queued (nothing is
+// applied); its pieces are then on their way to the device staging, and
+// `hold`, the caller's, is armed.
+int rows_front(pskv_shard* s, const std::vector<pskv_batch>& in, int flags, const RowFront& f, HstageHold& hold,
+               RowCall* c) {
   for (auto& b : in) {
     if (b.n == 0) continue;
     if (!b.keys || !b.vals) return fail(PSKV_EINVAL, std::string(f.what) + ": null keys/vals with n > 0");
@@ -1749,22 +1773,10 @@ int rows_front_checks(pskv_shard* s, const std::vector<pskv_batch>& in, int flag
   int rc = use_device(s);
   if (rc) return rc;
   if (f.stop_server && (rc = srv_stop(s))) return rc;
-  if ((flags & PSKV_DEVICE) || s->sparse) return PSKV_OK;  // (a sparse shard owns every key)
-  if (f.refusal)
-    if (const uint32_t* k = first_key_outside(c->v, s->key_begin, s->range))
-      return fail(PSKV_EINVAL, std::string(f.what) + ": " + f.refusal + " " + std::to_string(*k) +
-                                   " is outside [key_begin, key_end); " + f.why + " (nothing was applied)");
-  return PSKV_OK;
-}
-
-// A host call's keys are checked before anything is queued (nothing is
-// applied); its pieces are then on their way to the device staging, and
-// `hold`, the caller's, is armed.
-int rows_front(pskv_shard* s, const std::vector<pskv_batch>& in, int flags, const RowFront& f, HstageHold& hold,
-               RowCall* c) {
-  if (int rc = rows_front_checks(s, in, flags, f, c)) return rc;
-  if (c->v.empty()) return PSKV_OK;
   if (!(flags & PSKV_DEVICE)) {
+    if (f.refusal && !s->sparse)  // (a sparse shard owns every key)
+      if (const uint32_t* k = first_key_outside(c->v, s->key_begin, s->range))
+        return refuse_key(f.what, f.refusal, *k, f.why);
     c->host = true;
     c->lay = stage_layout(c->v, row_bytes(s), StageOrder::kKeysFirst);
     if (int rc = stage_keys_first(s, c->v, c->lay, row_bytes(s), f.with_values, hold, &c->dv)) return rc;
@@ -1836,6 +1848,20 @@ int rows_gather(pskv_shard* s, const std::vector<pskv_batch>& dv, const DenseVie
   return PSKV_OK;
 }
 
+// The way back of a host call's rows: bytes [at, at + bytes) of the device
+// staging go to the same offsets of the pinned staging, the stream is waited
+// for (bounded; `waiting` names the wait), the hold is dismissed and the pool
+// copies `back` (pinned staging -> the caller's buffers).
+int rows_to_host(pskv_shard* s, HstageHold& hold, size_t at, size_t bytes, const char* waiting,
+                 std::vector<Piece>& back) {
+  PSKV_HIP(hipMemcpyAsync(static_cast<char*>(s->hstage) + at, static_cast<char*>(s->dstage) + at, bytes,
+                          hipMemcpyDeviceToHost, s->stream));
+  if (int rc = wait_stream(s, s->stream, waiting)) return rc;
+  hold.dismiss();
+  run_copies(s, back, 0, back.size());
+  return PSKV_OK;
+}
+
 int rows_get_from(pskv_shard* s, const std::vector<pskv_batch>& in, int flags, const DenseView& src,
                   const char* what, uint64_t* calls) {
   HstageHold hold(s);
@@ -1843,18 +1869,11 @@ int rows_get_from(pskv_shard* s, const std::vector<pskv_batch>& in, int flags, c
   int rc = rows_front(s, in, flags, RowFront{what, calls, false, nullptr, nullptr, /*with_values=*/false}, hold, &c);
   if (rc || c.v.empty()) return rc;
   if ((rc = rows_gather(s, c.views(), src)) || !c.host) return rc;
-  // rows: device staging -> pinned staging -> the caller's buffers
-  char* h = static_cast<char*>(s->hstage);
-  char* d = static_cast<char*>(s->dstage);
-  PSKV_HIP(hipMemcpyAsync(h + c.lay.key_bytes, d + c.lay.key_bytes, c.lay.total - c.lay.key_bytes,
-                          hipMemcpyDeviceToHost, s->stream));
-  if (int rc2 = wait_stream(s, s->stream, "shard stream (row Get to host)")) return rc2;
-  hold.dismiss();
-  std::vector<Piece> pieces;
+  std::vector<Piece> back;
   for (size_t i = 0; i < c.v.size(); ++i)
-    add_pieces(pieces, h + c.lay.at[i].vals, static_cast<char*>(c.v[i].vals), c.v[i].n * row_bytes(s), -1);
-  run_copies(s, pieces, 0, pieces.size());
-  return PSKV_OK;
+    add_pieces(back, static_cast<char*>(s->hstage) + c.lay.at[i].vals, static_cast<char*>(c.v[i].vals),
+               c.v[i].n * row_bytes(s), -1);
+  return rows_to_host(s, hold, c.lay.key_bytes, c.lay.total - c.lay.key_bytes, "shard stream (row Get to host)", back);
 }
 
 int rows_get(pskv_shard* s, const std::vector<pskv_batch>& in, int flags) {
@@ -1890,6 +1909,41 @@ int stage_pool_batches(pskv_shard* s, const std::vector<pskv_pool_batch>& v, boo
   return pipelined_h2d(s, pieces, h, d, hold);
 }
 
+// The front of every pooled call (pskv_get_pooled, pskv_apply_pooled,
+// pskv_apply_pooled_grouped), beside rows_front.
+struct PoolFront {
+  const char* what;  // the call's name in messages
+  bool writing;      // a push: a sparse shard inserts its keys (growth first); a pull only reads
+  bool with_rows;    // a push stages its bag rows; a pull gets room for its result rows
+  const char* why;   // a host call's refusal of an out-of-range key: what stands behind the key
+};
+
+// `in`: the call's live batches; `index`: each one's number in the caller's
+// list (a grouped call's messages name it), or null.  The device is selected
+// and the server stopped; a host call's keys are checked before anything is
+// queued and its batches then staged under `hold`, the caller's; a sparse
+// shard's keys become slot ids (sparse_ids).  `v`: what the kernels read.
+int pool_front(pskv_shard* s, const std::vector<pskv_pool_batch>& in, const std::vector<uint64_t>* index, int flags,
+               const PoolFront& f, HstageHold& hold, std::vector<pskv_pool_batch>* v) {
+  int rc = use_device(s);
+  if (rc || (rc = srv_stop(s))) return rc;
+  const bool host = !(flags & PSKV_DEVICE);
+  for (size_t i = 0; i < in.size() && host && !s->sparse; ++i) {  // (a sparse shard owns every key)
+    std::vector<pskv_batch> keys;
+    push_pieces(keys, pskv_batch{in[i].keys, nullptr, in[i].n}, 0);
+    if (const uint32_t* k = first_key_outside(keys, s->key_begin, s->range))
+      return refuse_key(f.what + (index ? ": batch " + std::to_string((*index)[i]) : std::string()), "key", *k, f.why);
+  }
+  if (!host) *v = in;
+  if (host && (rc = stage_pool_batches(s, in, f.with_rows, hold, v))) return rc;
+  if (!s->sparse) return PSKV_OK;
+  std::vector<pskv_batch> k;
+  for (const auto& b : *v) k.push_back(pskv_batch{b.keys, nullptr, b.n});
+  if ((rc = sparse_ids(s, k, f.writing, /*in_place=*/host))) return rc;
+  for (size_t i = 0; i < k.size(); ++i) (*v)[i].keys = k[i].keys;
+  return PSKV_OK;
+}
+
 // ------------------------------------------------------------ pooled pulls
 // pskv_get_pooled (pskv.h "Pooled pulls"), at any width, 1
 // included.  One or two launches, timed as one operation (kTimePooled):
@@ -1898,22 +1952,15 @@ int stage_pool_batches(pskv_shard* s, const std::vector<pskv_pool_batch>& v, boo
 //   k_row_pooled          every bag: its sum, or the sum of its partial rows
 // The offsets stay where the caller has them, so a device call's launches do
 // not depend on them; the kernels clamp every bag (pool_clamp).
-struct PoolCall {
-  const uint32_t* keys;
-  uint64_t n;
-  const void* weights;  // or null
-  const uint64_t* offsets;
-  uint64_t nbags;
-  void* out;
-};
-
-int pooled_device(pskv_shard* s, const PoolCall& c) {
-  PoolArgs a{c.keys, c.weights, c.offsets, c.n, c.nbags, c.out, nullptr};
+// `c`: the call as the kernels read it, bag_grads the room of its result rows.
+int pooled_device(pskv_shard* s, const pskv_pool_batch& c) {
+  void* out = const_cast<void*>(c.bag_grads);
+  PoolArgs a{c.keys, c.weights, c.offsets, c.n, c.nbags, out, nullptr};
   if (c.n > kPoolChunk) {
     if (int rc = ensure_scratch(s, &s->pool_part, &s->pool_part_bytes, pool_slots(c.n) * row_bytes(s))) return rc;
     a.part = s->pool_part;
   }
-  const bool unit16 = row_bytes(s) % 16 == 0 && aligned16(s->dense) && aligned16(c.out) && aligned16(a.part);
+  const bool unit16 = row_bytes(s) % 16 == 0 && aligned16(s->dense) && aligned16(out) && aligned16(a.part);
   const RowShape rs = row_shape(s->width, s->vb, unit16);
   LaunchTimer t(s, kTimePooled, c.n);
   PSKV_HIP(launch_row_pooled_chunks(s->dtype, a, s->read_view(s->dense), s->ovf, rs, s->stream));
@@ -1922,46 +1969,24 @@ int pooled_device(pskv_shard* s, const PoolCall& c) {
   return PSKV_OK;
 }
 
-// The arguments hold (pskv_get_pooled checked them, a host call's offsets included).
-int pooled_impl(pskv_shard* s, const PoolCall& call, int flags) {
+// The arguments hold (pskv_get_pooled checked them, a host call's offsets
+// included).  A call of bags without a key still writes its rows of zeros.
+int pooled_impl(pskv_shard* s, const pskv_pool_batch& call, int flags) {
   ++s->n_get;
   if (call.nbags == 0) return PSKV_OK;
-  // rows_front's checks on the keys; `out` stands in for the values, which the
-  // checks only want non-null
-  RowCall c;
-  const std::vector<pskv_batch> in{pskv_batch{call.keys, call.out, call.n}};
-  int rc = rows_front_checks(s, in, flags,
-                             RowFront{"pskv_get_pooled", nullptr, /*stop_server=*/true, "key",
-                                      "a pooled pull reads the dense array only, not the overflow table; out is untouched",
-                                      /*with_values=*/false},
-                             &c);
-  if (rc) return rc;
-  if (c.v.empty()) {  // no key, but bags: rows of zeros
-    if ((rc = use_device(s)) || (rc = srv_stop(s))) return rc;
-  }
-  const pskv_pool_batch one{call.keys, call.weights, call.offsets, call.out, call.n, call.nbags};
-  if (flags & PSKV_DEVICE) {
-    if (!s->sparse) return pooled_device(s, call);
-    std::vector<pskv_pool_batch> ids{one};
-    if ((rc = sparse_pool_ids(s, ids, /*writing=*/false, /*in_place=*/false))) return rc;
-    return pooled_device(s, PoolCall{ids[0].keys, call.n, call.weights, call.offsets, call.nbags, call.out});
-  }
-  // host buffers: through the staging, the pooled rows behind keys, weights and offsets
-  const size_t rb = row_bytes(s);
   HstageHold hold(s);
-  std::vector<pskv_pool_batch> dv;
-  if ((rc = stage_pool_batches(s, {one}, /*with_rows=*/false, hold, &dv))) return rc;
-  if (s->sparse && (rc = sparse_pool_ids(s, dv, /*writing=*/false, /*in_place=*/true))) return rc;
-  char* d = static_cast<char*>(const_cast<void*>(dv[0].bag_grads));  // the rows' room in dstage
-  char* h = static_cast<char*>(s->hstage) + (d - static_cast<char*>(s->dstage));
-  if ((rc = pooled_device(s, PoolCall{dv[0].keys, call.n, dv[0].weights, dv[0].offsets, call.nbags, d}))) return rc;
-  PSKV_HIP(hipMemcpyAsync(h, d, call.nbags * rb, hipMemcpyDeviceToHost, s->stream));
-  if ((rc = wait_stream(s, s->stream, "shard stream (pooled pull to host)"))) return rc;
-  hold.dismiss();
+  std::vector<pskv_pool_batch> v;
+  int rc = pool_front(s, {call}, nullptr, flags,
+                      PoolFront{"pskv_get_pooled", /*writing=*/false, /*with_rows=*/false,
+                                "a pooled pull reads the dense array only, not the overflow table; out is untouched"},
+                      hold, &v);
+  if (rc || (rc = pooled_device(s, v[0])) || (flags & PSKV_DEVICE)) return rc;
+  // host buffers: the pooled rows lie behind keys, weights and offsets in the staging
+  const size_t at = static_cast<const char*>(v[0].bag_grads) - static_cast<char*>(s->dstage);
   std::vector<Piece> back;
-  add_pieces(back, h, static_cast<char*>(call.out), call.nbags * rb, -1);
-  run_copies(s, back, 0, back.size());
-  return PSKV_OK;
+  add_pieces(back, static_cast<char*>(s->hstage) + at, static_cast<char*>(const_cast<void*>(call.bag_grads)),
+             call.nbags * row_bytes(s), -1);
+  return rows_to_host(s, hold, at, call.nbags * row_bytes(s), "shard stream (pooled pull to host)", back);
 }
 
 // -------------------------------------------------------- optimizer steps
@@ -1977,19 +2002,8 @@ int pooled_impl(pskv_shard* s, const PoolCall& call, int flags) {
 // Momentum and Adam add a second state array, the step
 // counter opt_step (one per call: Adam's bias corrections are computed from it
 // here, in double) and pskv_put_state, the row assign Add aimed at a state array.
+// (The state slots of a kind: opt_slots, pskv_plan.h; the arrays: pskv_shard::row_array.)
 size_t opt_array_bytes(const pskv_shard* s) { return s->rows_held() * row_bytes(s); }
-
-// A sparse shard's limits (pskv.h): slot + 1 fits an index entry's 31 bits and
-// 0xFFFFFFFF stays free as the id the row kernels drop; the index has at least
-// two entries per slot.
-constexpr uint64_t kSparseMaxCapacity = (1ull << 31) - 2;
-uint64_t sparse_table_slots(uint64_t capacity) { return std::max<uint64_t>(16, next_pow2(2 * capacity)); }
-
-// State slots per kind (pskv_optimizer_kind).
-int opt_slots(int kind) {
-  return (kind == PSKV_OPT_ADAM || kind == PSKV_OPT_FTRL) ? 2
-         : (kind == PSKV_OPT_ADAGRAD || kind == PSKV_OPT_MOMENTUM) ? 1 : 0;
-}
 
 // The hyper-parameters of step `step` as a launch takes them, in double; a
 // field the kind does not use is 0.
@@ -2017,20 +2031,30 @@ OptArgs<double> opt_args(const pskv_optimizer_cfg& c, uint64_t step) {
   return o;
 }
 
-// The state back to its start values (Adagrad's h and FTRL's n: init_accum;
-// every other slot: 0), the gradient scratch to zero (stream-ordered), the step count to 0.
+// `start` over rows [first_row, first_row + rows), the last rows of a
+// row-shaped array, and zero over the zero row a sparse shard keeps behind
+// them (stream-ordered; zeros are one memset, another value is k_fill).
+int fill_rows(pskv_shard* s, void* array, uint64_t first_row, uint64_t rows, double start) {
+  const size_t rb = row_bytes(s);
+  char* at = static_cast<char*>(array) + first_row * rb;
+  const uint64_t zero_rows = s->sparse ? 1 : 0;
+  if (start == 0.0 && !std::signbit(start)) {
+    PSKV_HIP(hipMemsetAsync(at, 0, (rows + zero_rows) * rb, s->stream));
+    return PSKV_OK;
+  }
+  PSKV_HIP(launch_fill(s->dtype, at, rows * (uint64_t)s->width, start, s->stream));
+  if (zero_rows) PSKV_HIP(hipMemsetAsync(at + rows * rb, 0, rb, s->stream));
+  return PSKV_OK;
+}
+
+// The state back to its start values (row_array: Adagrad's h and FTRL's n
+// init_accum, every other slot 0), the gradient scratch to zero
+// (stream-ordered), the step count to 0.
 int opt_reset_state(pskv_shard* s) {
   s->opt_step = 0;
-  if (s->opt_gsum) PSKV_HIP(hipMemsetAsync(s->opt_gsum, 0, opt_array_bytes(s), s->stream));
-  for (int i = 0; i < opt_slots(s->opt.kind); ++i) {
-    if (s->opt.kind == PSKV_OPT_ADAGRAD || (s->opt.kind == PSKV_OPT_FTRL && i == 1)) {
-      PSKV_HIP(launch_fill(s->dtype, s->opt_slot[i], s->range * (uint64_t)s->width, s->opt.init_accum, s->stream));
-      if (s->sparse)  // the zero row an absent key reads
-        PSKV_HIP(hipMemsetAsync(static_cast<char*>(s->opt_slot[i]) + s->range * row_bytes(s), 0, row_bytes(s),
-                                s->stream));
-    } else
-      PSKV_HIP(hipMemsetAsync(s->opt_slot[i], 0, opt_array_bytes(s), s->stream));
-  }
+  for (int a : {3, 1, 2})  // the gradient scratch, then the state slots
+    if (const auto ra = s->row_array(a); ra.used)
+      if (int rc = fill_rows(s, *ra.p, 0, s->range, ra.start)) return rc;
   return PSKV_OK;
 }
 
@@ -2043,7 +2067,17 @@ struct DevBuf {  // a device allocation that is freed unless it was swapped into
   ~DevBuf() {
     if (p) (void)hipFree(p);
   }
-  bool alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1) == hipSuccess; }
+  bool alloc(size_t bytes) {
+    if (hipMalloc(&p, bytes ? bytes : 1) != hipSuccess) p = nullptr;
+    return p != nullptr;
+  }
+  // The allocation takes the place of the shard's `field`; what was there goes with this DevBuf.
+  template <typename T>
+  void swap_with(T*& field) {
+    void* old = field;
+    field = static_cast<T*>(p);
+    p = old;
+  }
 };
 
 // dead: null (growth: every slot keeps its number and its rows move by plain
@@ -2053,18 +2087,14 @@ struct DevBuf {  // a device allocation that is freed unless it was swapped into
 // touched, so PSKV_ENOMEM leaves the shard as it was.  The launches are not
 // timed operations.
 int sparse_rebuild(pskv_shard* s, uint64_t new_capacity, const uint8_t* dead) {
-  uint32_t cnt = 0, err = 0;
-  if (int rc = read_overflow_stat(s, &cnt, &err)) return rc;
-  const uint32_t count = (uint32_t)std::min<uint64_t>(cnt, s->range);
+  uint64_t count = 0;
+  if (int rc = sparse_count(s, &count)) return rc;
   const size_t rb = row_bytes(s);
   const uint64_t table_slots = sparse_table_slots(new_capacity);
-  const int nslots = opt_slots(s->opt.kind);
-  // the row-shaped arrays: the parameters, then the state slots the kind has
-  void** old_rows[3] = {&s->dense, &s->opt_slot[0], &s->opt_slot[1]};
-  DevBuf rows[3], gsum, owner, slot_keys, table, survivors;
+  DevBuf rows[pskv_shard::kRowArrays], owner, slot_keys, table, survivors;
   bool ok = true;
-  for (int a = 0; a < 1 + nslots; ++a) ok = ok && rows[a].alloc((new_capacity + 1) * rb);
-  if (s->opt_gsum) ok = ok && gsum.alloc((new_capacity + 1) * rb);
+  for (int a = 0; a < pskv_shard::kRowArrays; ++a)
+    if (s->row_array(a).used) ok = ok && rows[a].alloc((new_capacity + 1) * rb);
   if (s->owner) ok = ok && owner.alloc(new_capacity * sizeof(unsigned long long));
   ok = ok && slot_keys.alloc(new_capacity * sizeof(uint32_t)) && table.alloc(table_slots * sizeof(unsigned long long));
   if (dead) ok = ok && survivors.alloc((size_t)count * sizeof(uint32_t));
@@ -2078,53 +2108,39 @@ int sparse_rebuild(pskv_shard* s, uint64_t new_capacity, const uint8_t* dead) {
   if (dead) PSKV_HIP(hipMemsetAsync(s->ovf.c->stat, 0, sizeof(uint32_t), s->stream));  // the new slot counter
   const SparseIndex nx{static_cast<unsigned long long*>(table.p), static_cast<uint32_t*>(slot_keys.p), s->ovf.c->stat,
                        table_slots - 1, (uint32_t)new_capacity};
-  PSKV_HIP(launch_index_rebuild(s->sp_slot_keys, count, dead, nx, static_cast<uint32_t*>(survivors.p), s->stream));
-  uint32_t kept = count;
+  PSKV_HIP(launch_index_rebuild(s->sp_slot_keys, (uint32_t)count, dead, nx, static_cast<uint32_t*>(survivors.p),
+                                s->stream));
+  uint64_t kept = count;
   if (dead) {  // how many survived: the gather below is sized by it
-    if (int rc = read_overflow_stat(s, &kept, &err)) return rc;
+    if (int rc = sparse_count(s, &kept)) return rc;
     kept = std::min(kept, count);
   }
-  // the rows of the survivors, then the start values behind them (opt_reset_state's)
-  for (int a = 0; a < 1 + nslots; ++a) {
+  // the rows of the survivors (the gradient scratch carries none: it is zero
+  // between calls), then each array's start value behind them
+  for (int a = 0; a < pskv_shard::kRowArrays; ++a) {
+    const pskv_shard::RowArray ra = s->row_array(a);
+    if (!ra.used) continue;
     char* fresh = static_cast<char*>(rows[a].p);
-    if (kept && !dead)
-      PSKV_HIP(hipMemcpyAsync(fresh, *old_rows[a], (size_t)kept * rb, hipMemcpyDeviceToDevice, s->stream));
-    if (kept && dead) {
-      const std::vector<pskv_batch> mv{pskv_batch{static_cast<const uint32_t*>(survivors.p), fresh, kept}};
+    const uint64_t carried = ra.p == &s->opt_gsum ? 0 : kept;
+    if (carried && !dead)
+      PSKV_HIP(hipMemcpyAsync(fresh, *ra.p, (size_t)carried * rb, hipMemcpyDeviceToDevice, s->stream));
+    if (carried && dead) {
+      const std::vector<pskv_batch> mv{pskv_batch{static_cast<const uint32_t*>(survivors.p), fresh, carried}};
       const LaunchGroup g = make_group(mv, 0, 1, kGeneralChunk);
-      const DenseView from{*old_rows[a], 0, s->rows_held(), 0};
+      const DenseView from{*ra.p, 0, s->rows_held(), 0};
       const RowShape rs = row_shape(s->width, s->vb, rows_unit16(s, {from.param}, mv));
       PSKV_HIP(launch_row_gather(s->vb, s->tune_nt, g.ga, g.nwg, from, rs, s->stream));
     }
-    const bool accum = a > 0 && (s->opt.kind == PSKV_OPT_ADAGRAD || (s->opt.kind == PSKV_OPT_FTRL && a == 2));
-    const uint64_t tail = new_capacity - kept;  // rows [kept, new_capacity), then the zero row
-    if (accum && tail) {
-      PSKV_HIP(launch_fill(s->dtype, fresh + (size_t)kept * rb, tail * (uint64_t)s->width, s->opt.init_accum,
-                           s->stream));
-      PSKV_HIP(hipMemsetAsync(fresh + new_capacity * rb, 0, rb, s->stream));
-    } else {
-      PSKV_HIP(hipMemsetAsync(fresh + (size_t)kept * rb, 0, (tail + 1) * rb, s->stream));
-    }
+    if (int rc = fill_rows(s, fresh, carried, new_capacity - carried, ra.start)) return rc;
   }
-  if (gsum.p) PSKV_HIP(hipMemsetAsync(gsum.p, 0, (new_capacity + 1) * rb, s->stream));
   if (owner.p) PSKV_HIP(hipMemsetAsync(owner.p, 0, new_capacity * sizeof(unsigned long long), s->stream));
   if (int rc = wait_stream(s, s->stream, "shard stream (sparse rebuild)")) return rc;
   // nothing is queued: the new arrays take over and the old ones go with the DevBufs
-  for (int a = 0; a < 1 + nslots; ++a) std::swap(*old_rows[a], rows[a].p);
-  if (gsum.p) std::swap(s->opt_gsum, gsum.p);
-  if (owner.p) {
-    void* o = s->owner;
-    s->owner = static_cast<unsigned long long*>(owner.p);
-    owner.p = o;
-  }
-  {
-    void* k = s->sp_slot_keys;
-    s->sp_slot_keys = static_cast<uint32_t*>(slot_keys.p);
-    slot_keys.p = k;
-    void* t = s->sp_table;
-    s->sp_table = static_cast<unsigned long long*>(table.p);
-    table.p = t;
-  }
+  for (int a = 0; a < pskv_shard::kRowArrays; ++a)
+    if (rows[a].p) rows[a].swap_with(*s->row_array(a).p);
+  if (owner.p) owner.swap_with(s->owner);
+  slot_keys.swap_with(s->sp_slot_keys);
+  table.swap_with(s->sp_table);
   s->sp_table_slots = table_slots;
   s->range = new_capacity;
   s->sp_bound = kept;
@@ -2134,19 +2150,16 @@ int sparse_rebuild(pskv_shard* s, uint64_t new_capacity, const uint8_t* dead) {
 }
 
 // The growth rule of a writing call of n key positions (pskv.h "Sparse
-// shards"): grow iff count + n > capacity, to min(max, max(2 * capacity,
-// count + n)).  count is read -- one bounded stream wait -- only when the
-// host-side bound cannot rule the growth out; while bound + n <= capacity,
-// count + n <= capacity too, so both make the same decision.
+// shards"; sparse_grown_capacity, pskv_plan.h).  The count is read -- one
+// bounded stream wait -- only when the host-side bound cannot rule the growth
+// out (sparse_may_grow): both then make the same decision.
 int sparse_autogrow(pskv_shard* s, uint64_t n) {
-  if (s->range < s->sp_max_capacity && s->sp_bound + n > s->range) {
-    uint32_t cnt = 0, err = 0;
-    if (int rc = read_overflow_stat(s, &cnt, &err)) return rc;  // (sp_bound = count)
-    const uint64_t count = s->sp_bound;
-    if (count + n > s->range) {
-      const uint64_t want = std::min(s->sp_max_capacity, std::max(2 * s->range, count + n));
+  if (sparse_may_grow(s->sp_bound, n, s->range, s->sp_max_capacity)) {
+    uint64_t count = 0;
+    if (int rc = sparse_count(s, &count)) return rc;
+    const uint64_t want = sparse_grown_capacity(s->range, count, n, s->sp_max_capacity);
+    if (want != s->range)
       if (int rc = sparse_rebuild(s, want, nullptr)) return rc;
-    }
   }
   s->sp_bound = std::min(s->sp_bound + n, s->range);  // (count never exceeds the capacity)
   return PSKV_OK;
@@ -2255,29 +2268,19 @@ const char* pooled_step_refusal(const pskv_shard* s) {
   return nullptr;
 }
 
+// A pooled push's front: it inserts, and a host call stages its bag rows.
+PoolFront pooled_push_front(const char* what) {
+  return PoolFront{what, /*writing=*/true, /*with_rows=*/true, "an optimizer step takes no out-of-range keys"};
+}
+
 // The arguments hold (pskv_apply_pooled checked them, a host call's offsets included).
 int apply_pooled_impl(pskv_shard* s, const pskv_pool_batch& call, int flags) {
   if (const char* why = pooled_step_refusal(s)) return fail(PSKV_EINVAL, std::string("pskv_apply_pooled") + why);
   if (call.n == 0 || call.nbags == 0) return PSKV_OK;  // no key, or no bag to take a row from: no step
-  // rows_front's checks on the keys (apply_impl's: the request server ends, a
-  // host call refuses an out-of-range key); the bag rows stand in for the
-  // values, which the checks only want non-null
-  RowCall c;
-  int rc = rows_front_checks(s, pool_mark_batches({call}), flags,
-                             RowFront{"pskv_apply_pooled", nullptr, /*stop_server=*/true, "key",
-                                      "an optimizer step takes no out-of-range keys", /*with_values=*/false},
-                             &c);
-  if (rc) return rc;
-  if (flags & PSKV_DEVICE) {
-    std::vector<pskv_pool_batch> one{call};
-    if (s->sparse && (rc = sparse_pool_ids(s, one, /*writing=*/true, /*in_place=*/false))) return rc;
-    return apply_pooled_device(s, one[0]);
-  }
-  HstageHold hold(s);  // the call returns before its DMA: the hold stays armed
-  std::vector<pskv_pool_batch> dv;
-  if ((rc = stage_pool_batches(s, {call}, /*with_rows=*/true, hold, &dv))) return rc;
-  if (s->sparse && (rc = sparse_pool_ids(s, dv, /*writing=*/true, /*in_place=*/true))) return rc;
-  return apply_pooled_device(s, dv[0]);
+  HstageHold hold(s);  // a host call returns before its DMA: the hold stays armed
+  std::vector<pskv_pool_batch> v;
+  if (int rc = pool_front(s, {call}, nullptr, flags, pooled_push_front("pskv_apply_pooled"), hold, &v)) return rc;
+  return apply_pooled_device(s, v[0]);
 }
 
 // The arguments hold (pskv_apply_pooled_grouped checked every batch, a host
@@ -2288,25 +2291,10 @@ int apply_pooled_grouped_impl(pskv_shard* s, const pskv_pool_batch* batches, uin
   std::vector<uint64_t> index;
   const std::vector<pskv_pool_batch> live = pool_live_batches(batches, nb, &index);
   if (live.empty()) return PSKV_OK;  // no batch with a key and a bag: no step
-  int rc = use_device(s);
-  if (rc || (rc = srv_stop(s))) return rc;
-  if (flags & PSKV_DEVICE) {
-    std::vector<pskv_pool_batch> ids = live;
-    if (s->sparse && (rc = sparse_pool_ids(s, ids, /*writing=*/true, /*in_place=*/false))) return rc;
-    return apply_pooled_grouped_device(s, ids);
-  }
-  for (size_t i = 0; i < live.size() && !s->sparse; ++i) {
-    if (const uint32_t* k = first_key_outside(pool_mark_batches({live[i]}), s->key_begin, s->range))
-      return fail(PSKV_EINVAL, "pskv_apply_pooled_grouped: batch " + std::to_string(index[i]) + ": key " +
-                                   std::to_string(*k) +
-                                   " is outside [key_begin, key_end); an optimizer step takes no out-of-range keys "
-                                   "(nothing was applied)");
-  }
-  HstageHold hold(s);  // the call returns before its DMA: the hold stays armed
-  std::vector<pskv_pool_batch> dv;
-  if ((rc = stage_pool_batches(s, live, /*with_rows=*/true, hold, &dv))) return rc;
-  if (s->sparse && (rc = sparse_pool_ids(s, dv, /*writing=*/true, /*in_place=*/true))) return rc;
-  return apply_pooled_grouped_device(s, dv);
+  HstageHold hold(s);  // a host call returns before its DMA: the hold stays armed
+  std::vector<pskv_pool_batch> v;
+  if (int rc = pool_front(s, live, &index, flags, pooled_push_front("pskv_apply_pooled_grouped"), hold, &v)) return rc;
+  return apply_pooled_grouped_device(s, v);
 }
 
 // What is wrong with a configuration, or null (checked before any handle;
@@ -2803,52 +2791,30 @@ int set_optimizer_impl(pskv_shard* s, pskv_optimizer_cfg cfg, OptAbi abi, const 
   // given up, so a failure leaves the shard as it was
   const size_t bytes = opt_array_bytes(s);
   const int slots = opt_slots(cfg.kind);
-  void* gsum = s->opt_gsum;
-  void* state[2] = {nullptr, nullptr};
-  auto give_back = [&]() {
-    if (gsum && gsum != s->opt_gsum) (void)hipFree(gsum);
-    for (void* p : state)
-      if (p) (void)hipFree(p);
-  };
+  // (gsum, state: the new arrays until they are swapped in, then the ones that go)
+  DevBuf gsum, state[2];
   if (cfg.kind != PSKV_OPT_NONE) {
-    if (!gsum && hipMalloc(&gsum, bytes) != hipSuccess) {
-      gsum = nullptr;
-      return fail(PSKV_ENOMEM, who + ": gradient scratch allocation failed");
-    }
+    if (!s->opt_gsum && !gsum.alloc(bytes)) return fail(PSKV_ENOMEM, who + ": gradient scratch allocation failed");
     for (int i = 0; i < slots; ++i)
-      if (hipMalloc(&state[i], bytes) != hipSuccess) {
-        state[i] = nullptr;
-        give_back();
-        return fail(PSKV_ENOMEM, who + ": state allocation failed");
-      }
-    if ((rc = ensure_owner(s))) {
-      give_back();
-      return rc;
-    }
+      if (!state[i].alloc(bytes)) return fail(PSKV_ENOMEM, who + ": state allocation failed");
+    if ((rc = ensure_owner(s))) return rc;
   }
   // queued steps may still use the arrays that go
-  if (s->opt_slot[0] || (cfg.kind == PSKV_OPT_NONE && s->opt_gsum)) {
-    if ((rc = srv_stop(s)) || (rc = wait_stream(s, s->stream, "shard stream (optimizer change)"))) {
-      give_back();
-      return rc;
-    }
-    for (void* p : s->opt_slot)
-      if (p) (void)hipFree(p);
-    if (cfg.kind == PSKV_OPT_NONE) {
-      (void)hipFree(s->opt_gsum);
-      gsum = nullptr;
-    }
-  }
-  s->opt_gsum = gsum;
-  for (int i = 0; i < 2; ++i) s->opt_slot[i] = state[i];
+  if (s->opt_slot[0] || (cfg.kind == PSKV_OPT_NONE && s->opt_gsum))
+    if ((rc = srv_stop(s)) || (rc = wait_stream(s, s->stream, "shard stream (optimizer change)"))) return rc;
+  if (gsum.p || cfg.kind == PSKV_OPT_NONE) gsum.swap_with(s->opt_gsum);  // (else the scratch it has stays)
+  for (int i = 0; i < 2; ++i) state[i].swap_with(s->opt_slot[i]);
   s->opt = cfg;
   return opt_reset_state(s);
 }
 
 uint64_t opt_state_bytes(const pskv_shard* s) {
   if (s->opt.kind == PSKV_OPT_NONE) return 0;
-  // gradient scratch + one array per state slot + the stamp array (8 bytes per key)
-  return (uint64_t)(1 + opt_slots(s->opt.kind)) * opt_array_bytes(s) + s->range * sizeof(unsigned long long);
+  // the row arrays behind the parameters (gradient scratch, state slots) + the stamp array (8 bytes per key)
+  uint64_t bytes = s->range * sizeof(unsigned long long);
+  for (int a = 1; a < pskv_shard::kRowArrays; ++a)
+    if (s->row_array(a).used) bytes += opt_array_bytes(s);
+  return bytes;
 }
 
 // The state array of `slot`, or null with the error set.
@@ -2926,8 +2892,7 @@ static int create_impl(int device, uint32_t key_begin, uint64_t key_end, int dty
     return bail(fail(PSKV_EHIP, "hipEventCreate failed"));
   if (hipMalloc(&s->dense, s->rows_held() * (size_t)width * (size_t)vb) != hipSuccess)
     return bail(fail(PSKV_ENOMEM, "dense parameter allocation failed"));
-  if (hipMemsetAsync(s->dense, 0, s->rows_held() * (size_t)width * (size_t)vb, s->stream) != hipSuccess)
-    return bail(fail(PSKV_EHIP, "hipMemsetAsync failed"));
+  if (fill_rows(s, s->dense, 0, s->range, 0.0) != PSKV_OK) return bail(fail(PSKV_EHIP, "hipMemsetAsync failed"));
   // flag[0]: the sorted path's verification tag
   // the verification tag (16 bytes), then K1r's replay table (add_get's folded replay)
   if (hipMalloc(&s->flag, 64 + kK1rTableWords * sizeof(uint32_t)) != hipSuccess)
@@ -2999,10 +2964,10 @@ int pskv_sparse_info_get(pskv_shard* s, pskv_sparse_info* out) {
   if (!s->sparse) return fail(PSKV_EINVAL, "pskv_sparse_info_get: not a sparse shard (pskv_shard_create_sparse)");
   int rc = use_device(s);
   if (rc) return rc;
-  uint32_t cnt = 0, err = 0;
-  if ((rc = read_overflow_stat(s, &cnt, &err))) return rc;
+  uint64_t count = 0;
+  if ((rc = sparse_count(s, &count))) return rc;
   out->capacity = s->range;
-  out->count = std::min<uint64_t>(cnt, s->range);
+  out->count = count;
   out->table_slots = s->sp_table_slots;
   out->index_bytes = s->sp_table_slots * sizeof(unsigned long long) + s->range * sizeof(uint32_t);
   return PSKV_OK;
@@ -3016,9 +2981,8 @@ int pskv_sparse_keys(pskv_shard* s, uint32_t* out, uint64_t cap, uint64_t* n, in
   if (!s->sparse) return fail(PSKV_EINVAL, "pskv_sparse_keys: not a sparse shard (pskv_shard_create_sparse)");
   int rc = use_device(s);
   if (rc) return rc;
-  uint32_t cnt = 0, err = 0;
-  if ((rc = read_overflow_stat(s, &cnt, &err))) return rc;  // (waits for the stream)
-  const uint64_t held = std::min<uint64_t>(cnt, s->range);
+  uint64_t held = 0;
+  if ((rc = sparse_count(s, &held))) return rc;  // (waits for the stream)
   *n = held;
   const uint64_t take = std::min(held, cap);
   if (take == 0) return PSKV_OK;
@@ -3030,10 +2994,7 @@ int pskv_sparse_keys(pskv_shard* s, uint32_t* out, uint64_t cap, uint64_t* n, in
 // What is wrong with `capacity` as a sparse shard's new capacity or growth limit, or null.
 static const char* sparse_capacity_refusal(const pskv_shard* s, uint64_t capacity) {
   if (!s->sparse) return "not a sparse shard (pskv_shard_create_sparse)";
-  if (capacity < s->range) return "capacity is below the shard's current capacity (a sparse shard does not shrink)";
-  if ((capacity + 1) * (uint64_t)s->width * (uint64_t)s->vb > (1ull << 46))
-    return "(capacity + 1) * width * value bytes exceeds 2^46 bytes";
-  return nullptr;
+  return sparse_capacity_error(s->range, capacity, (uint64_t)s->width * (uint64_t)s->vb);
 }
 
 int pskv_sparse_reserve(pskv_shard* s, uint64_t capacity) {
@@ -3102,16 +3063,20 @@ int pskv_sparse_erase(pskv_shard* s, const uint32_t* keys, uint64_t n, int flags
   return sparse_rebuild(s, s->range, static_cast<const uint8_t*>(dead.p));
 }
 
-int pskv_index_time(pskv_shard* s, uint64_t* launches, double* total_ms, uint64_t* elements) {
-  if (!s) return fail(PSKV_EINVAL, "pskv_index_time: null shard");
+// The counters of one timed operation (kTimeApply, kTimePooled, kTimeIndex).
+static int timed_op_read(pskv_shard* s, const char* who, int slot, uint64_t* launches, double* total_ms,
+                         uint64_t* elements) {
+  if (!s) return fail(PSKV_EINVAL, std::string(who) + ": null shard");
   int rc = use_device(s);
-  if (rc) return rc;
-  rc = drain_timing(s);
-  if (rc) return rc;
-  if (launches) *launches = s->t_launches[kTimeIndex];
-  if (total_ms) *total_ms = s->t_ms[kTimeIndex];
-  if (elements) *elements = s->t_elems[kTimeIndex];
+  if (rc || (rc = drain_timing(s))) return rc;
+  if (launches) *launches = s->t_launches[slot];
+  if (total_ms) *total_ms = s->t_ms[slot];
+  if (elements) *elements = s->t_elems[slot];
   return PSKV_OK;
+}
+
+int pskv_index_time(pskv_shard* s, uint64_t* launches, double* total_ms, uint64_t* elements) {
+  return timed_op_read(s, "pskv_index_time", kTimeIndex, launches, total_ms, elements);
 }
 
 int pskv_shard_create_ex(int device, uint32_t key_begin, uint64_t key_end, int dtype, int mode,
@@ -3171,11 +3136,9 @@ int pskv_shard_destroy(pskv_shard* s) {
   }
   for (auto e : s->event_pool) (void)hipEventDestroy(e);
   if (s->sync_ev) (void)hipEventDestroy(s->sync_ev);
-  if (s->dense) (void)hipFree(s->dense);
+  for (int a = 0; a < pskv_shard::kRowArrays; ++a)
+    if (void* p = *s->row_array(a).p) (void)hipFree(p);
   if (s->owner) (void)hipFree(s->owner);
-  if (s->opt_gsum) (void)hipFree(s->opt_gsum);
-  for (void* p : s->opt_slot)
-    if (p) (void)hipFree(p);
   if (s->flag) (void)hipFree(s->flag);
   for (const auto& t : s->tables) {  // (the service no longer touches the list)
     (void)hipFree(t.keys);
@@ -3259,7 +3222,7 @@ int pskv_get_pooled(pskv_shard* s, const uint32_t* keys, uint64_t n, const void*
                                    std::to_string(n) + ", nbags = " + std::to_string(nbags) + ")");
   }
   if (!s) return fail(PSKV_EINVAL, "pskv_get_pooled: null shard");
-  return pooled_impl(s, PoolCall{keys, n, weights, offsets, nbags, out}, flags);
+  return pooled_impl(s, pskv_pool_batch{keys, weights, offsets, out, n, nbags}, flags);
 }
 
 int pskv_shard_set_optimizer(pskv_shard* s, const pskv_optimizer* cfg) {
@@ -3423,27 +3386,11 @@ int pskv_put_state(pskv_shard* s, int slot, const uint32_t* keys, const void* va
 }
 
 int pskv_apply_time(pskv_shard* s, uint64_t* launches, double* total_ms, uint64_t* elements) {
-  if (!s) return fail(PSKV_EINVAL, "pskv_apply_time: null shard");
-  int rc = use_device(s);
-  if (rc) return rc;
-  rc = drain_timing(s);
-  if (rc) return rc;
-  if (launches) *launches = s->t_launches[kTimeApply];
-  if (total_ms) *total_ms = s->t_ms[kTimeApply];
-  if (elements) *elements = s->t_elems[kTimeApply];
-  return PSKV_OK;
+  return timed_op_read(s, "pskv_apply_time", kTimeApply, launches, total_ms, elements);
 }
 
 int pskv_pooled_time(pskv_shard* s, uint64_t* launches, double* total_ms, uint64_t* elements) {
-  if (!s) return fail(PSKV_EINVAL, "pskv_pooled_time: null shard");
-  int rc = use_device(s);
-  if (rc) return rc;
-  rc = drain_timing(s);
-  if (rc) return rc;
-  if (launches) *launches = s->t_launches[kTimePooled];
-  if (total_ms) *total_ms = s->t_ms[kTimePooled];
-  if (elements) *elements = s->t_elems[kTimePooled];
-  return PSKV_OK;
+  return timed_op_read(s, "pskv_pooled_time", kTimePooled, launches, total_ms, elements);
 }
 
 int pskv_sync(pskv_shard* s) {
@@ -3482,7 +3429,7 @@ int pskv_clear(pskv_shard* s) {
   uint32_t cnt = 0, err = 0;
   rc = read_overflow_stat(s, &cnt, &err);  // (adopts the current table; stops the server)
   if (rc) return rc;
-  PSKV_HIP(hipMemsetAsync(s->dense, 0, s->rows_held() * (size_t)s->width * (size_t)s->vb, s->stream));
+  if ((rc = fill_rows(s, s->dense, 0, s->range, 0.0))) return rc;
   // a sparse shard: an empty index (the slot counter and the full bit go with stat below)
   if (s->sparse) PSKV_HIP(hipMemsetAsync(s->sp_table, 0, s->sp_table_slots * sizeof(unsigned long long), s->stream));
   PSKV_HIP(hipMemsetAsync(s->cur.keys, 0xFF, s->ocap * sizeof(unsigned long long), s->stream));

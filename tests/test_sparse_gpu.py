@@ -542,6 +542,36 @@ def test_flags_options_and_views(cuda):
         st.shard.close()
 
 
+@pytest.mark.parametrize("dtype,w", [(np.float32, 3), (np.float64, 4)], ids=["f32-w3", "f64-w4"])
+def test_a_dense_row_shards_host_grouped_pooled_push_names_the_callers_batch(cuda, dtype, w):
+    """The dense side of the pooled front that sparse shards share: caller batch
+    0 is empty, so the refused key lies in live batch 0 and the message must
+    still say batch 1; nothing is applied and the step is not counted.  A sparse
+    shard takes the same call (it owns every key)."""
+    import pooled_push_group_util as ggu
+
+    ps, hp = ps_mod(), ppu.hyper("sgd")
+    rng = np.random.default_rng(ou.case_seed("front-refusal", np.dtype(dtype).name, w))
+    keys = np.array([1001, 1005, 3007, 1002, 1001], dtype=np.uint32)  # 3007 is outside; 1001 lies in both bags
+    batches = [ggu.empty_batch(w, dtype, nbags=1),
+               (keys, pu.offsets_of([2, 3]), (rng.standard_normal((2, w)) * 3).astype(dtype), None)]
+    with ps.Shard(1000, 1040, dtype, width=w) as sh:
+        ppu.set_optimizer(sh, hp)
+        with pytest.raises(ps.PskvError) as e:
+            sh.apply_pooled_grouped(batches)
+        assert str(e.value) == ("pskv error -1: pskv_apply_pooled_grouped: batch 1: key 3007 is outside [key_begin, "
+                                "key_end); an optimizer step takes no out-of-range keys (nothing was applied)")
+        assert sh.step == 0 and not rows(sh, np.arange(1000, 1040)).any()
+        sh.sync()
+    with ps.Shard.sparse(8, dtype, "assign", width=w) as sh:
+        ppu.set_optimizer(sh, hp)
+        sh.apply_pooled_grouped(batches)
+        assert sh.step == 1 and sorted(sh.keys().tolist()) == [1001, 1002, 1005, 3007]
+        ggu.check_step(np.zeros((4, w), dtype=dtype), [], 0, [(su.Relabel(keys).rank(keys),) + batches[1][1:]],
+                       rows(sh, np.unique(keys)), [], np.dtype(dtype), hp, t=1, msg="sparse grouped push")
+        sh.sync()
+
+
 def test_cpp_sparse_program(cuda):
     """tests/cpp/hip_storage_sparse_test.cpp: HipStorage::Sparse and CreateTable's
     sparse_capacity, two servers under jump hashing."""

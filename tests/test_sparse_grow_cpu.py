@@ -144,6 +144,54 @@ def test_capacity_model_follows_the_rule_along_a_call_sequence():
     assert gu.table_slots(8) == 16 and gu.table_slots(20) == 64 and gu.table_slots(4100) == 16384
 
 
+def _build_and_run(tmp_path, name, extra, args=()):
+    """tests/cpp/sparse_plan_test.cpp (the rules of pskv_plan.h in C++), built with g++ and run."""
+    src = os.path.join(ROOT, "tests", "cpp", "sparse_plan_test.cpp")
+    exe = str(tmp_path / name)
+    r = subprocess.run(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", *extra,
+                        "-I", os.path.join(ROOT, "include"),
+                        "-I", os.path.join(ROOT, "parameter_server_amd", "csrc"), src, "-o", exe],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    r = subprocess.run([exe, *args], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    if not args:
+        assert " 0 failed" in r.stdout
+    return r.stdout
+
+
+def test_sparse_plan(tmp_path):
+    _build_and_run(tmp_path, "sparse_plan_test", [])
+
+
+def test_sparse_plan_under_host_sanitizers(tmp_path):
+    """The same host-only program with AddressSanitizer and UBSan: a stand-alone
+    executable, nothing loaded into Python."""
+    _build_and_run(tmp_path, "sparse_plan_test_san",
+                   ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])
+
+
+def test_sparse_plan_grid_against_the_python_model(tmp_path):
+    """sparse_table_slots and sparse_grown_capacity as the library computes them
+    against table_slots and grown_capacity of sparse_grow_util, the reference:
+    capacity 1..33, count 0..capacity, n 0..70, max in {c, c + 1, 2c - 1, 2c, 4c}."""
+    out = _build_and_run(tmp_path, "sparse_plan_grid", [], ["--grid", "1", "33", "70"])
+    slots, grown = {}, {}
+    for line in out.splitlines():
+        f = line.split()
+        if f[0] == "slots":
+            slots[int(f[1])] = int(f[2])
+        else:
+            assert f[0] == "grow", line
+            grown[tuple(int(x) for x in f[1:5])] = int(f[5])
+    assert slots == {c: gu.table_slots(c) for c in range(1, 34)}
+    want = {(c, count, n, m): gu.grown_capacity(c, count, n, m)
+            for c in range(1, 34) for count in range(c + 1) for n in range(71)
+            for m in (c, c + 1, 2 * c - 1, 2 * c, 4 * c)}
+    assert grown.keys() == want.keys()
+    assert [k for k in want if grown[k] != want[k]] == []
+
+
 def test_fuzz_scenarios_compare_nine_calls_in_ten_bit_for_bit():
     """The model alone: 40 scenarios, what each call is and whether its result
     is order-dependent (duplicated keys in an accumulate Add or a step)."""

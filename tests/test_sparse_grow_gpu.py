@@ -306,6 +306,57 @@ def test_a_grouped_call_grows_before_its_first_insert_not_between_launch_groups(
         tw.close()
 
 
+@pytest.mark.parametrize("grow", [False, True], ids=["fixed", "grows"])
+@pytest.mark.parametrize("dev", [False, True], ids=["host", "device"])
+@pytest.mark.parametrize("dtype,w", [(np.float32, 3), (np.float32, 4), (np.float64, 3), (np.float64, 4)],
+                         ids=["f32-w3", "f32-w4", "f64-w3", "f64-w4"])
+def test_tiny_pooled_calls_at_capacity_8_against_the_reference_models(cuda, dtype, w, dev, grow):
+    """The three pooled calls through their one front, each against its Python
+    model on ranks: a grouped push whose caller batch 0 is empty, a single
+    push and a pull, 2-3 bags over 5-11 keys with a key in two bags, the pull
+    with an absent key.  grows: each push has more key positions than the shard
+    has free slots, so growth (limit 64) fires inside the call."""
+    import pooled_push_group_util as ggu
+
+    ps, hp, dt = ps_mod(), ppu.hyper("sgd"), np.dtype(dtype)
+    rng = np.random.default_rng(ou.case_seed("tiny-pooled", dt.name, w, dev, grow))
+    pool = su.key_pool(rng, 16)
+    rl = su.Relabel(pool)
+    c = cuda if dev else None
+    bag_rows = lambda n: (rng.standard_normal((n, w)) * 3).astype(dtype)  # noqa: E731
+    cm = gu.CapacityModel(8, 64 if grow else 0)
+    with ps.Shard.sparse(8, dtype, "assign", width=w, max_capacity=64 if grow else None) as sh:
+        ppu.set_optimizer(sh, hp)
+        p = np.zeros((rl.m, w), dtype=dtype)
+        # grouped push: the live batch is the caller's batch 1; its first key is also its last
+        k = np.append(pool[:10 if grow else 5], pool[0])
+        live = (k, pu.offsets_of([3, 0, k.size - 3]), bag_rows(3), rng.standard_normal(k.size).astype(dtype))
+        ggu.apply_grouped(sh, [ggu.empty_batch(w, dtype, nbags=1), live], c)
+        cm.write(k)
+        assert info(sh) == (cm.capacity, cm.count, gu.table_slots(cm.capacity)) and sh.growth()["rebuilds"] == cm.rebuilds
+        got = rows(sh, rl.uniq)
+        ggu.check_step(p, [], 0, [(rl.rank(k),) + live[1:]], got, [], dt, hp, t=1, msg="grouped push")
+        p = got
+        # single push: stored and new keys, unweighted
+        k = np.concatenate([pool[3:5], pool[10:14] if grow else pool[5:7], pool[3:4]])
+        off, bg = pu.offsets_of([2, k.size - 2]), bag_rows(2)
+        ppu.apply_pooled(sh, k, off, bg, None, c)
+        cm.write(k)
+        assert info(sh) == (cm.capacity, cm.count, gu.table_slots(cm.capacity)) and sh.growth()["rebuilds"] == cm.rebuilds
+        got = rows(sh, rl.uniq)
+        ppu.check_step(p, [], rl.rank(k).astype(np.int64), None, bg, ppu.bag_index(off), got, [], dt, hp, t=2,
+                       msg="single push")
+        p = got
+        # pull: pool[0] in two bags, pool[15] absent (it reads zeros and is not inserted)
+        k = pool[[0, 1, 15, 0, 2, 3, 4]]
+        off, wts = pu.offsets_of([3, 0, 4]), rng.standard_normal(7).astype(dtype)
+        assert not p[rl.rank(pool[15:16])].any()
+        pu.check(pu.pooled(sh, k, off, wts, c), pu.reference(p, 0, rl.rank(k), off, wts), "pull")
+        assert info(sh)[:2] == (cm.capacity, cm.count) and sh.step == 2
+        assert cm.rebuilds == (2 if grow else 0) and cm.capacity == (32 if grow else 8)
+        sh.sync()
+
+
 @pytest.mark.parametrize("kind", ["adagrad", "adam", "ftrl"])
 @pytest.mark.parametrize("dev", [False, True], ids=["host", "device"])
 def test_a_growing_step_with_duplicated_keys_passes_the_one_step_check(cuda, kind, dev):
