@@ -150,12 +150,35 @@
  *     weight-decay term and is then replaced; to start from given weights,
  *     put the matching z with pskv_put_state;
  *   - non-finite inputs, and a negative n written by pskv_put_state, propagate
- *     by IEEE rules (sqrt of a negative n is a NaN); nothing checks for them;
+ *     by IEEE rules (sqrt of a negative n is a NaN); nothing checks for them
+ *     ("Non-finite, subnormal and overflowing values" below);
  *   - the step counter, pskv_clear (z to 0, n to init_accum, t to 0) and a kind
  *     change follow the rules above; lazy as Adam: a key not in the call keeps
  *     p, z and n bit for bit;
  *   - not provided: lr_power other than -1/2, L2 shrinkage, per-key step
  *     counts.
+ *
+ * Non-finite, subnormal and overflowing values.  No call
+ * checks for them and none treats them specially; one contract holds for every
+ * step kind (SGD, Adagrad, momentum, Nesterov, Adam, FTRL) through pskv_apply,
+ * pskv_apply_grouped, pskv_apply_pooled and pskv_apply_pooled_grouped, for
+ * accumulate Adds on every path and for pooled pulls:
+ *   - values propagate by IEEE 754 rules in T, element by element.  A NaN
+ *     among a key's addends, or both infinities, gives NaN; one infinity gives
+ *     itself; a sum or product that overflows T gives the infinity T
+ *     arithmetic gives (max + max, Adagrad's h + d*d, Adam's v, FTRL's n, a
+ *     weight times a bag row); 0 * inf of a weighted pooled call is NaN.  The
+ *     rule then runs on that value as written above;
+ *   - a non-finite value reaches only its own element of its own key: the other
+ *     columns of the row, every other key and every later call on other keys
+ *     are what they would be without it.  In particular the gradient scratch
+ *     of the step kernels is all-zero bits again after every call, whatever
+ *     the losers' sum was (NaN, an infinity, a subnormal, -0);
+ *   - subnormal addends, sums and products are kept, not flushed to zero, in
+ *     float and double, by the float atomics as by the plain arithmetic; -0.0
+ *     added onto +0 is +0;
+ *   - assign Adds and every Get move bits: NaN payloads, -0.0
+ *     and subnormals come back unchanged.
  *
  * Pooled pulls (pskv_get_pooled): one row per BAG of keys, a bag
  * being one sample's contiguous run of the call's keys (bag b = keys

@@ -230,8 +230,8 @@ def check_step64(p, h, idx, grads, p_got, h_got, dt, kind, lr, wd=0.0, eps=0.0, 
 
 # --------------------------------------------------------------- emulation
 def emulate(p, slots, idx, grads, dt, hp, t=1, rng=None):
-    """The kernel's operation order in numpy arithmetic of type dt (no FMA),
-    momentum and Adam:
+    """The kernel's operation order (opt_step_unit) in numpy arithmetic of type
+    dt (no FMA), every kind of SLOT_NAMES:
     gsum = the losers' gradient rows added one by one into zero (in call order,
     or in a random order with `rng`), the winner = the key's LAST occurrence,
     d = (g_own + gsum) + wd * p, then the rule with every hyper-parameter
@@ -262,7 +262,13 @@ def emulate(p, slots, idx, grads, dt, hp, t=1, rng=None):
     d = (own + gsum[rows]) + wd * pr
     pn = p.copy()
     sn = [np.asarray(s, dtype=dt).copy() for s in slots]
-    if hp["kind"] == "momentum":
+    if hp["kind"] == "sgd":
+        pn[rows] = pr - lr * d
+    elif hp["kind"] == "adagrad":
+        h = sn[0][rows] + d * d
+        sn[0][rows] = h
+        pn[rows] = pr - lr * (d / (np.sqrt(h) + dt(hp["eps"])))
+    elif hp["kind"] == "momentum":
         mu = dt(hp["mu"])
         v = mu * sn[0][rows] + d
         sn[0][rows] = v

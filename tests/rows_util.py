@@ -74,7 +74,7 @@ class RowOracle:
         if isinstance(want, tuple):
             ref, bound = want
             err = np.abs(got.astype(np.float64) - ref)
-            bad = np.argwhere(err > bound)
+            bad = np.argwhere(~(err <= bound))  # (a NaN fails)
             assert bad.size == 0, (f"{msg}: {len(bad)} elements beyond the bound, first (row, col) {bad[:3].tolist()}: "
                                    f"err {err[tuple(bad[0])]:.3e} bound {bound[tuple(bad[0])]:.3e}")
             return
