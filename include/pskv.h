@@ -795,7 +795,13 @@ int pskv_shard_info(pskv_shard* s, pskv_info* info);
  * TILE_SHIFT, TILE_GRID, RB_WBITS, RB_NBD, RB_TB, RB_APPLY_LOG2, RB_BIN_BLOCK,
  * SYNC_TIMEOUT_MS (the bound of every host wait, pskv_sync), FOLD_REPLAY
  * (pskv_add_get_grouped: the Add's conditional replay rides on the Get's
- * first K1 launch, K1r, instead of a K4r launch of its own; 1 = on).
+ * first K1 launch, K1r, instead of a K4r launch of its own; 1 = on),
+ * EPOCH (a test and diagnosis seam: the shard's 32-bit stamp epoch, which
+ * advances once per launch group and wraps after 0xFFFFFFFF.  Get returns the
+ * current value; set accepts current <= value <= 0xFFFFFFFF, so that the
+ * wrap-around can be reached without 2^32 calls -- every stamp and tag on the
+ * device is at most the current epoch, so forward is always safe; anything
+ * else is PSKV_EINVAL.  It has no environment default).
  * Every option changes speed only, never results.  Some apply only together
  * with others (a value is accepted and echoed either way):
  *   EARLY = 1     K2g with UNROLL 8 and NT 1 (otherwise the default loads)

@@ -2658,6 +2658,10 @@ const Option kOptions[] = {
     PSKV_OPT("UNROLL", 4, 8, tune_unroll, int),              // 4 or 8 (others: 8)
     PSKV_OPT("GET_UNROLL", 0, 8, tune_get_unroll, int),      // 0 (by size), 4 or 8
     PSKV_OPT("FOLD_REPLAY", 0, 1, tune_fold_replay, int),   // add_get: K4r folded into K1 (K1r)
+    // the stamp epoch, a test and diagnosis seam: it only moves forward (every
+    // stamp and tag on the device is at most the current epoch, so a later one
+    // still beats them all); no environment default
+    PSKV_OPT("EPOCH", 0, 0xFFFFFFFFll, epoch, uint32_t),
     PSKV_OPT("NT", 0, 1, tune_nt, bool),
     PSKV_OPT("NTP", 0, 1, tune_ntp, bool),
     PSKV_OPT("RESIDENT_BYTES", -1, INT64_MAX, tune_resident_bytes, int64_t),  // -1 = auto, 0 = off
@@ -2701,6 +2705,8 @@ int set_option(pskv_shard* s, const Option& o, int64_t v) {
     return fail(PSKV_EINVAL, "option RB_APPLY_LOG2: 0, 13 or 14");
   if (std::strcmp(o.name, "RB_BIN_BLOCK") == 0 && v != 512 && v != 1024)
     return fail(PSKV_EINVAL, "option RB_BIN_BLOCK: 512 or 1024");
+  if (std::strcmp(o.name, "EPOCH") == 0 && v < (int64_t)s->epoch)
+    return fail(PSKV_EINVAL, "option EPOCH: the epoch only moves forward");
   o.set(s, v);
   if (std::strcmp(o.name, "SYNC_TIMEOUT_MS") == 0) refresh_grow_wait(s);
   if (std::strcmp(o.name, "INLINE_ADD_CHUNKS") == 0) s->add_chunks_set = true;
@@ -2737,6 +2743,7 @@ int apply_env_options(pskv_shard* s) {
     }
   }
   for (const auto& o : kOptions) {
+    if (std::strcmp(o.name, "EPOCH") == 0) continue;  // (a seam of a live shard, not a creation default)
     const std::string var = std::string("PSKV_") + o.name;
     const char* e = std::getenv(var.c_str());
     if (!e || !*e) continue;
