@@ -61,6 +61,23 @@ def held(cuda, before, limit_gib=40):
     return now
 
 
+def reported(cuda, nbytes):
+    """What mem_get_info shows for one allocation of nbytes, made and released
+    here.  Not every device accounts for all it was asked: an MI355X inside a
+    virtual machine showed 2 MiB less per GiB (16 GiB less 32 MiB for 16 GiB),
+    so a case that must tell whether an array exists compares with this, not
+    with the array's size."""
+    import torch
+
+    torch.cuda.empty_cache()  # (no cached block may serve the probe)
+    free0, _ = torch.cuda.mem_get_info(cuda)
+    probe = torch.empty(nbytes, dtype=torch.uint8, device=cuda)
+    free1, _ = torch.cuda.mem_get_info(cuda)
+    del probe
+    torch.cuda.empty_cache()
+    return free0 - free1
+
+
 class Keys:
     """The keys a case may touch (`t`) and the probes it never touches (`u`),
     offsets into a range of `span` keys from kb: the bottom band, +-BAND around
@@ -476,11 +493,14 @@ def test_scalar_shard_with_stamps_past_2_31(cuda, oracle_mod, base):
 
     span = 2**31 + 8192
     kb = 0 if base == "low" else 2**31 - 8192
+    need(cuda, 25)
+    stamps = reported(cuda, span * 8 >> 21 << 21)  # (whole 2 MiB blocks, which torch allocates as asked: 16 GiB)
     before = need(cuda, 25)
     ks, rng = scalar_keys(("stamps", base), kb, span, [2**29, 2**30, 2**31])
     ref = oracle_mod.MapStorageRef(np.float32)
     try:
         with ps.Shard(kb, kb + span, np.float32, options={"GENERAL": 0}) as sh:
+            params = held(cuda, before)  # (the stamps come with the first general-path Add)
             sh.set_timing(True)
             for c in range(2):
                 k = ks.draw(6000)
@@ -489,7 +509,7 @@ def test_scalar_shard_with_stamps_past_2_31(cuda, oracle_mod, base):
                 ref.add(k, v)
                 check_scalar(sh, ks, ref.get, f"K4 call {c}", cuda)
             assert sh.kernel_time(_lib.PSKV_K_GENERAL_COMMIT)["launches"] == 2
-            assert held(cuda, before) > 24 * GIB, "no stamp array"
+            assert held(cuda, before) >= params + stamps, "no stamp array"
             for grouped in (False, True):  # a hint that does not hold: the replay
                 ka, kc = ks.draw(3000), ks.draw(3000)
                 va, vc = (unique_rows(7 + 2 * grouped + j, 3000, 1, np.float32).reshape(-1) for j in range(2))
