@@ -239,6 +239,50 @@ class HipStorage : public AbstractStorage {
                "pskv_apply_pooled");
   }
 
+  // The pooled rows and the factorization-machine pair term of every bag
+  // (pskv_get_pooled_fm), the bags as SubGetPooled's: pair receives one value
+  // per bag, 0.5 * sum_j((sum_i x_ij)^2 - sum_i x_ij^2) with x_i = weights[i] *
+  // row(typed_keys[i]) -- user . item for the bag {user, item}.  want_sum
+  // false: only the pairs are computed and the reply is empty.  Not part of
+  // AbstractStorage.
+  third_party::SArray<char> SubGetPooledFm(const third_party::SArray<Key>& typed_keys,
+                                           const third_party::SArray<Val>* weights,
+                                           const third_party::SArray<uint64_t>& offsets,
+                                           third_party::SArray<Val>* pair, bool want_sum = true) {
+    if (offsets.size() == 0 || (weights && weights->size() != typed_keys.size()) || !pair) {
+      std::fprintf(stderr, "Check failed: offsets.size() >= 1, weights.size() == typed_keys.size() and pair != null\n");
+      std::abort();
+    }
+    const uint64_t nbags = offsets.size() - 1;
+    auto reply_vals = FrameArray<Val>(want_sum ? nbags * width_ : 0);
+    *pair = FrameArray<Val>(nbags);
+    pskv_check(pskv_get_pooled_fm(shard_, typed_keys.data(), typed_keys.size(), weights ? weights->data() : nullptr,
+                                  offsets.data(), nbags, want_sum ? reply_vals.data() : nullptr, pair->data(),
+                                  PSKV_HOST | PSKV_HOST_FRAME),
+               "pskv_get_pooled_fm");
+    return third_party::SArray<char>(reply_vals);
+  }
+
+  // One optimizer step that is the backward pass of SubGetPooledFm
+  // (pskv_apply_pooled_fm): bag_scale holds dL/dpair per bag, bag_grads
+  // dL/dsum ((offsets.size() - 1) * width values) or null.  Every row on the
+  // right-hand side is read before the step writes any.  Not part of
+  // AbstractStorage.
+  void SubApplyPooledFm(const third_party::SArray<Key>& typed_keys, const third_party::SArray<Val>* weights,
+                        const third_party::SArray<uint64_t>& offsets, const third_party::SArray<Val>& bag_scale,
+                        const third_party::SArray<Val>* bag_grads = nullptr) {
+    if (offsets.size() == 0 || (weights && weights->size() != typed_keys.size()) ||
+        bag_scale.size() != offsets.size() - 1 || (bag_grads && bag_grads->size() != (offsets.size() - 1) * width_)) {
+      std::fprintf(stderr, "Check failed: offsets.size() >= 1, weights.size() == typed_keys.size(), "
+                           "bag_scale.size() == offsets.size() - 1 and bag_grads.size() == (offsets.size() - 1) * width\n");
+      std::abort();
+    }
+    pskv_check(pskv_apply_pooled_fm(shard_, typed_keys.data(), typed_keys.size(), weights ? weights->data() : nullptr,
+                                    offsets.data(), offsets.size() - 1, bag_scale.data(),
+                                    bag_grads ? bag_grads->data() : nullptr, PSKV_HOST | PSKV_HOST_FRAME),
+               "pskv_apply_pooled_fm");
+  }
+
   // The four arrays of one SubApplyPooled call, each a counted reference, so a
   // deferred push keeps its data alive until the flush (weighted false: every
   // weight is one and `weights` is not read).

@@ -307,6 +307,71 @@
  *     slot, one operation per launch group, elements = the sum of n;
  *   - not provided: a grouped pooled PULL (it would save launches only).
  *
+ * Factorization-machine pooled calls (pskv_get_pooled_fm, pskv_apply_pooled_fm;
+ * DESIGN.md §8p): the second-order term of a factorization machine over a bag,
+ *     pair_b = 0.5 * sum_j [ (sum_i x_ij)^2 - sum_i x_ij^2 ],   x_i = w_i * row(key_i),
+ * and its backward step, both computed in the shard.  For the bag {user, item}
+ * with unit weights pair is user . item, the prediction of the reference's
+ * matrix factorisation (app/mf.cpp:426-430), and the push below is its update
+ * (app/mf.cpp:496-497).  Bags, offsets, weights (NULL: every weight is one and
+ * nothing is multiplied) and flags are pskv_get_pooled's and
+ * pskv_apply_pooled's; T is the shard's value type; every operation below is
+ * rounded to T once and none is contracted with a neighbour, except where a
+ * fused operation is named.
+ *   The pull, for bag b over its key positions i in key order:
+ *     x_ij = w_i * p_ij                    (weights NULL: x_ij = p_ij)
+ *     S_j  : pskv_get_pooled's sum, the same order and the same fma, so out_sum
+ *            equals pskv_get_pooled's out bit for bit
+ *     Q_j  = fma(x_ij, x_ij, Q_j)          the first term is x_ij * x_ij alone
+ *     t_j  = (S_j * S_j) - Q_j             two roundings, never an fma
+ *     pair = 0.5 * sum_j t_j               in an order that is a function of W
+ *            and T alone, a fixed tree: never of the launch, the alignment of
+ *            an argument, an option or timing
+ *   - a bag of zero or one key has pair == +0 (all bits zero); the same call on
+ *     the same contents returns the same bits; there are no atomics;
+ *   - a bag of more than 256 keys is cut into chunks of 256 as a pooled pull's:
+ *     its partial S and Q rows (not partial pairs: the term is not additive
+ *     over chunks) are added in chunk order and t_j is formed after that;
+ *   - out_sum == NULL skips that store and changes nothing else.
+ *   The push: one call is one optimizer step, the step pskv_apply(keys, rows, n)
+ *   would make with, c_b = bag_scale[b] (dL/dpair_b) and S_b the pull's sum,
+ *     t_bj  = c_b * S_bj                   (+ bag_grads[b][j], one addition, when bag_grads != NULL)
+ *     e_i   = c_b * (w_i * w_i)            (weights NULL: e_i = c_b)
+ *     rows[i][j] = (w_i * t_bj) - (e_i * p_ij)      (weights NULL: t_bj - c_b * p_ij)
+ *   - EVERY S_b and every p_ij on the right-hand side is read from the rows as
+ *     they are before this step writes any of them;
+ *   - occurrences of a key are summed in unspecified order, the rule is applied
+ *     once per distinct key, every other key keeps p and its state bit for bit;
+ *     with distinct keys p and every state slot equal pskv_apply of those rows
+ *     bit for bit;
+ *   - the bag {u, v} with unit weights and c = -(label - predict) gives
+ *     rows[u] = c * v and rows[v] = c * u: with SGD and weight_decay = beta the
+ *     reference's update, but for its line 497, which reads the user vector
+ *     line 496 has already updated; here both rows are pre-step.
+ *   Rules, each as the named call's:
+ *   - float shards only (PSKV_I32: PSKV_EINVAL), any width (1 included),
+ *     either creation mode; the push needs an optimizer, as pskv_apply_pooled;
+ *   - as pskv_get_pooled / pskv_apply_pooled word for word: the checks before
+ *     the handle is looked at (flags; null keys, offsets, out_pair / bag_scale
+ *     with a non-zero count; the push's n > 2^31; a host call's offsets,
+ *     naming the first bad bag; all also for a null shard); nbags == 0 and
+ *     n == 0 (the pull writes zeros to both outputs; the push does nothing and
+ *     leaves the step counter alone); keys outside the range of a row shard;
+ *     the clamp of malformed device offsets (unspecified values, never an
+ *     access outside the call's arrays or a change to a key not in the call);
+ *     the step counter; SERVE = 1 is ended first; a host pull is synchronous, a
+ *     host push returns once its copies are queued, device calls are
+ *     stream-ordered;
+ *   - sparse shards by the relabelling rule: the pull never inserts and reads
+ *     an absent key as a row of zeros without error; the push inserts before
+ *     anything is read, so a new key contributes a zero row to S;
+ *   - non-finite values propagate by IEEE rules and reach only the bags and
+ *     keys that hold them; the gradient scratch is all-zero bits after the call;
+ *   - timing: the pull counts in PSKV_TIME_POOLED, the push in PSKV_TIME_APPLY,
+ *     elements = n;
+ *   - not provided: grouped forms, int32, field-aware or higher-order terms,
+ *     and the linear term, which is a W = 1 shard's existing pooled calls.
+ *
  * Sparse shards (pskv_shard_create_sparse): a shard whose memory
  * follows the number of keys it holds, not the span of the key space -- the
  * storage of a server under consistent hashing (a scattered 1/N of the keys),
@@ -616,6 +681,16 @@ int pskv_get_pooled(pskv_shard* s, const uint32_t* keys, uint64_t n, const void*
  * bag_grads: nbags * W values, row b at element b * W. */
 int pskv_apply_pooled(pskv_shard* s, const uint32_t* keys, uint64_t n, const void* weights,
                       const uint64_t* offsets, uint64_t nbags, const void* bag_grads, int flags);
+
+/* FM pooled pull and push (semantics: "Factorization-machine pooled calls").
+ * out_sum: nbags * W values (the pooled pull's rows) or NULL; out_pair: nbags
+ * values.  bag_scale: nbags values, dL/dpair_b; bag_grads: nbags * W values,
+ * dL/dsum_b, or NULL. */
+int pskv_get_pooled_fm(pskv_shard* s, const uint32_t* keys, uint64_t n, const void* weights,
+                       const uint64_t* offsets, uint64_t nbags, void* out_sum, void* out_pair, int flags);
+int pskv_apply_pooled_fm(pskv_shard* s, const uint32_t* keys, uint64_t n, const void* weights,
+                         const uint64_t* offsets, uint64_t nbags, const void* bag_scale,
+                         const void* bag_grads, int flags);
 
 /* Grouped pooled push (semantics: "Grouped pooled pushes"): ONE optimizer step
  * from the pooled pushes of nb workers, the step pskv_apply_pooled would make

@@ -365,6 +365,59 @@ hipError_t launch_row_pooled_chunks(int dtype, const PoolArgs& a, const DenseVie
 hipError_t launch_row_pooled(int dtype, bool nt, const PoolArgs& a, const DenseView& d, const Ovf& o,
                              const RowShape& rs, hipStream_t st);
 
+// Factorization-machine pooled calls (pskv_get_pooled_fm, pskv_apply_pooled_fm;
+// pskv.h "Factorization-machine pooled calls"), float shards.
+// With S_b the pooled pull's sum of bag b and Q_b the sum of its squared terms:
+//   the pull      sum[b] = S_b (skipped when null), pair[b] = 0.5 * sum_j (S_bj * S_bj - Q_bj)
+//   the bag rows  out[b] = scale[b] * S_b (+ bag_grads[b]): phase 1 of the push
+// Bags, their clamp and the chunks of long bags as a pooled pull's.
+struct FmPoolArgs {
+  const uint32_t* keys;     // n
+  const void* weights;      // n values, or null: every weight is one
+  const uint64_t* offsets;  // nbags + 1
+  uint64_t n, nbags;
+  void* out;                // nbags rows: the pull's sum (or null), the bag rows' result
+  void* pair;               // the pull: nbags values
+  void* part;               // pool_slots(n) partial S rows of long bags' chunks; null when n <= kPoolChunk
+  void* part_q;             // the pull: as many partial Q rows
+  const void* scale;        // the bag rows: nbags values
+  const void* bag_grads;    // the bag rows: nbags rows, or null
+  int out_unit16;           // `out` is 16-byte aligned (else a 16-byte unit is stored element by element)
+};
+// The pull: long bags' partial S and Q rows first (skipped when n <=
+// kPoolChunk), then every bag.  unit16 of rs wants the row size a multiple of
+// 16 bytes and the dense array and the partial rows aligned, NOT `out`: the
+// unit is a function of the width alone, and with it the order of the sum over j.
+hipError_t launch_row_fm_pooled_chunks(int dtype, const FmPoolArgs& a, const DenseView& d, const Ovf& o,
+                                       const RowShape& rs, hipStream_t st);
+hipError_t launch_row_fm_pooled(int dtype, const FmPoolArgs& a, const DenseView& d, const Ovf& o,
+                                const RowShape& rs, hipStream_t st);
+// The bag rows; a.part as launch_row_pooled_chunks left it (the pooled pull's own chunk pass).
+hipError_t launch_row_fm_bag_rows(int dtype, const FmPoolArgs& a, const DenseView& d, const Ovf& o,
+                                  const RowShape& rs, hipStream_t st);
+
+// The push's step: PoolPushArgs with the bag rows of phase 1 in bag_grads and
+// the scale c of every bag; the gradient row of key position i, formed in
+// registers from its bag's row t and the key's own PRE-STEP row p, is
+//   (w_i * t) - ((c * (w_i * w_i)) * p)      weights null: t - (c * p)
+// every product and the difference rounded to the value type once.
+struct FmPushArgs {
+  const uint32_t* keys;     // n
+  const void* weights;      // n values, or null
+  const uint64_t* offsets;  // nbags + 1 (the kernels read [0, nbags))
+  uint64_t n, nbags;
+  const void* bag_grads;    // nbags rows: t
+  const void* bag_scale;    // nbags values: c
+};
+// As the templates above (chosen for an FmPushArgs block): the losers read
+// d.param, so they run before the apply pass of the same step.
+hipError_t launch_row_step_losers(int dtype, const FmPushArgs& a, uint32_t nwg, const DenseView& d, void* gsum,
+                                  const unsigned long long* owner, const Ovf& o, uint32_t epoch, const RowShape& rs,
+                                  hipStream_t st);
+hipError_t launch_row_step_apply(int dtype, int kind, const FmPushArgs& a, uint32_t nwg, const DenseView& d, void* gsum,
+                                 void* const state[2], const unsigned long long* owner, uint32_t epoch,
+                                 const RowShape& rs, const OptArgs<double>& hy, hipStream_t st);
+
 // Sparse shards (pskv_index.hip): the hash index that maps a
 // uint32 key to a slot of the row arrays.  table: mask + 1 entries (a power of
 // two, >= 2 * capacity), linear probing from fmix32(key).  An entry is 0 when

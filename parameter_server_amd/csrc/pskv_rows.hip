@@ -10,6 +10,11 @@
 //                     or a group of pooled pushes' rows weight * bag_grads[bag], formed in registers)
 //   k_row_pooled      pooled pull: out[b] = sum over bag b's keys of weight * row(key)
 //   k_row_pooled_chunks  pooled pull: the chunks of bags longer than kPoolChunk, into partial rows
+//   k_row_fm_pooled      FM pooled pull: the pooled sum and pair[b] = 0.5 * sum_j (S_j * S_j - Q_j), reduced
+//                        over the row inside the wave; also the bag rows c_b * S_b (+ bag_grads[b]) of an FM push
+//   k_row_fm_pooled_chunks  FM pooled pull: the partial S and Q rows of long bags' chunks
+//   k_row_fm_step_losers, k_row_fm_step_apply  FM push: the pooled step whose gradient rows hold the key's own
+//                        pre-step row, (w * t) - (e * p)
 //
 // Lane mapping (all of them).  A row is U units long (RowShape); a group of
 // L = min(64, next_pow2(U)) consecutive lanes owns one row at a time, lane l
@@ -883,6 +888,410 @@ void launch_row_pooled_chunks_v(uint32_t grid, const PoolArgs& a, const DenseVie
     k_row_pooled_chunks<T, V, false><<<grid, kBlock, 0, st>>>(a, d, err, rs);
 }
 
+// ------------------------------------- factorization-machine pooled calls
+// pskv_get_pooled_fm / pskv_apply_pooled_fm.  The pull is the
+// pooled pull's lane mapping with a second chain per element, Q = sum of the
+// squared terms, beside S; at the end of a unit strip a lane folds
+// S * S - Q of the strip's elements into ONE running scalar, and after the
+// last strip the scalars of the group's L lanes meet in a butterfly inside the
+// wave (a group never spans waves: no LDS).  The order of that sum over j is
+// fixed by the unit and L, both functions of the width (the unit does not
+// depend on where `out` lies: FmPoolArgs::out_unit16).
+
+// These kernels are compiled without the packed-float instructions
+// (v_pk_add_f32, v_pk_mul_f32, v_pk_fma_f32): every float operation is a scalar
+// VALU instruction.
+#define PSKV_NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
+
+// x with its rounding kept apart from whatever reads it (rounded_mul's device).
+template <typename T>
+__device__ __forceinline__ T rounded(T x) {
+  asm("" : "+v"(x));
+  return x;
+}
+
+// pool_sum with the second chain: unit u of S (pool_sum's bits: the same
+// order, the same fma) and, PAIR, of Q = x_0 * x_0, then fma(x_i, x_i, Q),
+// x_i = w_i * p_i rounded (weights null: p_i).
+template <typename T, int V, int R, bool WEIGHTED, bool PAIR>
+__device__ __forceinline__ void fm_sum(const uint32_t* __restrict__ keys, const T* __restrict__ weights, uint64_t b,
+                                       uint64_t e, const T* __restrict__ param, const DenseView& d, uint32_t U,
+                                       uint32_t u, bool& oor, OptUnit<T, V>& S, OptUnit<T, V>& Q) {
+  S = zero_opt_unit<T, V>();
+  Q = zero_opt_unit<T, V>();
+  bool have = false;
+  uint32_t k[R];
+  T w[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    k[r] = b + r < e ? keys[b + r] : 0u;
+    w[r] = (WEIGHTED && b + r < e) ? weights[b + r] : T(0);
+  }
+  for (uint64_t i = b; i < e; i += R) {
+    OptUnit<T, V> p[R];
+    T wc[R];
+    bool live[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      live[r] = i + r < e;
+      const uint32_t off = k[r] - d.key_begin;
+      const bool in = live[r] && (uint64_t)off < d.range;
+      oor |= live[r] && !in;
+      wc[r] = w[r];
+      p[r] = in ? load_opt_unit<T, V>(param, (uint64_t)off * U + u) : zero_opt_unit<T, V>();
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const uint64_t nx = i + R + r;
+      k[r] = nx < e ? keys[nx] : 0u;
+      w[r] = (WEIGHTED && nx < e) ? weights[nx] : T(0);
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      if (!live[r]) continue;
+#pragma unroll
+      for (int j = 0; j < V; ++j) {
+        const T pj = p[r].e[j];
+        const T x = WEIGHTED ? rounded_mul(wc[r], pj) : pj;
+        if (WEIGHTED)
+          S.e[j] = have ? pool_fma(wc[r], pj, S.e[j]) : x;
+        else
+          S.e[j] = have ? S.e[j] + pj : pj;
+        if (PAIR) Q.e[j] = have ? pool_fma(x, x, Q.e[j]) : x * x;
+      }
+      have = true;
+    }
+  }
+}
+
+// k_row_pooled_chunks with the second chain: the at most two long-bag chunks
+// that start in a window, their partial S rows into `part`, Q rows into `part_q`.
+template <typename T, int V, bool WEIGHTED>
+__global__ PSKV_NO_PK_F32 __launch_bounds__(kBlock) void k_row_fm_pooled_chunks(FmPoolArgs a, DenseView d, uint32_t* err,
+                                                                 RowShape rs) {
+  const uint32_t lane = threadIdx.x & (rs.lanes - 1u);
+  const uint32_t grp = threadIdx.x >> rs.lshift;
+  const uint32_t G = (uint32_t)kBlock >> rs.lshift;
+  const uint32_t U = rs.units;
+  const T* __restrict__ param = reinterpret_cast<const T*>(d.param);
+  const T* __restrict__ weights = reinterpret_cast<const T*>(a.weights);
+  T* __restrict__ part = reinterpret_cast<T*>(a.part);
+  T* __restrict__ part_q = reinterpret_cast<T*>(a.part_q);
+  const uint64_t nwin = (a.n + kPoolChunk - 1) / kPoolChunk;
+  for (uint64_t q = (uint64_t)blockIdx.x * G + grp; q < nwin; q += (uint64_t)gridDim.x * G) {
+    const uint64_t lo = q * kPoolChunk;
+    const uint64_t hi = (lo + kPoolChunk < a.n ? lo + kPoolChunk : a.n) - 1;
+    const uint64_t ba = pool_bag_of(a.offsets, a.nbags, lo);
+    const uint64_t bb = pool_bag_of(a.offsets, a.nbags, hi);
+    for (int cand = 0; cand < 2; ++cand) {
+      if (cand == 1 && bb == ba) break;
+      const uint64_t bag = cand ? bb : ba;  // < nbags
+      const PoolBag bg = pool_clamp(a.offsets[bag], a.offsets[bag + 1], a.n);
+      const uint64_t c = pool_window_chunk(bg.begin, bg.end, q);
+      if (c == kPoolNone) continue;
+      const uint64_t p0 = bg.begin + c * kPoolChunk;  // in the window, below bg.end <= n
+      const uint64_t p1 = p0 + kPoolChunk < bg.end ? p0 + kPoolChunk : bg.end;
+      const uint64_t slot = pool_slot(bg.begin, c);  // < pool_slots(n), as p0 < n
+      bool oor = false;
+      for (uint32_t u = lane; u < U; u += rs.lanes) {
+        OptUnit<T, V> S, Q;
+        fm_sum<T, V, kPoolChunkRowsInFlight, WEIGHTED, true>(a.keys, weights, p0, p1, param, d, U, u, oor, S, Q);
+        store_opt_unit<T, V>(part, slot * U + u, S);
+        store_opt_unit<T, V>(part_q, slot * U + u, Q);
+      }
+      if (oor && lane == 0) atomicOr(err, kErrRowOutOfRange);
+    }
+  }
+}
+
+// The sum of a long bag's partial rows in chunk order (k_row_pooled's).
+template <typename T, int V>
+__device__ __forceinline__ OptUnit<T, V> fm_parts_sum(const T* __restrict__ part, uint64_t begin, uint64_t nc,
+                                                      uint32_t U, uint32_t u) {
+  OptUnit<T, V> acc = zero_opt_unit<T, V>();
+  bool have = false;
+  for (uint64_t c = 0; c < nc; c += kPoolPartsInFlight) {
+    OptUnit<T, V> s[kPoolPartsInFlight];
+#pragma unroll
+    for (int r = 0; r < kPoolPartsInFlight; ++r)
+      if (c + r < nc) s[r] = load_opt_unit<T, V>(part, pool_slot(begin, c + r) * U + u);
+#pragma unroll
+    for (int r = 0; r < kPoolPartsInFlight; ++r)
+      if (c + r < nc) pool_add_unit<T, V>(acc, have, s[r]);
+  }
+  return acc;
+}
+
+// Work items as k_row_pooled's: a lane group per bag.  PAIR: the pull (S to
+// a.out unless null, the pair term to a.pair); else the bag rows of a push,
+// a.out[b] = c_b * S_b (+ bag_grads[b]), no Q chain and no cross-lane step.
+// The pair term: lane l of the group adds (S * S) - Q, two roundings, of its
+// elements to one scalar in the order it meets them (strips outward, a unit's
+// elements in order); lanes at or past U hold +0; then log2(L) butterfly
+// steps, partner l ^ (L/2), ..., l ^ 1 -- every lane of the group ends with
+// the same bits (IEEE addition commutes), lane 0 stores 0.5 times them.
+template <typename T, int V, bool WEIGHTED, bool PAIR>
+__global__ PSKV_NO_PK_F32 __launch_bounds__(kBlock) void k_row_fm_pooled(FmPoolArgs a, DenseView d, uint32_t* err, RowShape rs) {
+  const uint32_t lane = threadIdx.x & (rs.lanes - 1u);
+  const uint32_t grp = threadIdx.x >> rs.lshift;
+  const uint32_t G = (uint32_t)kBlock >> rs.lshift;
+  const uint32_t U = rs.units;
+  const T* __restrict__ param = reinterpret_cast<const T*>(d.param);
+  const T* __restrict__ weights = reinterpret_cast<const T*>(a.weights);
+  const T* __restrict__ part = reinterpret_cast<const T*>(a.part);
+  const T* __restrict__ part_q = reinterpret_cast<const T*>(a.part_q);
+  const T* __restrict__ scale = reinterpret_cast<const T*>(a.scale);
+  const T* __restrict__ bag_grads = reinterpret_cast<const T*>(a.bag_grads);
+  T* __restrict__ out = reinterpret_cast<T*>(a.out);
+  T* __restrict__ pair = reinterpret_cast<T*>(a.pair);
+  const uint64_t nvwg = (a.nbags + kPoolBagsPerWg - 1) / kPoolBagsPerWg;
+  for (uint64_t wg = blockIdx.x; wg < nvwg; wg += gridDim.x) {
+    for (uint32_t g = grp; g < kPoolBagsPerWg; g += G) {
+      const uint64_t bag = wg * kPoolBagsPerWg + g;
+      if (bag >= a.nbags) break;
+      const PoolBag bg = pool_clamp(a.offsets[bag], a.offsets[bag + 1], a.n);
+      const uint64_t m = bg.end - bg.begin;
+      const T c = PAIR ? T(0) : scale[bag];
+      T term = T(0);
+      bool oor = false;
+      for (uint32_t u = lane; u < U; u += rs.lanes) {
+        OptUnit<T, V> S, Q;
+        if (m > kPoolChunk) {
+          const uint64_t nc = pool_chunks(m);
+          S = fm_parts_sum<T, V>(part, bg.begin, nc, U, u);
+          if (PAIR) Q = fm_parts_sum<T, V>(part_q, bg.begin, nc, U, u);
+        } else {
+          fm_sum<T, V, kRowsInFlight, WEIGHTED, PAIR>(a.keys, weights, bg.begin, bg.end, param, d, U, u, oor, S, Q);
+        }
+        if (PAIR) {
+#pragma unroll
+          for (int j = 0; j < V; ++j) term = term + rounded(rounded_mul(S.e[j], S.e[j]) - Q.e[j]);
+        } else {
+          OptUnit<T, V> bgr = zero_opt_unit<T, V>();
+          if (bag_grads) bgr = load_opt_unit<T, V>(bag_grads, bag * U + u);
+#pragma unroll
+          for (int j = 0; j < V; ++j) {
+            S.e[j] = rounded_mul(c, S.e[j]);
+            if (bag_grads) S.e[j] = S.e[j] + bgr.e[j];
+          }
+        }
+        if (out) {
+          if (V == 1 || a.out_unit16) {
+            store_opt_unit<T, V>(out, bag * U + u, S);
+          } else {
+#pragma unroll
+            for (int j = 0; j < V; ++j) out[(bag * U + u) * V + j] = S.e[j];
+          }
+        }
+      }
+      if (PAIR) {
+        for (uint32_t step = rs.lanes >> 1; step > 0; step >>= 1) term = term + __shfl_xor(term, (int)step);
+        if (lane == 0) pair[bag] = T(0.5) * term;
+      }
+      if (oor && lane == 0) atomicOr(err, kErrRowOutOfRange);
+    }
+  }
+}
+
+// The gradient row element of a position of an FM push from its bag's t and
+// its key's pre-step p: (w * t) - (e * p), e = c * (w * w); weights null: t - (c * p).
+template <typename T, bool WEIGHTED>
+__device__ __forceinline__ T fm_row(T w, T e, T t, T p) {
+  return rounded((WEIGHTED ? rounded_mul(w, t) : t) - rounded_mul(e, p));
+}
+template <typename T, bool WEIGHTED>
+__device__ __forceinline__ T fm_own_scale(T c, T w) {
+  return WEIGHTED ? rounded_mul(c, rounded_mul(w, w)) : c;
+}
+
+// k_row_step_losers for an FM push: one element per lane; a loser also reads
+// its key's row of d.param, which no launch writes before every loser is done
+// (the apply pass is the next launch of the stream).
+template <typename AT, bool WEIGHTED>
+__global__ PSKV_NO_PK_F32 __launch_bounds__(kBlock) void k_row_fm_step_losers(FmPushArgs a, DenseView d, AT* __restrict__ gsum,
+                                                               const unsigned long long* __restrict__ owner,
+                                                               uint32_t* err, uint32_t epoch, RowShape rs) {
+  const uint32_t lane = threadIdx.x & (rs.lanes - 1u);
+  const uint32_t grp = threadIdx.x >> rs.lshift;
+  const uint32_t G = (uint32_t)kBlock >> rs.lshift;
+  const uint32_t U = rs.units;
+  const AT* param = reinterpret_cast<const AT*>(d.param);
+  const AT* __restrict__ weights = reinterpret_cast<const AT*>(a.weights);
+  const AT* __restrict__ rows = reinterpret_cast<const AT*>(a.bag_grads);
+  const AT* __restrict__ scale = reinterpret_cast<const AT*>(a.bag_scale);
+  const uint32_t nvwg = (uint32_t)((a.n + kGeneralChunk - 1) / kGeneralChunk);
+  for (uint32_t wg = blockIdx.x; wg < nvwg; wg += gridDim.x) {
+    const uint64_t base = (uint64_t)wg * kGeneralChunk;
+    PoolSpan sp{0, 0};
+    bool have = false;
+    for (uint32_t r0 = grp; r0 < (uint32_t)kGeneralChunk; r0 += kRowsInFlight * G) {
+      if (base + r0 >= a.n) break;
+      RowStep s;
+      load_step(s, a.keys, a.n, base, r0, G, d);
+      bool lose[kRowsInFlight];
+      bool any = false;
+#pragma unroll
+      for (int r = 0; r < kRowsInFlight; ++r) {
+        const unsigned long long tag = row_tag(epoch, base + r0 + (uint32_t)r * G);
+        lose[r] = s.in[r] && owner[s.off[r]] != tag;
+        any |= lose[r];
+        if (s.live[r] && !s.in[r] && lane == 0) atomicOr(err, kErrRowOutOfRange);
+      }
+      if (!any) continue;  // distinct keys: only keys and stamps were read
+      uint64_t bag[kRowsInFlight];
+      AT w[kRowsInFlight], e[kRowsInFlight];
+      step_bags(a, a.offsets, base, sp, have, s, lose, bag);
+#pragma unroll
+      for (int r = 0; r < kRowsInFlight; ++r) {
+        w[r] = (WEIGHTED && lose[r]) ? weights[s.i[r]] : AT(1);
+        e[r] = fm_own_scale<AT, WEIGHTED>(lose[r] ? scale[bag[r]] : AT(0), w[r]);
+      }
+      for (uint32_t u = lane; u < U; u += rs.lanes) {
+        AT t[kRowsInFlight], p[kRowsInFlight];
+#pragma unroll
+        for (int r = 0; r < kRowsInFlight; ++r) {
+          t[r] = lose[r] ? rows[bag[r] * U + u] : AT(0);
+          p[r] = lose[r] ? param[(uint64_t)s.off[r] * U + u] : AT(0);
+        }
+#pragma unroll
+        for (int r = 0; r < kRowsInFlight; ++r)
+          if (lose[r])
+            (void)atomicAdd(gsum + (uint64_t)s.off[r] * U + u, fm_row<AT, WEIGHTED>(w[r], e[r], t[r], p[r]));
+      }
+    }
+  }
+}
+
+// opt_step_unit as pskv_apply's kernels run it.  One instantiation differs:
+// k_row_step_apply's element kernel of float Adam is compiled with its two
+// moment updates paired into packed instructions, which settles which product
+// of each update is fused into the addition (m: the new term's, v: the decayed
+// moment's); without packed instructions the compiler fuses the decayed moment's
+// in both and a last bit of m differs now and then.  That instantiation is written out here with
+// pskv_apply's fusions, so that distinct keys give pskv_apply's bits at every
+// width (tests/test_fm_gpu.py compares them).
+template <typename T, int KIND, int V>
+__device__ __forceinline__ bool fm_step_unit(const OptUnit<T, V>& g, OptUnit<T, V>& gs, OptUnit<T, V>& p,
+                                             OptUnit<T, V>& h, OptUnit<T, V>& h2, const OptArgs<T>& o) {
+  if constexpr (KIND == 4 && V == 1 && std::is_same<T, float>::value) {
+    const bool dirty = nonzero_bits(gs.e[0]);
+    const float dd = pool_fma(o.wd, p.e[0], g.e[0] + gs.e[0]);
+    h.e[0] = pool_fma(o.omb1, dd, rounded_mul(o.beta1, h.e[0]));
+    h2.e[0] = pool_fma(o.beta2, h2.e[0], rounded_mul(o.omb2, rounded_mul(dd, dd)));
+    const float q = h.e[0] / pool_fma(sqrt(h2.e[0]), o.b, o.eps);
+    p.e[0] = pool_fma(-o.a, q, p.e[0]);
+    gs.e[0] = 0.0f;
+    return dirty;
+  } else {
+    return opt_step_unit<T, KIND, V>(g, gs, p, h, h2, o);
+  }
+}
+
+// k_row_step_apply for an FM push: the winner forms its row from its bag's t
+// unit and the p unit it loads for the step anyway.  It is its row's only
+// writer and no other position reads that row in this launch.
+template <typename T, int KIND, int V, bool WEIGHTED>
+__global__ PSKV_NO_PK_F32 __launch_bounds__(kBlock) void k_row_fm_step_apply(FmPushArgs a, DenseView d, T* __restrict__ gsum,
+                                                              T* __restrict__ state, T* __restrict__ state2,
+                                                              const unsigned long long* __restrict__ owner,
+                                                              uint32_t epoch, RowShape rs, OptArgs<T> o) {
+  const uint32_t lane = threadIdx.x & (rs.lanes - 1u);
+  const uint32_t grp = threadIdx.x >> rs.lshift;
+  const uint32_t G = (uint32_t)kBlock >> rs.lshift;
+  const uint32_t U = rs.units;
+  T* __restrict__ param = reinterpret_cast<T*>(d.param);
+  const T* __restrict__ weights = reinterpret_cast<const T*>(a.weights);
+  const T* __restrict__ rows = reinterpret_cast<const T*>(a.bag_grads);
+  const T* __restrict__ scale = reinterpret_cast<const T*>(a.bag_scale);
+  const uint32_t nvwg = (uint32_t)((a.n + kGeneralChunk - 1) / kGeneralChunk);
+  for (uint32_t wg = blockIdx.x; wg < nvwg; wg += gridDim.x) {
+    const uint64_t base = (uint64_t)wg * kGeneralChunk;
+    PoolSpan sp{0, 0};
+    bool have = false;
+    for (uint32_t r0 = grp; r0 < (uint32_t)kGeneralChunk; r0 += kRowsInFlight * G) {
+      if (base + r0 >= a.n) break;
+      RowStep s;
+      load_step(s, a.keys, a.n, base, r0, G, d);
+      bool win[kRowsInFlight];
+      bool any = false;
+#pragma unroll
+      for (int r = 0; r < kRowsInFlight; ++r) {
+        win[r] = s.in[r] && owner[s.off[r]] == row_tag(epoch, base + r0 + (uint32_t)r * G);
+        any |= win[r];
+      }
+      if (!any) continue;
+      uint64_t bag[kRowsInFlight];
+      T w[kRowsInFlight], e[kRowsInFlight];
+      step_bags(a, a.offsets, base, sp, have, s, win, bag);
+#pragma unroll
+      for (int r = 0; r < kRowsInFlight; ++r) {
+        w[r] = (WEIGHTED && win[r]) ? weights[s.i[r]] : T(1);
+        e[r] = fm_own_scale<T, WEIGHTED>(win[r] ? scale[bag[r]] : T(0), w[r]);
+      }
+      for (uint32_t u = lane; u < U; u += rs.lanes) {
+        OptUnit<T, V> g[kRowsInFlight], gs[kRowsInFlight], p[kRowsInFlight], h[kRowsInFlight], h2[kRowsInFlight];
+#pragma unroll
+        for (int r = 0; r < kRowsInFlight; ++r) {
+          if (!win[r]) continue;
+          const uint64_t at = (uint64_t)s.off[r] * U + u;
+          g[r] = load_opt_unit<T, V>(rows, bag[r] * U + u);
+          gs[r] = load_opt_unit<T, V>(gsum, at);
+          p[r] = load_opt_unit<T, V>(param, at);
+          if (KIND >= 2) h[r] = load_opt_unit<T, V>(state, at);
+          if (KIND >= 4) h2[r] = load_opt_unit<T, V>(state2, at);
+        }
+#pragma unroll
+        for (int r = 0; r < kRowsInFlight; ++r) {
+          if (!win[r]) continue;
+          const uint64_t at = (uint64_t)s.off[r] * U + u;
+#pragma unroll
+          for (int i = 0; i < V; ++i) g[r].e[i] = fm_row<T, WEIGHTED>(w[r], e[r], g[r].e[i], p[r].e[i]);
+          const bool dirty = fm_step_unit<T, KIND, V>(g[r], gs[r], p[r], h[r], h2[r], o);
+          store_opt_unit<T, V>(param, at, p[r]);
+          if (KIND >= 2) store_opt_unit<T, V>(state, at, h[r]);
+          if (KIND >= 4) store_opt_unit<T, V>(state2, at, h2[r]);
+          if (dirty) store_opt_unit<T, V>(gsum, at, gs[r]);
+        }
+      }
+    }
+  }
+}
+
+bool fm_step_args_ok(const FmPushArgs& a, uint32_t nwg) {
+  return a.n != 0 && a.n <= kMaxPiece && a.nbags != 0 && a.bag_grads && a.bag_scale &&
+         nwg == (a.n + kGeneralChunk - 1) / kGeneralChunk;
+}
+
+// f(V) with V the elements of rs's unit, as an integral constant.
+template <typename T, typename F>
+void with_opt_unit(const RowShape& rs, F&& f) {
+  if (rs.unit_bytes == 16)
+    f(std::integral_constant<int, 16 / sizeof(T)>());
+  else
+    f(std::integral_constant<int, 1>());
+}
+
+template <bool PAIR>
+hipError_t launch_row_fm_bags(int dtype, const FmPoolArgs& a, const DenseView& d, const Ovf& o, const RowShape& rs,
+                              hipStream_t st) {
+  if (a.nbags == 0) return hipSuccess;
+  if ((PAIR ? !a.pair : !a.out || !a.scale) || (a.n > kPoolChunk && (!a.part || (PAIR && !a.part_q))))
+    return hipErrorInvalidValue;
+  const uint64_t nwg = (a.nbags + kPoolBagsPerWg - 1) / kPoolBagsPerWg;
+  const uint32_t grid = row_grid((uint32_t)std::min<uint64_t>(nwg, 4096));
+  uint32_t* err = &o.c->stat[1];
+  return with_float_type(dtype, [&](auto z) {
+    using T = decltype(z);
+    with_opt_unit<T>(rs, [&](auto v) {
+      constexpr int V = decltype(v)::value;
+      if (a.weights)
+        k_row_fm_pooled<T, V, true, PAIR><<<grid, kBlock, 0, st>>>(a, d, err, rs);
+      else
+        k_row_fm_pooled<T, V, false, PAIR><<<grid, kBlock, 0, st>>>(a, d, err, rs);
+    });
+  });
+}
+
 }  // namespace
 
 RowShape row_shape(uint32_t width, int vb, bool unit16) {
@@ -1031,6 +1440,77 @@ hipError_t launch_row_pooled(int dtype, bool nt, const PoolArgs& a, const DenseV
       launch_row_pooled_v<T, 16 / sizeof(T)>(grid, nt, a, d, err, rs, st);
     else
       launch_row_pooled_v<T, 1>(grid, nt, a, d, err, rs, st);
+  });
+}
+
+hipError_t launch_row_fm_pooled_chunks(int dtype, const FmPoolArgs& a, const DenseView& d, const Ovf& o,
+                                       const RowShape& rs, hipStream_t st) {
+  if (a.nbags == 0 || a.n <= kPoolChunk) return hipSuccess;  // no bag can be long
+  if (!a.part || !a.part_q) return hipErrorInvalidValue;
+  const uint64_t G = (uint64_t)kBlock >> rs.lshift;
+  const uint64_t nwg = ((a.n + kPoolChunk - 1) / kPoolChunk + G - 1) / G;
+  const uint32_t grid = row_grid((uint32_t)std::min<uint64_t>(nwg, 4096));
+  uint32_t* err = &o.c->stat[1];
+  return with_float_type(dtype, [&](auto z) {
+    using T = decltype(z);
+    with_opt_unit<T>(rs, [&](auto v) {
+      constexpr int V = decltype(v)::value;
+      if (a.weights)
+        k_row_fm_pooled_chunks<T, V, true><<<grid, kBlock, 0, st>>>(a, d, err, rs);
+      else
+        k_row_fm_pooled_chunks<T, V, false><<<grid, kBlock, 0, st>>>(a, d, err, rs);
+    });
+  });
+}
+
+hipError_t launch_row_fm_pooled(int dtype, const FmPoolArgs& a, const DenseView& d, const Ovf& o,
+                                const RowShape& rs, hipStream_t st) {
+  return launch_row_fm_bags<true>(dtype, a, d, o, rs, st);
+}
+
+hipError_t launch_row_fm_bag_rows(int dtype, const FmPoolArgs& a, const DenseView& d, const Ovf& o,
+                                  const RowShape& rs, hipStream_t st) {
+  return launch_row_fm_bags<false>(dtype, a, d, o, rs, st);
+}
+
+hipError_t launch_row_step_losers(int dtype, const FmPushArgs& a, uint32_t nwg, const DenseView& d, void* gsum,
+                                  const unsigned long long* owner, const Ovf& o, uint32_t epoch, const RowShape& rs,
+                                  hipStream_t st) {
+  if (nwg == 0) return hipSuccess;
+  if (!fm_step_args_ok(a, nwg)) return hipErrorInvalidValue;
+  const uint32_t grid = row_grid(nwg);
+  uint32_t* err = &o.c->stat[1];
+  return with_float_type(dtype, [&](auto z) {
+    using T = decltype(z);
+    if (a.weights)
+      k_row_fm_step_losers<T, true><<<grid, kBlock, 0, st>>>(a, d, static_cast<T*>(gsum), owner, err, epoch, rs);
+    else
+      k_row_fm_step_losers<T, false><<<grid, kBlock, 0, st>>>(a, d, static_cast<T*>(gsum), owner, err, epoch, rs);
+  });
+}
+
+hipError_t launch_row_step_apply(int dtype, int kind, const FmPushArgs& a, uint32_t nwg, const DenseView& d, void* gsum,
+                                 void* const state[2], const unsigned long long* owner, uint32_t epoch,
+                                 const RowShape& rs, const OptArgs<double>& hy, hipStream_t st) {
+  if (nwg == 0) return hipSuccess;
+  if (!fm_step_args_ok(a, nwg) || !opt_kind_ok(kind, state)) return hipErrorInvalidValue;
+  const uint32_t grid = row_grid(nwg);
+  return with_float_type(dtype, [&](auto z) {
+    using T = decltype(z);
+    const OptArgs<T> o = round_opt_args<T>(hy);
+    T* g = static_cast<T*>(gsum);
+    T* s1 = static_cast<T*>(state[0]);
+    T* s2 = static_cast<T*>(state[1]);
+    with_opt_kind(kind, [&](auto k) {
+      with_opt_unit<T>(rs, [&](auto v) {
+        constexpr int K = decltype(k)::value;
+        constexpr int V = decltype(v)::value;
+        if (a.weights)
+          k_row_fm_step_apply<T, K, V, true><<<grid, kBlock, 0, st>>>(a, d, g, s1, s2, owner, epoch, rs, o);
+        else
+          k_row_fm_step_apply<T, K, V, false><<<grid, kBlock, 0, st>>>(a, d, g, s1, s2, owner, epoch, rs, o);
+      });
+    });
   });
 }
 

@@ -285,6 +285,12 @@ struct pskv_shard {
   // the K5 scratch: a steady workload allocates nothing)
   void* pool_part = nullptr;
   size_t pool_part_bytes = 0;
+  // FM pooled calls, by the same policy: the partial Q rows of a pull's long
+  // bags, and a push's bag rows (phase 1)
+  void* fm_part_q = nullptr;
+  size_t fm_part_q_bytes = 0;
+  void* fm_bag_rows = nullptr;
+  size_t fm_bag_rows_bytes = 0;
   int general_path = 1;  // PSKV_GENERAL: stamps = 0 (K4 always), auto = 1, radix = 2 (K5 always)
   // tuning knobs (environment, read at creation): PSKV_TILE_SHIFT, PSKV_TILE_GRID
   uint32_t tune_tile_shift = 0;
@@ -2169,10 +2175,11 @@ int sparse_autogrow(pskv_shard* s, uint64_t n) {
 // as the mark takes them (keys and n; vals: where the kernels read the batch's
 // rows), `spans` their launch groups; args_of(mark group, span): the argument
 // block of a group's loser and apply passes (GroupArgs, PoolPushArgs or
-// PoolGroupArgs, pskv_internal.h).
-template <typename Args, typename ArgsOf>
+// PoolGroupArgs, pskv_internal.h; FmPushArgs).  first(): launches of the same
+// operation in front of the stamps (an FM push's bag rows), PSKV_OK or the failure.
+template <typename Args, typename ArgsOf, typename First>
 int step_device(pskv_shard* s, const std::vector<pskv_batch>& marks, const std::vector<Span>& spans,
-                const ArgsOf& args_of) {
+                const ArgsOf& args_of, const First& first) {
   if (int rc = ensure_owner(s)) return rc;
   // 16-byte units for the whole call or for none of it
   const bool vec = rows_unit16(s, {s->dense, s->opt_gsum, s->opt_slot[0], s->opt_slot[1]}, marks);
@@ -2200,6 +2207,7 @@ int step_device(pskv_shard* s, const std::vector<pskv_batch>& marks, const std::
   const RowShape rsv = row_shape(s->width, s->vb, vec);
   LaunchTimer t(s, kTimeApply, elems);
   t.count = groups.size();
+  if (int rc = first()) return rc;
   for (const Group& g : groups)
     PSKV_HIP(launch_general_mark(s->dtype, PSKV_ASSIGN, g.mark.ga, g.mark.nwg, s->dview(), s->flag + 1, s->owner,
                                  nullptr, g.epoch, s->stream));
@@ -2212,6 +2220,12 @@ int step_device(pskv_shard* s, const std::vector<pskv_batch>& marks, const std::
   t.done();
   s->n_general += 3 * groups.size();
   return PSKV_OK;
+}
+
+template <typename Args, typename ArgsOf>
+int step_device(pskv_shard* s, const std::vector<pskv_batch>& marks, const std::vector<Span>& spans,
+                const ArgsOf& args_of) {
+  return step_device<Args>(s, marks, spans, args_of, [] { return PSKV_OK; });
 }
 
 int apply_device(pskv_shard* s, const std::vector<pskv_batch>& v) {
@@ -2295,6 +2309,141 @@ int apply_pooled_grouped_impl(pskv_shard* s, const pskv_pool_batch* batches, uin
   std::vector<pskv_pool_batch> v;
   if (int rc = pool_front(s, live, &index, flags, pooled_push_front("pskv_apply_pooled_grouped"), hold, &v)) return rc;
   return apply_pooled_grouped_device(s, v);
+}
+
+// ------------------------------------ factorization-machine pooled calls
+// pskv_get_pooled_fm / pskv_apply_pooled_fm (pskv.h "Factorization-machine
+// pooled calls").  Both go through pool_front.  A host call has
+// one array more than the pooled layout holds (the pull's pairs, the push's
+// bag scales): room for it is reserved behind the layout before the front
+// stages the rest, so it lies at offset `total` of both stagings.
+const char* fm_refusal(const pskv_shard* s) {
+  return (s->dtype != PSKV_F32 && s->dtype != PSKV_F64) ? ": float shards only" : nullptr;
+}
+
+// The staging of a host call with `extra` bytes behind the pooled layout of
+// `call`; *at: where they begin.  Selects the device and ends the server, as
+// pool_front does again (both then find nothing to do).
+int fm_reserve_stage(pskv_shard* s, const pskv_pool_batch& call, size_t extra, size_t* at) {
+  int rc = use_device(s);
+  if (rc || (rc = srv_stop(s))) return rc;
+  *at = pool_stage_layout({call}, (size_t)s->vb, row_bytes(s)).total;
+  if ((rc = ensure_hstage(s, *at + round16(extra)))) return rc;
+  return ensure_dstage(s, *at + round16(extra));
+}
+
+// unit16 of an FM launch: a function of the width alone (the shard's arrays
+// and scratches are allocations, so aligned), never of the caller's pointers.
+RowShape fm_row_shape(const pskv_shard* s, std::initializer_list<const void*> arrays) {
+  bool unit16 = row_bytes(s) % 16 == 0;
+  for (const void* p : arrays) unit16 = unit16 && aligned16(p);
+  return row_shape(s->width, s->vb, unit16);
+}
+
+// The pull, one timed operation (kTimePooled): the chunks of long bags (S and
+// Q rows), then every bag.  `c`: the call as the kernels read it, bag_grads
+// the room of its sum rows or null.
+int pooled_fm_device(pskv_shard* s, const pskv_pool_batch& c, void* pair) {
+  void* out = const_cast<void*>(c.bag_grads);
+  FmPoolArgs a{c.keys, c.weights, c.offsets, c.n, c.nbags, out, pair, nullptr, nullptr, nullptr, nullptr, aligned16(out)};
+  if (c.n > kPoolChunk) {
+    const size_t bytes = pool_slots(c.n) * row_bytes(s);
+    int rc = ensure_scratch(s, &s->pool_part, &s->pool_part_bytes, bytes);
+    if (rc || (rc = ensure_scratch(s, &s->fm_part_q, &s->fm_part_q_bytes, bytes))) return rc;
+    a.part = s->pool_part;
+    a.part_q = s->fm_part_q;
+  }
+  const RowShape rs = fm_row_shape(s, {s->dense, a.part, a.part_q});
+  LaunchTimer t(s, kTimePooled, c.n);
+  PSKV_HIP(launch_row_fm_pooled_chunks(s->dtype, a, s->read_view(s->dense), s->ovf, rs, s->stream));
+  PSKV_HIP(launch_row_fm_pooled(s->dtype, a, s->read_view(s->dense), s->ovf, rs, s->stream));
+  t.done();
+  return PSKV_OK;
+}
+
+// The arguments hold (pskv_get_pooled_fm checked them).  call.bag_grads: out_sum or null.
+int pooled_fm_impl(pskv_shard* s, const pskv_pool_batch& call, void* out_pair, int flags) {
+  if (const char* why = fm_refusal(s)) return fail(PSKV_EINVAL, std::string("pskv_get_pooled_fm") + why);
+  ++s->n_get;
+  if (call.nbags == 0) return PSKV_OK;
+  const bool host = !(flags & PSKV_DEVICE);
+  const size_t pair_bytes = call.nbags * (size_t)s->vb;
+  HstageHold hold(s);
+  size_t pair_at = 0;
+  int rc = host ? fm_reserve_stage(s, call, pair_bytes, &pair_at) : PSKV_OK;
+  if (rc) return rc;
+  std::vector<pskv_pool_batch> v;
+  rc = pool_front(s, {call}, nullptr, flags,
+                  PoolFront{"pskv_get_pooled_fm", /*writing=*/false, /*with_rows=*/false,
+                            "a pooled pull reads the dense array only; the outputs are untouched"},
+                  hold, &v);
+  if (rc) return rc;
+  if (!call.bag_grads) v[0].bag_grads = nullptr;
+  if (!host) return pooled_fm_device(s, v[0], out_pair);
+  char* d = static_cast<char*>(s->dstage);
+  char* h = static_cast<char*>(s->hstage);
+  if ((rc = pooled_fm_device(s, v[0], d + pair_at))) return rc;
+  // the sum rows end where the pairs begin: one copy back for both
+  const size_t sum_bytes = call.nbags * row_bytes(s);
+  const size_t at = call.bag_grads ? pair_at - round16(sum_bytes) : pair_at;
+  std::vector<Piece> back;
+  if (call.bag_grads) add_pieces(back, h + at, static_cast<char*>(const_cast<void*>(call.bag_grads)), sum_bytes, -1);
+  add_pieces(back, h + pair_at, static_cast<char*>(out_pair), pair_bytes, -1);
+  return rows_to_host(s, hold, at, pair_at + pair_bytes - at, "shard stream (FM pooled pull to host)", back);
+}
+
+// The push: step_device over an FmPushArgs whose rows are the bag rows t_b,
+// computed from the pre-step parameters in front of the stamps (a long bag's
+// partial sums by the pooled pull's own chunk pass).  Stream order is what
+// keeps every read of a parameter row in front of its one write: DESIGN.md §8p.
+// `c`: the call as the kernels read it, bag_grads null when the call has none.
+int apply_pooled_fm_device(pskv_shard* s, const pskv_pool_batch& c, const void* scale) {
+  if (int rc = ensure_scratch(s, &s->fm_bag_rows, &s->fm_bag_rows_bytes, c.nbags * row_bytes(s))) return rc;
+  FmPoolArgs a{c.keys, c.weights, c.offsets, c.n, c.nbags, s->fm_bag_rows, nullptr, nullptr, nullptr, scale, c.bag_grads, 1};
+  if (c.n > kPoolChunk) {
+    if (int rc = ensure_scratch(s, &s->pool_part, &s->pool_part_bytes, pool_slots(c.n) * row_bytes(s))) return rc;
+    a.part = s->pool_part;
+  }
+  const RowShape rs = fm_row_shape(s, {s->dense, a.part, a.bag_grads});
+  const std::vector<pskv_batch> marks{pskv_batch{c.keys, s->fm_bag_rows, c.n}};
+  return step_device<FmPushArgs>(
+      s, marks, {Span{0, 1}},
+      [&](const LaunchGroup&, const Span&) {
+        return FmPushArgs{c.keys, c.weights, c.offsets, c.n, c.nbags, s->fm_bag_rows, scale};
+      },
+      [&] {
+        const PoolArgs chunks{c.keys, c.weights, c.offsets, c.n, c.nbags, nullptr, a.part};
+        PSKV_HIP(launch_row_pooled_chunks(s->dtype, chunks, s->dview(), s->ovf, rs, s->stream));
+        PSKV_HIP(launch_row_fm_bag_rows(s->dtype, a, s->dview(), s->ovf, rs, s->stream));
+        return (int)PSKV_OK;
+      });
+}
+
+// The arguments hold (pskv_apply_pooled_fm checked them).  call.bag_grads: null when the call has none.
+int apply_pooled_fm_impl(pskv_shard* s, const pskv_pool_batch& call, const void* bag_scale, int flags) {
+  if (const char* why = pooled_step_refusal(s)) return fail(PSKV_EINVAL, std::string("pskv_apply_pooled_fm") + why);
+  if (call.n == 0 || call.nbags == 0) return PSKV_OK;  // no key, or no bag: no step
+  const bool host = !(flags & PSKV_DEVICE);
+  const size_t scale_bytes = call.nbags * (size_t)s->vb;
+  HstageHold hold(s);  // a host call returns before its DMA: the hold stays armed
+  size_t scale_at = 0;
+  if (host)
+    if (int rc = fm_reserve_stage(s, call, scale_bytes, &scale_at)) return rc;
+  std::vector<pskv_pool_batch> v;
+  PoolFront front = pooled_push_front("pskv_apply_pooled_fm");
+  front.with_rows = call.bag_grads != nullptr;
+  if (int rc = pool_front(s, {call}, nullptr, flags, front, hold, &v)) return rc;
+  if (!call.bag_grads) v[0].bag_grads = nullptr;
+  const void* scale = bag_scale;
+  if (host) {
+    char* h = static_cast<char*>(s->hstage) + scale_at;
+    char* d = static_cast<char*>(s->dstage) + scale_at;
+    std::memcpy(h, bag_scale, scale_bytes);
+    PSKV_HIP(hipMemcpyAsync(d, h, scale_bytes, hipMemcpyHostToDevice, s->stream));
+    hold.arm();
+    scale = d;
+  }
+  return apply_pooled_fm_device(s, v[0], scale);
 }
 
 // What is wrong with a configuration, or null (checked before any handle;
@@ -3157,6 +3306,8 @@ int pskv_shard_destroy(pskv_shard* s) {
   if (s->rb_loff) (void)hipFree(s->rb_loff);
   if (s->rb_ent) (void)hipFree(s->rb_ent);
   if (s->pool_part) (void)hipFree(s->pool_part);
+  if (s->fm_part_q) (void)hipFree(s->fm_part_q);
+  if (s->fm_bag_rows) (void)hipFree(s->fm_bag_rows);
   if (s->sp_table) (void)hipFree(s->sp_table);
   if (s->sp_slot_keys) (void)hipFree(s->sp_slot_keys);
   if (s->sp_ids) (void)hipFree(s->sp_ids);
@@ -3317,11 +3468,13 @@ int pskv_apply_grouped(pskv_shard* s, const pskv_batch* batches, uint64_t nb, in
 
 // What is wrong with a pooled push's batch, or "": pointers, the size limit
 // (`one`: what a batch of at most 2^31 keys is to the call) and a host call's
-// offsets, in that order.  who: the call, and in a grouped one the batch.
-static std::string pool_batch_error(const std::string& who, const pskv_pool_batch& b, int flags, const char* one) {
+// offsets, in that order.  who: the call, and in a grouped one the batch;
+// rows: the name of the array in bag_grads' place.
+static std::string pool_batch_error(const std::string& who, const pskv_pool_batch& b, int flags, const char* one,
+                                    const char* rows = "bag_grads") {
   if (b.n && !b.keys) return who + "null keys with n > 0";
   if (b.nbags && !b.offsets) return who + "null offsets with nbags > 0";
-  if (b.nbags && !b.bag_grads) return who + "null bag_grads with nbags > 0";
+  if (b.nbags && !b.bag_grads) return who + "null " + rows + " with nbags > 0";
   if (b.n > kMaxPiece) return who + "n = " + std::to_string(b.n) + " exceeds 2^31 keys (" + one + ")";
   if (!(flags & PSKV_DEVICE)) {
     uint64_t bad = 0;
@@ -3342,6 +3495,37 @@ int pskv_apply_pooled(pskv_shard* s, const uint32_t* keys, uint64_t n, const voi
   if (!err.empty()) return fail(PSKV_EINVAL, err);
   if (!s) return fail(PSKV_EINVAL, "pskv_apply_pooled: null shard");
   return apply_pooled_impl(s, b, flags);
+}
+
+// pskv_get_pooled's checks in its order, with out_pair in the place of out (out_sum may be null).
+int pskv_get_pooled_fm(pskv_shard* s, const uint32_t* keys, uint64_t n, const void* weights, const uint64_t* offsets,
+                       uint64_t nbags, void* out_sum, void* out_pair, int flags) {
+  if (bad_flags(flags)) return fail(PSKV_EINVAL, "pskv_get_pooled_fm: unknown flags");
+  if (n && !keys) return fail(PSKV_EINVAL, "pskv_get_pooled_fm: null keys with n > 0");
+  if (nbags && !offsets) return fail(PSKV_EINVAL, "pskv_get_pooled_fm: null offsets with nbags > 0");
+  if (nbags && !out_pair) return fail(PSKV_EINVAL, "pskv_get_pooled_fm: null out_pair with nbags > 0");
+  if (!(flags & PSKV_DEVICE)) {
+    uint64_t bad = 0;
+    if (const char* why = pool_offsets_error(offsets, nbags, n, &bad))
+      return fail(PSKV_EINVAL, "pskv_get_pooled_fm: offsets: bag " + std::to_string(bad) + ": " + why + " (n = " +
+                                   std::to_string(n) + ", nbags = " + std::to_string(nbags) + ")");
+  }
+  if (!s) return fail(PSKV_EINVAL, "pskv_get_pooled_fm: null shard");
+  return pooled_fm_impl(s, pskv_pool_batch{keys, weights, offsets, out_sum, n, nbags}, out_pair, flags);
+}
+
+// pskv_apply_pooled's checks (pool_batch_error) with bag_scale in the place of
+// bag_grads, which may be null.
+int pskv_apply_pooled_fm(pskv_shard* s, const uint32_t* keys, uint64_t n, const void* weights,
+                         const uint64_t* offsets, uint64_t nbags, const void* bag_scale, const void* bag_grads,
+                         int flags) {
+  if (bad_flags(flags)) return fail(PSKV_EINVAL, "pskv_apply_pooled_fm: unknown flags");
+  const std::string err =
+      pool_batch_error("pskv_apply_pooled_fm: ", pskv_pool_batch{keys, weights, offsets, bag_scale, n, nbags}, flags,
+                       "an FM pooled push is one launch group", "bag_scale");
+  if (!err.empty()) return fail(PSKV_EINVAL, err);
+  if (!s) return fail(PSKV_EINVAL, "pskv_apply_pooled_fm: null shard");
+  return apply_pooled_fm_impl(s, pskv_pool_batch{keys, weights, offsets, bag_grads, n, nbags}, bag_scale, flags);
 }
 
 // Every batch gets pskv_apply_pooled's checks, before the handle is looked at;

@@ -413,6 +413,87 @@ class Shard:
         check(lib.pskv_apply_pooled_grouped(self._h, arr, len(batches), flags))
         del keep
 
+    def _bag_values(self, who, name, x, count, device):
+        """`x` as `count` values of the shard's dtype where the call's keys are
+        (a tensor of the shard's device, or a numpy array); None stays None.
+        Returns (pointer, the array behind it)."""
+        if x is None:
+            return None, None
+        if device:
+            if x.dtype != _torch_dtype(self.dtype) or x.numel() != count:
+                raise ValueError(f"{who}: {name} must hold {count} values of the shard's dtype")
+            self._check_dev(x)
+            return x.data_ptr(), x
+        a = np.ascontiguousarray(x, dtype=self.dtype)
+        if a.size != count:
+            raise ValueError(f"{who}: {a.size} {name} values, {count} expected")
+        return a.ctypes.data, a
+
+    def get_pooled_fm(self, keys, offsets, weights=None, want_sum=True):
+        """The pooled sum and the factorization-machine pair term of every bag
+        (pskv_get_pooled_fm): pair[b] = 0.5 * sum_j((sum_i x_ij)^2 - sum_i
+        x_ij^2), x_i = weights[i] * row(keys[i]).  Arguments as get_pooled's.
+        Returns (sum, pair): sum as get_pooled returns it, or None when
+        want_sum is false; pair holds nbags values."""
+        dev = _is_torch(keys)
+        if dev:
+            import torch
+
+            if offsets.dtype != torch.int64 or offsets.numel() < 1:
+                raise ValueError("get_pooled_fm: device offsets must be an int64 tensor of nbags + 1 values")
+            self._check_dev(keys, offsets)
+            nbags = offsets.numel() - 1
+            shape = (nbags, self.width) if self.width > 1 else nbags
+            tdt = _torch_dtype(self.dtype)
+            out = torch.empty(shape, dtype=tdt, device=keys.device) if want_sum else None
+            pair = torch.empty(nbags, dtype=tdt, device=keys.device)
+            pk, n, po, ps, pp = keys.data_ptr(), keys.numel(), offsets.data_ptr(), out.data_ptr() if want_sum else None, \
+                pair.data_ptr()
+            flags = _lib.PSKV_DEVICE
+        else:
+            k = self._host_keys(keys)
+            off = np.ascontiguousarray(offsets, dtype=np.uint64)
+            if off.size < 1:
+                raise ValueError("get_pooled_fm: offsets must hold nbags + 1 values")
+            nbags = off.size - 1
+            out = np.empty((nbags, self.width) if self.width > 1 else nbags, dtype=self.dtype) if want_sum else None
+            pair = np.empty(nbags, dtype=self.dtype)
+            pk, n, po, ps, pp = k.ctypes.data, k.size, off.ctypes.data, out.ctypes.data if want_sum else None, \
+                pair.ctypes.data
+            flags = _lib.PSKV_HOST
+        pw, w = self._bag_values("get_pooled_fm", "weights", weights, n, dev)
+        check(lib.pskv_get_pooled_fm(self._h, pk, n, pw, po, nbags, ps, pp, flags))
+        del w
+        return out, pair
+
+    def apply_pooled_fm(self, keys, offsets, bag_scale, weights=None, bag_grads=None):
+        """One optimizer step that is the backward pass of get_pooled_fm
+        (pskv_apply_pooled_fm): bag_scale[b] = dL/dpair_b (nbags values),
+        bag_grads[b] = dL/dsum_b (nbags * width values) or None.  The gradient
+        row of keys[i] is w_i * (c_b * S_b + bag_grads[b]) - c_b * w_i^2 *
+        row(keys[i]), S_b and every row as they are before the step.  numpy ->
+        host path; torch tensors -> device path, stream-ordered."""
+        dev = _is_torch(keys)
+        if dev:
+            import torch
+
+            if offsets.dtype != torch.int64 or offsets.numel() < 1:
+                raise ValueError("apply_pooled_fm: device offsets must be an int64 tensor of nbags + 1 values")
+            self._check_dev(keys, offsets)
+            pk, n, po, nbags, flags = keys.data_ptr(), keys.numel(), offsets.data_ptr(), offsets.numel() - 1, \
+                _lib.PSKV_DEVICE
+        else:
+            k = self._host_keys(keys)
+            off = np.ascontiguousarray(offsets, dtype=np.uint64)
+            if off.size < 1:
+                raise ValueError("apply_pooled_fm: offsets must hold nbags + 1 values")
+            pk, n, po, nbags, flags = k.ctypes.data, k.size, off.ctypes.data, off.size - 1, _lib.PSKV_HOST
+        pw, w = self._bag_values("apply_pooled_fm", "weights", weights, n, dev)
+        pc, c = self._bag_values("apply_pooled_fm", "bag_scale", bag_scale, nbags, dev)
+        pg, g = self._bag_values("apply_pooled_fm", "bag_grads", bag_grads, nbags * self.width, dev)
+        check(lib.pskv_apply_pooled_fm(self._h, pk, n, pw, po, nbags, pc, pg, flags))
+        del w, c, g
+
     def get_state(self, keys, out=None, slot: int = 0):
         """The rows of `keys` in state slot `slot` (pskv_get_state_slot; Adagrad
         h, momentum v, Adam m and v, FTRL z and n), as get returns values."""
