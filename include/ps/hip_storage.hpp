@@ -327,6 +327,23 @@ class HipStorage : public AbstractStorage {
     pskv_check(pskv_sparse_erase(shard_, typed_keys.data(), typed_keys.size(), PSKV_HOST), "pskv_sparse_erase");
   }
 
+  // Row initializers (pskv.h "Row initializers"; not part of AbstractStorage).
+  // SetInitializer: what a never-written row holds (kind: PSKV_INIT_*); acts as
+  // a clear under the new rule, so it is called once, before the first push.
+  // SubGetInit: init(key) of every key as a frame of keys * width values -- the
+  // worker-side "a stored 0 reads as 0.01" of the reference's MF app is
+  // SetInitializer(PSKV_INIT_CONSTANT, 0.01) and this call.
+  void SetInitializer(int kind, double a = 0.0, double b = 0.0, uint64_t seed = 0) {
+    const pskv_initializer cfg{kind, seed, a, b};
+    pskv_check(pskv_shard_set_initializer(shard_, &cfg), "pskv_shard_set_initializer");
+  }
+  third_party::SArray<char> SubGetInit(const third_party::SArray<Key>& typed_keys) {
+    auto reply_vals = FrameArray<Val>(typed_keys.size() * width_);
+    pskv_check(pskv_get_init(shard_, typed_keys.data(), typed_keys.size(), reply_vals.data(), PSKV_HOST),
+               "pskv_get_init");
+    return third_party::SArray<char>(reply_vals);
+  }
+
   // The reference's FinishIter is a no-op (map_storage.hpp:47); here it is the
   // point where deferred device errors surface and the overflow table, which
   // grows on the device as keys arrive, is trimmed and its old arrays freed.

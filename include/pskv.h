@@ -491,6 +491,64 @@
  *     scalar fast path (the resident request server and inline messages serve
  *     scalar range shards only).
  *
+ * Row initializers (pskv_shard_set_initializer): the value of a
+ * row that has never been written.  Without one (PSKV_INIT_ZERO, the default)
+ * it is a row of zeros, bit for bit and launch for launch what the sections
+ * above describe.  With one it is init(key): a pure function of (seed, key,
+ * element index, dtype, kind, a, b) -- never of the slot, the capacity, the
+ * insertion order, the width (a row of width 8 is the prefix of the same key's
+ * row of width 16), the call path or the shard that holds the key; a table
+ * partitioned again over more servers initialises identically, and an erased
+ * key comes back with the bits it first had.
+ *   - the value of element e of key k, in T = float or double: with per =
+ *     16 / sizeof(T), q = e / per, r = e % per and x[0..3] = Philox4x32-10 of
+ *     counter (k, q, 0, 0) under key (seed low word, seed high word):
+ *       CONSTANT  (T)a
+ *       UNIFORM   rounded(u * d) + lo, lo = (T)a, d = (T)(b - a) (the
+ *                 subtraction in double); two roundings in T, never an fma;
+ *                 float: u = (x[r] >> 8) * 2^-24; double: u = ((x[2r] >> 5) *
+ *                 2^26 + (x[2r+1] >> 6)) * 2^-53, both exact and in [0, 1)
+ *       NORMAL    (T)(a + b * z), Box-Muller in double for BOTH value types:
+ *                 z = rad * cos(ang) for even r, rad * sin(ang) for odd r, rad =
+ *                 sqrt(-2 log u1), ang = 2 pi u2; float: h = r / 2, u1 =
+ *                 ((x[2h] >> 8) + 1) * 2^-24, u2 = (x[2h+1] >> 8) * 2^-24;
+ *                 double: u1 = u(x[0], x[1]) + 2^-53, u2 = u(x[2], x[3]).  Every
+ *                 product is rounded on its own.  CONSTANT and UNIFORM are
+ *                 bit-exact everywhere; NORMAL moves by the device library's
+ *                 log, sin and cos in double, for a float shard at most where
+ *                 the one final rounding falls;
+ *   - pskv_shard_set_initializer: checked before the handle, each PSKV_EINVAL
+ *     naming its argument: a null cfg, kind out of range, a or b not finite,
+ *     UNIFORM with a > b, NORMAL with b < 0.  Then: legal on row shards
+ *     (pskv_shard_create_rows, any width, 1 included) and sparse shards of
+ *     float or double; PSKV_I32, a scalar range shard (pskv_shard_create,
+ *     pskv_shard_create_ex) or a value not finite in T ((T)a, (T)b, UNIFORM's
+ *     (T)(b - a)) is PSKV_EINVAL naming the argument.  It records the rule and
+ *     then acts as pskv_clear under it: stream-ordered, returns when done, ends
+ *     the request server first.  A creation-time call.  A row shard's keys
+ *     outside its range (width 1: the overflow table) are not covered;
+ *   - pskv_clear resets to the rule: a row shard holds init(key) in every row
+ *     (key_begin + row, not the row index); a sparse shard is emptied.  State
+ *     and step counter as before;
+ *   - sparse shards: a key inserted by any writing call of the list above
+ *     starts as init(key), filled before anything of that call reads or writes
+ *     the row; its optimizer state is the start state.  By relabelling the
+ *     shard returns what its row-shard twin returns when the twin's row rank(k)
+ *     was assigned init(k) beforehand: an accumulate Add gives init + v, an FM
+ *     push's S_b sees init rows for new keys.  A key dropped at a full shard
+ *     gets nothing; reserve and growth keep every row; an erased key comes back
+ *     as init(key).  Reading calls are unchanged: they never insert and an
+ *     absent key reads zeros.  The fill is part of the call's index operation
+ *     (PSKV_TIME_INDEX) and waits for nothing on the host;
+ *   - pskv_get_init(keys, n, out, flags) is the read side: row i of out =
+ *     init(keys[i]) (zeros under PSKV_INIT_ZERO), nothing in the shard is
+ *     touched, no key is refused, n == 0 is PSKV_OK.  PSKV_HOST (synchronous, as
+ *     a host pull) or PSKV_DEVICE (stream-ordered).  Checked before the handle:
+ *     unknown flags, null keys or out with n > 0;
+ *   - not provided: reads that insert or that return init for absent keys
+ *     inside pooled sums; truncated normal, per-column scales; int32; the
+ *     initializer inside a saved state (callers set it again after a restore).
+ *
  * Threading: one shard handle is used by one host thread at a time (the
  * reference calls a storage only from its ServerThread, server_thread.cpp:20-50);
  * distinct handles may be used concurrently.  Every call selects the shard's
@@ -648,6 +706,17 @@ int pskv_sparse_get_growth(pskv_shard* s, uint64_t* max_capacity, uint64_t* rebu
  * are freed, their rows and optimizer state are gone.  A maintenance call whose
  * cost follows the keys stored; returns when done. */
 int pskv_sparse_erase(pskv_shard* s, const uint32_t* keys, uint64_t n, int flags);
+/* Row initializers (semantics: the header comment, "Row initializers"). */
+#define PSKV_INIT_ZERO     0   /* default: rows start as zeros */
+#define PSKV_INIT_CONSTANT 1   /* every element (T)a */
+#define PSKV_INIT_UNIFORM  2   /* lo = a, hi = b */
+#define PSKV_INIT_NORMAL   3   /* mean = a, std = b */
+typedef struct { int kind; uint64_t seed; double a; double b; } pskv_initializer;
+/* Record the rule, then act as pskv_clear under it; returns when done. */
+int pskv_shard_set_initializer(pskv_shard* s, const pskv_initializer* cfg);
+int pskv_shard_get_initializer(pskv_shard* s, pskv_initializer* out);
+/* out row i = init(keys[i]); touches nothing in the shard. */
+int pskv_get_init(pskv_shard* s, const uint32_t* keys, uint64_t n, void* out, int flags);
 int pskv_shard_destroy(pskv_shard* s);
 
 /* Push: apply n (key, value) pairs.  Asynchronous on the shard's stream for

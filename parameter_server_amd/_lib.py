@@ -48,6 +48,7 @@ PSKV_TIME_INDEX = 1 << 16
 PSKV_OPT_NONE, PSKV_OPT_SGD, PSKV_OPT_ADAGRAD = 0, 1, 2
 PSKV_OPT_MOMENTUM, PSKV_OPT_ADAM = 3, 4  # only through pskv_shard_set_optimizer_ex
 PSKV_OPT_FTRL = 5  # only through pskv_shard_set_optimizer_cfg
+PSKV_INIT_ZERO, PSKV_INIT_CONSTANT, PSKV_INIT_UNIFORM, PSKV_INIT_NORMAL = 0, 1, 2, 3
 KERNEL_NAMES = {
     PSKV_K_GATHER: "k_gather",
     PSKV_K_ASSIGN_SORTED: "k_assign_sorted",
@@ -84,6 +85,7 @@ EXPORTED = [
     "pskv_shard_create_sparse", "pskv_sparse_info_get", "pskv_sparse_keys", "pskv_index_time",
     "pskv_sparse_reserve", "pskv_sparse_set_growth", "pskv_sparse_get_growth", "pskv_sparse_erase",
     "pskv_get_pooled_fm", "pskv_apply_pooled_fm",
+    "pskv_shard_set_initializer", "pskv_shard_get_initializer", "pskv_get_init",
 ]
 
 
@@ -128,6 +130,10 @@ class PskvOptimizerCfg(ctypes.Structure):
     # the first 72 bytes are PskvOptimizerEx's
     _fields_ = PskvOptimizerEx._fields_ + [("l1", ctypes.c_double), ("l2", ctypes.c_double),
                                            ("ftrl_beta", ctypes.c_double)]
+
+
+class PskvInitializer(ctypes.Structure):
+    _fields_ = [("kind", ctypes.c_int), ("seed", ctypes.c_uint64), ("a", ctypes.c_double), ("b", ctypes.c_double)]
 
 
 class PskvError(RuntimeError):
@@ -203,6 +209,9 @@ def _load():
         "pskv_sparse_set_growth": ([vp, u64], i32),
         "pskv_sparse_get_growth": ([vp, ctypes.POINTER(u64), ctypes.POINTER(u64)], i32),
         "pskv_sparse_erase": ([vp, vp, u64, i32], i32),
+        "pskv_shard_set_initializer": ([vp, ctypes.POINTER(PskvInitializer)], i32),
+        "pskv_shard_get_initializer": ([vp, ctypes.POINTER(PskvInitializer)], i32),
+        "pskv_get_init": ([vp, vp, u64, vp, i32], i32),
         "pskv_index_time": ([vp, ctypes.POINTER(u64), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(u64)], i32),
     }
     for name, (args, res) in sig.items():

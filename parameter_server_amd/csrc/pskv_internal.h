@@ -460,4 +460,53 @@ hipError_t launch_index_mark_dead(const uint32_t* ids, uint64_t n, uint32_t capa
 hipError_t launch_index_rebuild(const uint32_t* old_keys, uint32_t count, const uint8_t* dead, const SparseIndex& x,
                                 uint32_t* survivors, hipStream_t st);
 
+// Row initializers (pskv_init.hip; pskv.h "Row initializers"):
+// the value of a row that was never written, a function of (seed, key, element,
+// dtype, kind, a, b) alone.  kind: PSKV_INIT_CONSTANT / UNIFORM / NORMAL (never
+// ZERO: a ZERO shard launches none of these); a, b as pskv_initializer's.
+struct InitRule {
+  int kind;
+  uint32_t seed_lo, seed_hi;
+  double a, b;
+};
+// param[row] = init(key_begin + row) for rows [0, rows) of a dense row shard of
+// `width` values per row (float or double by dtype).
+hipError_t launch_row_init_range(int dtype, const InitRule& r, void* param, uint32_t key_begin, uint64_t rows,
+                                 uint32_t width, hipStream_t st);
+// Behind launch_index_insert in stream order: param[slot] = init(x.slot_keys[slot])
+// for the slots handed out since the last fill, [*mark, min(x.stat[0],
+// x.capacity)), after which *mark is that end.  mark: two device words of the
+// shard, {mark, ticket}, the ticket zero between launches.  n: the key
+// positions of the call (a bound on the new slots; it sizes the grid).
+hipError_t launch_row_init_new(int dtype, const InitRule& r, void* param, const SparseIndex& x, uint32_t* mark,
+                               uint32_t width, uint64_t n, hipStream_t st);
+// out row i = init(keys[i]), i < n.
+hipError_t launch_init_eval(int dtype, const InitRule& r, const uint32_t* keys, uint64_t n, void* out, uint32_t width,
+                            hipStream_t st);
+
+#ifdef __HIPCC__
+// One multiplication rounded to T: the empty statement keeps the product out
+// of a contraction with the addition that follows, so a weighted term is the
+// same value in gsum, in a winner's step and in a host-expanded pskv_apply.
+__device__ __forceinline__ float rounded_mul(float w, float x) {
+  float r = w * x;
+  asm("" : "+v"(r));
+  return r;
+}
+__device__ __forceinline__ double rounded_mul(double w, double x) {
+  double r = w * x;
+  asm("" : "+v"(r));
+  return r;
+}
+// x with its rounding kept apart from whatever reads it (rounded_mul's device).
+template <typename T>
+__device__ __forceinline__ T rounded(T x) {
+  asm("" : "+v"(x));
+  return x;
+}
+// A kernel compiled without the packed-float instructions (v_pk_add_f32,
+// v_pk_mul_f32, v_pk_fma_f32): every float operation is a scalar VALU instruction.
+#define PSKV_NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
+#endif
+
 }  // namespace pskv

@@ -280,19 +280,7 @@ __device__ __forceinline__ void store_opt_unit(T* p, uint64_t unit, const OptUni
 __device__ __forceinline__ bool nonzero_bits(float x) { return __float_as_uint(x) != 0u; }
 __device__ __forceinline__ bool nonzero_bits(double x) { return __double_as_longlong(x) != 0ll; }
 
-// One multiplication rounded to T: the empty statement keeps the product out
-// of a contraction with the addition that follows, so a weighted term is the
-// same value in gsum, in a winner's step and in a host-expanded pskv_apply.
-__device__ __forceinline__ float rounded_mul(float w, float x) {
-  float r = w * x;
-  asm("" : "+v"(r));
-  return r;
-}
-__device__ __forceinline__ double rounded_mul(double w, double x) {
-  double r = w * x;
-  asm("" : "+v"(r));
-  return r;
-}
+// (rounded_mul, rounded and PSKV_NO_PK_F32: pskv_internal.h)
 
 // A wave-uniform value held in vector registers from here on (PIN), or left
 // to the compiler.
@@ -898,17 +886,7 @@ void launch_row_pooled_chunks_v(uint32_t grid, const PoolArgs& a, const DenseVie
 // fixed by the unit and L, both functions of the width (the unit does not
 // depend on where `out` lies: FmPoolArgs::out_unit16).
 
-// These kernels are compiled without the packed-float instructions
-// (v_pk_add_f32, v_pk_mul_f32, v_pk_fma_f32): every float operation is a scalar
-// VALU instruction.
-#define PSKV_NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
-
-// x with its rounding kept apart from whatever reads it (rounded_mul's device).
-template <typename T>
-__device__ __forceinline__ T rounded(T x) {
-  asm("" : "+v"(x));
-  return x;
-}
+// These kernels are compiled without the packed-float instructions (PSKV_NO_PK_F32).
 
 // pool_sum with the second chain: unit u of S (pool_sum's bits: the same
 // order, the same fma) and, PAIR, of Q = x_0 * x_0, then fma(x_i, x_i, Q),

@@ -413,6 +413,18 @@ struct pskv_shard {
   uint64_t sp_max_capacity = 0;
   uint64_t sp_bound = 0;
   uint64_t sp_rebuilds = 0;  // rebuilds of the index done (reserve, automatic growth, erase)
+  // The row initializer (pskv_shard_set_initializer): what a row
+  // holds before its first write.  scalar_api: made by pskv_shard_create[_ex],
+  // which takes none.  sp_mark: a sparse shard's {mark, ticket} device words:
+  // the slots below the mark hold their rows, those from it to the slot counter
+  // were handed out by the inserts queued since the last fill (k_row_init_new).
+  pskv_initializer init{};  // (kind 0: PSKV_INIT_ZERO)
+  bool scalar_api = false;
+  uint32_t* sp_mark = nullptr;
+  bool has_init() const { return init.kind != PSKV_INIT_ZERO; }
+  InitRule init_rule() const {
+    return InitRule{init.kind, (uint32_t)init.seed, (uint32_t)(init.seed >> 32), init.a, init.b};
+  }
   uint64_t rows_held() const { return range + (sparse ? 1u : 0u); }  // rows of every row-shaped array
   // The row-shaped arrays, described once: the parameters, the two state
   // slots, the gradient scratch.  `used`: the current kind has the array;
@@ -1694,7 +1706,8 @@ bool rows_unit16(const pskv_shard* s, std::initializer_list<const void*> arrays,
 // §8k): the keys of `v` (vals are not looked at) become slot ids, and each
 // batch's keys pointer is redirected to them.  writing: the call inserts
 // (k_index_insert over every launch group first, then the translate passes: a
-// key repeated across groups finds the one slot it got).  in_place: the keys lie
+// key repeated across groups finds the one slot it got; with an initializer,
+// k_row_init_new between the two fills the new slots' rows).  in_place: the keys lie
 // in the device staging (a host call) and are overwritten; else the ids go to
 // the shard's scratch and the caller's keys are only read.  The launches are
 // one timed operation (kTimeIndex), elements = the keys.
@@ -1729,6 +1742,9 @@ int sparse_ids(pskv_shard* s, std::vector<pskv_batch>& v, bool writing, bool in_
       const LaunchGroup g = make_group(io, sp.first, sp.second, kGeneralChunk);
       PSKV_HIP(launch_index_insert(g.ga, g.nwg, x, s->stream));
     }
+  // the rows of the keys just inserted, before anything of the call reads or writes them
+  if (writing && s->has_init())
+    PSKV_HIP(launch_row_init_new(s->dtype, s->init_rule(), s->dense, x, s->sp_mark, s->width, elems, s->stream));
   for (const Span& sp : spans) {
     const LaunchGroup g = make_group(io, sp.first, sp.second, kGeneralChunk);
     PSKV_HIP(launch_index_translate(writing, g.ga, g.nwg, x, s->stream));
@@ -1747,6 +1763,7 @@ struct RowFront {
   const char* refusal;   // a host call refuses an out-of-range key (null: it does not):
   const char* why;       //   what stands in front of and behind the key
   bool with_values;      // a host call stages its rows behind its keys (an Add's)
+  bool raw_keys = false; // the kernels read keys, not rows of the shard: a sparse shard translates nothing
 };
 struct RowCall {
   std::vector<pskv_batch> v;   // the call's pieces, where the caller has them (empty: nothing to do)
@@ -1789,7 +1806,8 @@ int rows_front(pskv_shard* s, const std::vector<pskv_batch>& in, int flags, cons
   }
   // a sparse shard: what the kernels read carries slot ids from here on (the
   // calls that bring values are the writing ones, and insert)
-  if (s->sparse) return sparse_ids(s, c->host ? c->dv : c->v, /*writing=*/f.with_values, /*in_place=*/c->host);
+  if (s->sparse && !f.raw_keys)
+    return sparse_ids(s, c->host ? c->dv : c->v, /*writing=*/f.with_values, /*in_place=*/c->host);
   return PSKV_OK;
 }
 
@@ -1868,13 +1886,28 @@ int rows_to_host(pskv_shard* s, HstageHold& hold, size_t at, size_t bytes, const
   return PSKV_OK;
 }
 
+// The rows of pskv_get_init: init(key) of every key, or zeros without a rule
+// (k_fill, not a memset: the call stays capturable).
+int init_eval(pskv_shard* s, const std::vector<pskv_batch>& dv) {
+  for (const auto& b : dv) {
+    if (s->has_init())
+      PSKV_HIP(launch_init_eval(s->dtype, s->init_rule(), b.keys, b.n, b.vals, s->width, s->stream));
+    else
+      PSKV_HIP(launch_fill(s->dtype, b.vals, b.n * (uint64_t)s->width, 0.0, s->stream));
+  }
+  return PSKV_OK;
+}
+
+// src.param null: the rows are not gathered but evaluated (pskv_get_init).
 int rows_get_from(pskv_shard* s, const std::vector<pskv_batch>& in, int flags, const DenseView& src,
                   const char* what, uint64_t* calls) {
   HstageHold hold(s);
   RowCall c;
-  int rc = rows_front(s, in, flags, RowFront{what, calls, false, nullptr, nullptr, /*with_values=*/false}, hold, &c);
+  const bool eval = src.param == nullptr;
+  int rc = rows_front(s, in, flags, RowFront{what, calls, false, nullptr, nullptr, /*with_values=*/false, eval}, hold,
+                      &c);
   if (rc || c.v.empty()) return rc;
-  if ((rc = rows_gather(s, c.views(), src)) || !c.host) return rc;
+  if ((rc = eval ? init_eval(s, c.views()) : rows_gather(s, c.views(), src)) || !c.host) return rc;
   std::vector<Piece> back;
   for (size_t i = 0; i < c.v.size(); ++i)
     add_pieces(back, static_cast<char*>(s->hstage) + c.lay.at[i].vals, static_cast<char*>(c.v[i].vals),
@@ -2040,10 +2073,17 @@ OptArgs<double> opt_args(const pskv_optimizer_cfg& c, uint64_t step) {
 // `start` over rows [first_row, first_row + rows), the last rows of a
 // row-shaped array, and zero over the zero row a sparse shard keeps behind
 // them (stream-ordered; zeros are one memset, another value is k_fill).
+// The parameters of a dense row shard with an initializer start as init(key)
+// instead (a sparse shard's rows are filled as their keys are inserted).
 int fill_rows(pskv_shard* s, void* array, uint64_t first_row, uint64_t rows, double start) {
   const size_t rb = row_bytes(s);
   char* at = static_cast<char*>(array) + first_row * rb;
   const uint64_t zero_rows = s->sparse ? 1 : 0;
+  if (array == s->dense && !s->sparse && s->has_init()) {
+    PSKV_HIP(launch_row_init_range(s->dtype, s->init_rule(), at, s->key_begin + (uint32_t)first_row, rows, s->width,
+                                   s->stream));
+    return PSKV_OK;
+  }
   if (start == 0.0 && !std::signbit(start)) {
     PSKV_HIP(hipMemsetAsync(at, 0, (rows + zero_rows) * rb, s->stream));
     return PSKV_OK;
@@ -2140,6 +2180,8 @@ int sparse_rebuild(pskv_shard* s, uint64_t new_capacity, const uint8_t* dead) {
     if (int rc = fill_rows(s, fresh, carried, new_capacity - carried, ra.start)) return rc;
   }
   if (owner.p) PSKV_HIP(hipMemsetAsync(owner.p, 0, new_capacity * sizeof(unsigned long long), s->stream));
+  // the survivors' slots [0, kept) hold their rows: the next fill starts behind them
+  if (s->has_init()) PSKV_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(s->sp_mark), (int)kept, 1, s->stream));
   if (int rc = wait_stream(s, s->stream, "shard stream (sparse rebuild)")) return rc;
   // nothing is queued: the new arrays take over and the old ones go with the DevBufs
   for (int a = 0; a < pskv_shard::kRowArrays; ++a)
@@ -3000,7 +3042,7 @@ int pskv_device_count(void) {
 // Every constructor ends here.  sparse: a sparse shard of key_end slots
 // (pskv_shard_create_sparse validated its arguments; key_begin is 0).
 static int create_impl(int device, uint32_t key_begin, uint64_t key_end, int dtype, int mode, uint32_t width,
-                       uint64_t overflow_slots, bool sparse, pskv_shard** out) {
+                       uint64_t overflow_slots, bool sparse, bool scalar_api, pskv_shard** out) {
   if (!out) return fail(PSKV_EINVAL, "pskv_shard_create: out is null");
   *out = nullptr;
   const int vb = value_bytes(dtype);
@@ -3025,6 +3067,7 @@ static int create_impl(int device, uint32_t key_begin, uint64_t key_end, int dty
   s->key_begin = key_begin;
   s->range = key_end - key_begin;
   s->sparse = sparse;
+  s->scalar_api = scalar_api;
   // tuning / path options: creation defaults from the environment (PSKV_<NAME>),
   // changeable later through pskv_set_option (kOptions below)
   if (int rc = apply_env_options(s)) {
@@ -3079,9 +3122,11 @@ static int create_impl(int device, uint32_t key_begin, uint64_t key_end, int dty
   if (sparse) {  // the index: an empty table and the key of every slot
     s->sp_table_slots = sparse_table_slots(s->range);
     if (hipMalloc(&s->sp_table, s->sp_table_slots * sizeof(unsigned long long)) != hipSuccess ||
-        hipMalloc(&s->sp_slot_keys, s->range * sizeof(uint32_t)) != hipSuccess)
+        hipMalloc(&s->sp_slot_keys, s->range * sizeof(uint32_t)) != hipSuccess ||
+        hipMalloc(&s->sp_mark, 2 * sizeof(uint32_t)) != hipSuccess)
       return bail(fail(PSKV_ENOMEM, "sparse index allocation failed"));
-    if (hipMemsetAsync(s->sp_table, 0, s->sp_table_slots * sizeof(unsigned long long), s->stream) != hipSuccess)
+    if (hipMemsetAsync(s->sp_table, 0, s->sp_table_slots * sizeof(unsigned long long), s->stream) != hipSuccess ||
+        hipMemsetAsync(s->sp_mark, 0, 2 * sizeof(uint32_t), s->stream) != hipSuccess)
       return bail(fail(PSKV_EHIP, "hipMemsetAsync failed"));
   }
   if (int wrc = wait_stream(s, s->stream, "shard stream (creation)")) return bail(wrc);
@@ -3093,7 +3138,8 @@ static int create_impl(int device, uint32_t key_begin, uint64_t key_end, int dty
 
 int pskv_shard_create_rows(int device, uint32_t key_begin, uint64_t key_end, int dtype, int mode,
                            uint32_t width, uint64_t overflow_slots, pskv_shard** out) {
-  return create_impl(device, key_begin, key_end, dtype, mode, width, overflow_slots, /*sparse=*/false, out);
+  return create_impl(device, key_begin, key_end, dtype, mode, width, overflow_slots, /*sparse=*/false,
+                     /*scalar_api=*/false, out);
 }
 
 int pskv_shard_create_sparse(int device, uint64_t capacity, int dtype, int mode, uint32_t width, pskv_shard** out) {
@@ -3109,7 +3155,8 @@ int pskv_shard_create_sparse(int device, uint64_t capacity, int dtype, int mode,
   if ((capacity + 1) * (uint64_t)width * (uint64_t)vb > (1ull << 46))
     return fail(PSKV_EINVAL, "pskv_shard_create_sparse: (capacity + 1) * width * value bytes exceeds 2^46 bytes");
   // (the overflow table is never used: its smallest size)
-  return create_impl(device, 0, capacity, dtype, mode, width, /*overflow_slots=*/64, /*sparse=*/true, out);
+  return create_impl(device, 0, capacity, dtype, mode, width, /*overflow_slots=*/64, /*sparse=*/true,
+                     /*scalar_api=*/false, out);
 }
 
 int pskv_sparse_info_get(pskv_shard* s, pskv_sparse_info* out) {
@@ -3237,7 +3284,8 @@ int pskv_index_time(pskv_shard* s, uint64_t* launches, double* total_ms, uint64_
 
 int pskv_shard_create_ex(int device, uint32_t key_begin, uint64_t key_end, int dtype, int mode,
                          uint64_t overflow_slots, pskv_shard** out) {
-  return pskv_shard_create_rows(device, key_begin, key_end, dtype, mode, 1, overflow_slots, out);
+  return create_impl(device, key_begin, key_end, dtype, mode, 1, overflow_slots, /*sparse=*/false, /*scalar_api=*/true,
+                     out);
 }
 
 uint32_t pskv_shard_width(pskv_shard* s) { return s ? s->width : 0u; }
@@ -3311,6 +3359,7 @@ int pskv_shard_destroy(pskv_shard* s) {
   if (s->sp_table) (void)hipFree(s->sp_table);
   if (s->sp_slot_keys) (void)hipFree(s->sp_slot_keys);
   if (s->sp_ids) (void)hipFree(s->sp_ids);
+  if (s->sp_mark) (void)hipFree(s->sp_mark);
   if (s->hstage) (void)hipHostFree(s->hstage);
   if (s->ireply) (void)hipHostFree(s->ireply);
   if (s->stat_host) (void)hipHostFree(s->stat_host);
@@ -3576,6 +3625,54 @@ int pskv_put_state(pskv_shard* s, int slot, const uint32_t* keys, const void* va
   return state_call(s, "pskv_put_state", false, slot, keys, const_cast<void*>(vals), n, flags, /*put=*/true);
 }
 
+// ------------------------------------------------------- row initializers
+// pskv.h "Row initializers", DESIGN.md §8q.
+int pskv_shard_set_initializer(pskv_shard* s, const pskv_initializer* cfg) {
+  const std::string who = "pskv_shard_set_initializer: ";
+  if (!cfg) return fail(PSKV_EINVAL, who + "cfg is null");
+  if (cfg->kind < PSKV_INIT_ZERO || cfg->kind > PSKV_INIT_NORMAL)
+    return fail(PSKV_EINVAL, who + "kind must be PSKV_INIT_ZERO, _CONSTANT, _UNIFORM or _NORMAL");
+  if (!std::isfinite(cfg->a)) return fail(PSKV_EINVAL, who + "a must be finite");
+  if (!std::isfinite(cfg->b)) return fail(PSKV_EINVAL, who + "b must be finite");
+  if (cfg->kind == PSKV_INIT_UNIFORM && cfg->a > cfg->b)
+    return fail(PSKV_EINVAL, who + "a (lo) must not exceed b (hi) for PSKV_INIT_UNIFORM");
+  if (cfg->kind == PSKV_INIT_NORMAL && cfg->b < 0.0)
+    return fail(PSKV_EINVAL, who + "b (std) must not be negative for PSKV_INIT_NORMAL");
+  if (!s) return fail(PSKV_EINVAL, who + "null shard");
+  if (s->dtype != PSKV_F32 && s->dtype != PSKV_F64)
+    return fail(PSKV_EINVAL, who + "shard: the dtype must be PSKV_F32 or PSKV_F64");
+  if (s->scalar_api)
+    return fail(PSKV_EINVAL, who + "shard: a scalar range shard takes no initializer (its overflow table holds keys "
+                                   "without rows; pskv_shard_create_rows or pskv_shard_create_sparse)");
+  if (s->dtype == PSKV_F32 && cfg->kind != PSKV_INIT_ZERO) {
+    if (!std::isfinite((float)cfg->a)) return fail(PSKV_EINVAL, who + "a is not finite as a float");
+    if (cfg->kind != PSKV_INIT_CONSTANT && !std::isfinite((float)cfg->b))
+      return fail(PSKV_EINVAL, who + "b is not finite as a float");
+  }
+  if (cfg->kind == PSKV_INIT_UNIFORM) {
+    const double d = cfg->b - cfg->a;
+    if (!std::isfinite(d) || (s->dtype == PSKV_F32 && !std::isfinite((float)d)))
+      return fail(PSKV_EINVAL, who + "b - a is not finite in the shard's value type");
+  }
+  s->init = *cfg;
+  return pskv_clear(s);
+}
+
+int pskv_shard_get_initializer(pskv_shard* s, pskv_initializer* out) {
+  if (!s || !out) return fail(PSKV_EINVAL, "pskv_shard_get_initializer: null argument");
+  *out = s->init;
+  return PSKV_OK;
+}
+
+int pskv_get_init(pskv_shard* s, const uint32_t* keys, uint64_t n, void* out, int flags) {
+  if (flags & ~PSKV_DEVICE) return fail(PSKV_EINVAL, "pskv_get_init: unknown flags (PSKV_HOST or PSKV_DEVICE)");
+  if (n && (!keys || !out)) return fail(PSKV_EINVAL, "pskv_get_init: null keys/out with n > 0");
+  if (!s) return fail(PSKV_EINVAL, "pskv_get_init: null shard");
+  if (s->dtype != PSKV_F32 && s->dtype != PSKV_F64)
+    return fail(PSKV_EINVAL, "pskv_get_init: shard: the dtype must be PSKV_F32 or PSKV_F64");
+  return rows_get_from(s, {pskv_batch{keys, out, n}}, flags, DenseView{nullptr, 0, 0, 0}, "pskv_get_init", nullptr);
+}
+
 int pskv_apply_time(pskv_shard* s, uint64_t* launches, double* total_ms, uint64_t* elements) {
   return timed_op_read(s, "pskv_apply_time", kTimeApply, launches, total_ms, elements);
 }
@@ -3623,6 +3720,7 @@ int pskv_clear(pskv_shard* s) {
   if ((rc = fill_rows(s, s->dense, 0, s->range, 0.0))) return rc;
   // a sparse shard: an empty index (the slot counter and the full bit go with stat below)
   if (s->sparse) PSKV_HIP(hipMemsetAsync(s->sp_table, 0, s->sp_table_slots * sizeof(unsigned long long), s->stream));
+  if (s->sparse && s->has_init()) PSKV_HIP(hipMemsetAsync(s->sp_mark, 0, 2 * sizeof(uint32_t), s->stream));
   PSKV_HIP(hipMemsetAsync(s->cur.keys, 0xFF, s->ocap * sizeof(unsigned long long), s->stream));
   PSKV_HIP(hipMemsetAsync(s->cur.vals, 0, s->ocap * (size_t)s->vb, s->stream));
   PSKV_HIP(hipMemsetAsync(s->ovf.c->stat, 0, 2 * sizeof(uint32_t), s->stream));

@@ -54,11 +54,14 @@ class Shard:
     memory following capacity and not the key space (include/pskv.h, "Sparse
     shards").  key_begin, key_end and overflow_slots are not used.  reserve,
     set_growth and erase change what it holds room for; `capacity` follows
-    reserve and load_state_dict, sparse_info()["capacity"] is always current."""
+    reserve and load_state_dict, sparse_info()["capacity"] is always current.
+
+    init: a row initializer set at creation, set_initializer's arguments as a
+    dict or a (kind, a, b, seed) tuple (include/pskv.h, "Row initializers")."""
 
     def __init__(self, key_begin: int = 0, key_end: int = 1 << 32, dtype=np.float32,
                  mode: str = "assign", device: int = 0, overflow_slots: int = 0, options=None,
-                 width: int = 1, capacity: int = 0):
+                 width: int = 1, capacity: int = 0, init=None):
         self.dtype = np.dtype(dtype) if not _is_torch(dtype) else _NP_DTYPE[dtype_code(dtype)]
         self.code = dtype_code(self.dtype)
         self.mode = {"assign": _lib.PSKV_ASSIGN, "accumulate": _lib.PSKV_ACCUMULATE}[mode]
@@ -81,15 +84,21 @@ class Shard:
         self._h = h
         for name, value in (options or {}).items():
             self.set_option(name, value)
+        if init is not None:  # set_initializer's arguments: a dict, or (kind, a, b, seed)
+            try:
+                self.set_initializer(**init) if isinstance(init, dict) else self.set_initializer(*init)
+            except Exception:
+                self.close()
+                raise
 
     @classmethod
     def sparse(cls, capacity: int, dtype=np.float32, mode: str = "assign", device: int = 0, width: int = 1,
-               options=None, max_capacity=None) -> "Shard":
+               options=None, max_capacity=None, init=None) -> "Shard":
         """A sparse shard of at most `capacity` distinct keys (pskv_shard_create_sparse).
         max_capacity: writing calls may grow it up to that many (set_growth)."""
         if int(capacity) == 0:
             raise ValueError("Shard.sparse: capacity must be positive")
-        s = cls(dtype=dtype, mode=mode, device=device, options=options, width=width, capacity=capacity)
+        s = cls(dtype=dtype, mode=mode, device=device, options=options, width=width, capacity=capacity, init=init)
         if max_capacity is not None:
             try:
                 s.set_growth(max_capacity)
@@ -629,6 +638,50 @@ class Shard:
             return
         k = self._host_keys(keys)
         check(lib.pskv_sparse_erase(self._h, k.ctypes.data, k.size, _lib.PSKV_HOST))
+
+    # ------------------------------------------------------------ row initializers
+    _INIT_KIND = {None: _lib.PSKV_INIT_ZERO, "zero": _lib.PSKV_INIT_ZERO, "constant": _lib.PSKV_INIT_CONSTANT,
+                  "uniform": _lib.PSKV_INIT_UNIFORM, "normal": _lib.PSKV_INIT_NORMAL}
+    _INIT_NAME = {_lib.PSKV_INIT_ZERO: "zero", _lib.PSKV_INIT_CONSTANT: "constant",
+                  _lib.PSKV_INIT_UNIFORM: "uniform", _lib.PSKV_INIT_NORMAL: "normal"}
+
+    def set_initializer(self, kind, a: float = 0.0, b: float = 0.0, seed: int = 0):
+        """pskv_shard_set_initializer: what a never-written row holds.  kind
+        "zero" (or None), "constant" (a), "uniform" (lo a, hi b) or "normal"
+        (mean a, std b), or the PSKV_INIT_* code.  Acts as clear() under the
+        new rule: a creation-time call."""
+        code = self._INIT_KIND.get(kind, kind)
+        cfg = _lib.PskvInitializer(int(code), int(seed) & ((1 << 64) - 1), float(a), float(b))
+        check(lib.pskv_shard_set_initializer(self._h, ctypes.byref(cfg)))
+
+    def initializer(self) -> dict:
+        cfg = _lib.PskvInitializer()
+        check(lib.pskv_shard_get_initializer(self._h, ctypes.byref(cfg)))
+        return {"kind": self._INIT_NAME[cfg.kind], "a": cfg.a, "b": cfg.b, "seed": cfg.seed}
+
+    def init_rows(self, keys, out=None):
+        """init(keys[i]) as row i (pskv_get_init): what each key's row holds
+        before its first write; nothing in the shard is touched.  numpy keys ->
+        a numpy array (synchronous); a device tensor -> a tensor, stream-ordered.
+        Shaped as get's result."""
+        if _is_torch(keys):
+            import torch
+
+            if out is None:
+                shape = (keys.numel(), self.width) if self.width > 1 else keys.numel()
+                out = torch.empty(shape, dtype=_torch_dtype(self.dtype), device=keys.device)
+            self._check_dev(keys, out)
+            self._check_dev_count(keys, out)
+            check(lib.pskv_get_init(self._h, keys.data_ptr(), keys.numel(), out.data_ptr(), _lib.PSKV_DEVICE))
+            return out
+        k = self._host_keys(keys)
+        if out is None:
+            out = np.empty((k.size, self.width) if self.width > 1 else k.size, dtype=self.dtype)
+        elif not (isinstance(out, np.ndarray) and out.dtype == self.dtype and out.flags.c_contiguous
+                  and out.size == k.size * self.width):
+            raise ValueError("init_rows: out must be a C-contiguous array of keys * width values")
+        check(lib.pskv_get_init(self._h, k.ctypes.data, k.size, out.ctypes.data, _lib.PSKV_HOST))
+        return out
 
     def index_time(self):
         """A sparse shard's index launches, one operation per call (pskv_index_time)."""
