@@ -263,6 +263,24 @@ class HipStorage : public AbstractStorage {
     return third_party::SArray<char>(reply_vals);
   }
 
+  // One dot product per key (pskv_get_scores), the bags as SubGetPooled's:
+  // the reply holds typed_keys.size() values, queries[b] . row(typed_keys[i])
+  // with b the bag that holds position i; queries holds (offsets.size() - 1) *
+  // width values, a row per bag.  Not part of AbstractStorage.
+  third_party::SArray<char> SubGetScores(const third_party::SArray<Key>& typed_keys,
+                                         const third_party::SArray<uint64_t>& offsets,
+                                         const third_party::SArray<Val>& queries) {
+    if (offsets.size() == 0 || queries.size() != (offsets.size() - 1) * width_) {
+      std::fprintf(stderr, "Check failed: offsets.size() >= 1 and queries.size() == (offsets.size() - 1) * width\n");
+      std::abort();
+    }
+    auto reply_vals = FrameArray<Val>(typed_keys.size());
+    pskv_check(pskv_get_scores(shard_, typed_keys.data(), typed_keys.size(), queries.data(), offsets.data(),
+                               offsets.size() - 1, reply_vals.data(), PSKV_HOST | PSKV_HOST_FRAME),
+               "pskv_get_scores");
+    return third_party::SArray<char>(reply_vals);
+  }
+
   // One optimizer step that is the backward pass of SubGetPooledFm
   // (pskv_apply_pooled_fm): bag_scale holds dL/dpair per bag, bag_grads
   // dL/dsum ((offsets.size() - 1) * width values) or null.  Every row on the

@@ -372,6 +372,44 @@
  *   - not provided: grouped forms, int32, field-aware or higher-order terms,
  *     and the linear term, which is a W = 1 shard's existing pooled calls.
  *
+ * Score pulls (pskv_get_scores): the forward half of a
+ * dot-product model, one score per key against a query row the caller brings,
+ *     out[i] = sum_j queries[bag(i) * W + j] * row(keys[i])[j],
+ * bag(i) the bag b with offsets[b] <= i < offsets[b+1].  With weights = dL/ds,
+ * pskv_get_pooled returns the query's gradient and pskv_apply_pooled(bag_grads
+ * = queries) applies the rows': three calls make a sampled-softmax or two-tower
+ * step, their payloads one scalar per key and one row per bag.  Bags, offsets
+ * and flags are pskv_get_pooled's; T is the shard's value type.
+ *   The sum of one score is a function of the row's bits, the query's bits and
+ *   W alone.  With a unit of 16 / sizeof(T) elements when W * sizeof(T) is a
+ *   multiple of 16 and of one element otherwise, U units in a row and L =
+ *   min(64, next_pow2(U)) lanes: lane l keeps one chain acc = fma(q_e, p_e, acc)
+ *   from +0 over the elements of units l, l + L, ... in that order, a unit's
+ *   elements in order; a lane at or past U keeps +0; then log2(L) steps acc =
+ *   acc + partner's acc, partner l ^ (L/2), ..., l ^ 1.  Never a function of
+ *   the key's position, the bag layout, n, the launch, host or device buffers,
+ *   row or sparse shard, the alignment of queries or out, an option or timing;
+ *   there are no atomics on values and the same call returns the same bits.
+ *   Rules:
+ *   - float shards only (PSKV_I32: PSKV_EINVAL), any width (1 included), row
+ *     and sparse shards; the call only reads: a Get (n_get_calls);
+ *   - checked before the handle is looked at, as pskv_get_pooled_fm: flags; null
+ *     keys with n > 0, null offsets or queries with nbags > 0, null out with
+ *     keys and bags; a host call's offsets, naming the first bad bag;
+ *   - nbags == 0, or n == 0: PSKV_OK, nothing is written, null pointers allowed
+ *     for what has no element;
+ *   - a key that reads zeros scores +0 against finite queries: a never-written
+ *     key without an initializer, a sparse shard's absent key (reads never
+ *     insert), and on the device path a key outside a row shard's range, which
+ *     also sets the out-of-range status as pskv_get_pooled reports it; a host
+ *     call with such a key is refused before anything is queued, out untouched;
+ *   - malformed device offsets give unspecified scores, never an access outside
+ *     keys[0, n), offsets[0, nbags], queries[0, nbags * W) and out[0, n);
+ *   - one launch per call at every n; timing: PSKV_TIME_POOLED's slot, one
+ *     operation per call, elements = n; SERVE = 1 is ended first; a host call
+ *     is synchronous, a device call stream-ordered;
+ *   - not provided: weights (scale the query), int32, a grouped form.
+ *
  * Sparse shards (pskv_shard_create_sparse): a shard whose memory
  * follows the number of keys it holds, not the span of the key space -- the
  * storage of a server under consistent hashing (a scattered 1/N of the keys),
@@ -760,6 +798,14 @@ int pskv_get_pooled_fm(pskv_shard* s, const uint32_t* keys, uint64_t n, const vo
 int pskv_apply_pooled_fm(pskv_shard* s, const uint32_t* keys, uint64_t n, const void* weights,
                          const uint64_t* offsets, uint64_t nbags, const void* bag_scale,
                          const void* bag_grads, int flags);
+
+/* Score pull (semantics: the header comment, "Score pulls"):
+ * out[i] = sum_j queries[bag(i) * W + j] * row(keys[i])[j], bag(i) the bag b with
+ * offsets[b] <= i < offsets[b+1].  keys: n keys, bag after bag; queries: nbags * W values
+ * of the shard's type; offsets: nbags + 1 values; out: n values.
+ * Synchronous for host buffers, stream-ordered for PSKV_DEVICE ones. */
+int pskv_get_scores(pskv_shard* s, const uint32_t* keys, uint64_t n, const void* queries,
+                    const uint64_t* offsets, uint64_t nbags, void* out, int flags);
 
 /* Grouped pooled push (semantics: "Grouped pooled pushes"): ONE optimizer step
  * from the pooled pushes of nb workers, the step pskv_apply_pooled would make

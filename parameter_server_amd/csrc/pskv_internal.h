@@ -418,6 +418,24 @@ hipError_t launch_row_step_apply(int dtype, int kind, const FmPushArgs& a, uint3
                                  void* const state[2], const unsigned long long* owner, uint32_t epoch,
                                  const RowShape& rs, const OptArgs<double>& hy, hipStream_t st);
 
+// Score pull (pskv_get_scores; pskv.h "Score pulls"), float
+// shards: out[i] = sum_j queries[bag(i) * W + j] * row(keys[i])[j].  One
+// launch at every n; windows, sub-passes and the bag of a position:
+// pskv_plan.h; the order of the sum: pskv_rows.hip.
+struct ScoreArgs {
+  const uint32_t* keys;     // n
+  const uint64_t* offsets;  // nbags + 1 (the kernel reads [0, nbags))
+  const void* queries;      // nbags rows, element-aligned
+  void* out;                // n values, element-aligned
+  uint64_t n, nbags;
+};
+// unit16 of rs wants the row size a multiple of 16 bytes and the dense array
+// aligned, NOT queries or out: the unit is a function of the width alone.  A
+// key outside the range scores +0 and sets kErrRowOutOfRange.  nt: the scores
+// leave in non-temporal stores.
+hipError_t launch_row_scores(int dtype, bool nt, const ScoreArgs& a, const DenseView& d, const Ovf& o,
+                             const RowShape& rs, hipStream_t st);
+
 // Sparse shards (pskv_index.hip): the hash index that maps a
 // uint32 key to a slot of the row arrays.  table: mask + 1 entries (a power of
 // two, >= 2 * capacity), linear probing from fmix32(key).  An entry is 0 when

@@ -408,6 +408,61 @@ static inline const char* pool_offsets_error(const uint64_t* off, uint64_t nbags
   return nullptr;
 }
 
+// Score pulls (pskv_get_scores) work position-major too, and
+// their output is per position: a virtual workgroup owns the WINDOW of
+// kScoreWindow consecutive key positions, so the grid is a function of n alone.
+// It walks its window in sub-passes; each stages the query rows of the next
+// bags, at most kScoreStageBytes of them (one row at least: 4096 doubles are
+// the whole budget), and scores the positions of those bags.
+constexpr uint32_t kScoreWindow = 1024;
+constexpr uint32_t kScoreStageBytes = 32768;
+// Query rows a sub-pass stages at most (row_bytes <= kScoreStageBytes).
+PSKV_HD static inline uint64_t score_stage_rows(uint64_t row_bytes) { return kScoreStageBytes / row_bytes; }
+
+// One sub-pass of the window whose bag span is sp: positions [p, p1) of bags
+// [b, bend).  score_pass starts it from the position p the last one ended at
+// (the window's first) and the first bag `from` not staged yet (sp.lo): b is
+// the last bag of [from, sp.hi] with off[b] <= p (`from` when there is none),
+// bend = min(b + rows, sp.hi + 1), and p1 the first position of bag bend
+// clamped to [p, end], or `end`, the window's, when bend is past the span.
+// Whatever the offsets hold: from <= b < bend <= sp.hi + 1 <= nbags and p <= p1
+// <= end, and a pass that scores no position still moves `from` up, so a
+// window ends after at most sp.hi - sp.lo + 1 passes.  With well-formed
+// offsets every position of [p, p1) lies in a bag of [b, bend).
+struct ScorePass {
+  uint64_t b, bend, p1;
+};
+// The last index i of [lo, hi) with off[i] <= x (lo when there is none; lo < hi).
+PSKV_HD static inline uint64_t score_bag_in(const uint64_t* off, uint64_t lo, uint64_t hi, uint64_t x) {
+  while (hi - lo > 1) {
+    const uint64_t mid = lo + ((hi - lo) >> 1);
+    if (off[mid] <= x)
+      lo = mid;
+    else
+      hi = mid;
+  }
+  return lo;
+}
+PSKV_HD static inline ScorePass score_pass(const uint64_t* off, const PoolSpan& sp, uint64_t from, uint64_t p,
+                                           uint64_t end, uint64_t rows) {
+  ScorePass r;
+  r.b = score_bag_in(off, from, sp.hi + 1, p);
+  r.bend = sp.hi + 1 - r.b > rows ? r.b + rows : sp.hi + 1;
+  r.p1 = end;
+  if (r.bend <= sp.hi) {
+    const uint64_t o = off[r.bend];
+    r.p1 = o < p ? p : (o < end ? o : end);
+  }
+  return r;
+}
+// The bag of position x inside a pass, walked forward from the cursor `cb`
+// (b <= cb < bend): the offsets are monotone, so a lane group whose positions
+// rise never searches.  The result stays in [cb, bend).
+PSKV_HD static inline uint64_t score_bag_walk(const uint64_t* off, uint64_t cb, uint64_t bend, uint64_t x) {
+  while (cb + 1 < bend && off[cb + 1] <= x) ++cb;
+  return cb;
+}
+
 }  // namespace
 
 // ---------------------------------------------------- grouped pooled pushes

@@ -13,6 +13,7 @@
 //   k_row_fm_pooled      FM pooled pull: the pooled sum and pair[b] = 0.5 * sum_j (S_j * S_j - Q_j), reduced
 //                        over the row inside the wave; also the bag rows c_b * S_b (+ bag_grads[b]) of an FM push
 //   k_row_fm_pooled_chunks  FM pooled pull: the partial S and Q rows of long bags' chunks
+//   k_row_scores         score pull: out[i] = queries[bag(i)] . row(keys[i]), the query rows through LDS
 //   k_row_fm_step_losers, k_row_fm_step_apply  FM push: the pooled step whose gradient rows hold the key's own
 //                        pre-step row, (w * t) - (e * p)
 //
@@ -1270,6 +1271,141 @@ hipError_t launch_row_fm_bags(int dtype, const FmPoolArgs& a, const DenseView& d
   });
 }
 
+// ------------------------------------------------------------ score pulls
+// pskv_get_scores: out[i] = queries[bag(i)] . row(keys[i]).
+// The output is per key position, so the work is split by position: a virtual
+// workgroup owns a window of kScoreWindow positions (grid-stride over the
+// windows; the grid is a function of n alone) and walks it in sub-passes
+// (score_pass, pskv_plan.h; thread 0 plans a pass and publishes it in LDS):
+//   stage   the query rows of the pass's bags [b, bend), contiguous in
+//           `queries`, into LDS: 16-byte loads where their first byte is
+//           aligned, else element loads -- the LDS image is the same
+//   score   the pass's positions [p, p1) in G contiguous runs, one per lane
+//           group: a group finds the bag of its run's first position by one
+//           search of [b, bend) and then walks the offsets forward; R rows'
+//           loads are in flight before the first use; the query comes from LDS
+//   store   the groups left their scalars in LDS; the workgroup writes them
+//           as out[p .. p1), 16-byte stores between the aligned ends
+// The sum of one score, a function of the row, the query and the width alone:
+// lane l of the group's L keeps ONE chain acc = fma(q_e, p_e, acc) from +0
+// over its elements in the order it meets them (units l, l + L, ..., a unit's
+// elements in order; a lane at or past U keeps +0), then log2(L) butterfly
+// steps acc + partner's acc, partner l ^ (L/2), ..., l ^ 1, as the FM pair
+// term.  The unit is a function of the width (and the shard's own arrays).
+// A key outside the range reads a zero row and sets kErrRowOutOfRange.
+// Whatever the offsets hold, a pass reads offsets[.. nbags), queries rows below
+// nbags, keys and out at positions of the window only.
+template <typename T, int V, bool NT>
+__global__ __launch_bounds__(kBlock) void k_row_scores(ScoreArgs a, DenseView d, uint32_t* err, RowShape rs) {
+  constexpr int R = kRowsInFlight;
+  constexpr int V16 = 16 / sizeof(T);
+  typedef T vt __attribute__((ext_vector_type(V16)));
+  __shared__ __attribute__((aligned(16))) T qs[kScoreStageBytes / sizeof(T)];
+  __shared__ __attribute__((aligned(16))) T sc[kScoreWindow];
+  __shared__ uint64_t pass[3];  // b, bend, p1
+  const uint32_t tid = threadIdx.x;
+  const uint32_t lane = tid & (rs.lanes - 1u);
+  const uint32_t grp = tid >> rs.lshift;
+  const uint32_t G = (uint32_t)kBlock >> rs.lshift;
+  const uint32_t U = rs.units;
+  const uint64_t W = (uint64_t)U * V;  // elements of a row
+  const uint64_t stage_rows = score_stage_rows(W * sizeof(T));
+  const T* __restrict__ param = reinterpret_cast<const T*>(d.param);
+  const T* __restrict__ queries = reinterpret_cast<const T*>(a.queries);
+  const uint64_t* __restrict__ off = a.offsets;
+  T* __restrict__ out = reinterpret_cast<T*>(a.out);
+  const uint64_t nwin = (a.n + kScoreWindow - 1) / kScoreWindow;
+  for (uint64_t win = blockIdx.x; win < nwin; win += gridDim.x) {
+    const uint64_t wb = win * kScoreWindow;
+    const uint64_t we = wb + kScoreWindow < a.n ? wb + kScoreWindow : a.n;
+    PoolSpan sp{0, 0};
+    if (tid == 0) sp = pool_bag_span(off, a.nbags, wb, we - 1);
+    uint64_t p = wb, from = sp.lo;  // (from: thread 0's alone)
+    while (p < we) {
+      if (tid == 0) {
+        const ScorePass sn = score_pass(off, sp, from, p, we, stage_rows);
+        pass[0] = sn.b;
+        pass[1] = sn.bend;
+        pass[2] = sn.p1;
+      }
+      __syncthreads();  // the pass is planned; the last one's scores have left `sc`
+      const uint64_t b = pass[0], bend = pass[1], p1 = pass[2];
+      {  // stage: (bend - b) * W * sizeof(T) <= kScoreStageBytes
+        const uint64_t cnt = (bend - b) * W;
+        const T* __restrict__ src = queries + b * W;
+        uint64_t done = 0;
+        if ((reinterpret_cast<uintptr_t>(src) & 15u) == 0) {
+          const uint64_t nvec = cnt / V16;
+          for (uint64_t v = tid; v < nvec; v += kBlock)
+            *reinterpret_cast<vt*>(qs + v * V16) = *reinterpret_cast<const vt*>(src + v * V16);
+          done = nvec * V16;
+        }
+        for (uint64_t i = done + tid; i < cnt; i += kBlock) qs[i] = src[i];
+      }
+      __syncthreads();  // the query rows are staged
+      const uint32_t m = (uint32_t)(p1 - p);  // <= kScoreWindow
+      const uint32_t c = (m + G - 1) / G;     // positions of a lane group's run
+      const uint32_t x0 = grp * c;            // the run's first, from p
+      uint64_t cb = b;
+      if (x0 < m) cb = score_bag_in(off, b, bend, p + x0);
+      for (uint32_t i = 0; i < c; i += R) {  // (c is uniform: every lane of a wave reaches the shuffles)
+        uint32_t ko[R], qu[R];
+        bool live[R], in[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+          const uint32_t x = x0 + i + (uint32_t)r;
+          live[r] = i + (uint32_t)r < c && x < m;
+          const uint32_t k = live[r] ? a.keys[p + x] : 0u;
+          ko[r] = k - d.key_begin;
+          in[r] = live[r] && (uint64_t)ko[r] < d.range;
+          if (live[r]) cb = score_bag_walk(off, cb, bend, p + x);
+          qu[r] = (uint32_t)(cb - b) * U;  // the bag's first unit in qs
+          if (live[r] && !in[r] && lane == 0) atomicOr(err, kErrRowOutOfRange);
+        }
+        T acc[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) acc[r] = T(0);
+        for (uint32_t u = lane; u < U; u += rs.lanes) {
+          OptUnit<T, V> pr[R];
+#pragma unroll
+          for (int r = 0; r < R; ++r)
+            pr[r] = in[r] ? load_opt_unit<T, V>(param, (uint64_t)ko[r] * U + u) : zero_opt_unit<T, V>();
+#pragma unroll
+          for (int r = 0; r < R; ++r) {
+            const OptUnit<T, V> q = load_opt_unit<T, V>(qs, qu[r] + u);
+#pragma unroll
+            for (int j = 0; j < V; ++j) acc[r] = pool_fma(q.e[j], pr[r].e[j], acc[r]);
+          }
+        }
+        for (uint32_t step = rs.lanes >> 1; step > 0; step >>= 1) {
+#pragma unroll
+          for (int r = 0; r < R; ++r) acc[r] = acc[r] + __shfl_xor(acc[r], (int)step);
+        }
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+          if (live[r] && lane == 0) sc[x0 + i + (uint32_t)r] = acc[r];
+      }
+      __syncthreads();  // the pass's scores lie in sc[0 .. m); qs is free again
+      {  // store
+        T* __restrict__ dst = out + p;
+        const uint32_t to16 = (uint32_t)((16u - (reinterpret_cast<uintptr_t>(dst) & 15u)) & 15u) / (uint32_t)sizeof(T);
+        const uint32_t head = to16 < m ? to16 : m;
+        const uint32_t nvec = (m - head) / V16;
+        if (tid < head) store_unit<NT>(dst + tid, sc[tid]);
+        for (uint32_t v = tid; v < nvec; v += kBlock) {
+          vt x;
+#pragma unroll
+          for (int j = 0; j < V16; ++j) x[j] = sc[head + v * V16 + j];
+          store_unit<NT>(reinterpret_cast<vt*>(dst + head + v * V16), x);
+        }
+        for (uint32_t i = head + nvec * V16 + tid; i < m; i += kBlock) store_unit<NT>(dst + i, sc[i]);
+      }
+      p = p1;
+      from = bend;
+    }
+  }
+}
+
 }  // namespace
 
 RowShape row_shape(uint32_t width, int vb, bool unit16) {
@@ -1449,6 +1585,26 @@ hipError_t launch_row_fm_pooled(int dtype, const FmPoolArgs& a, const DenseView&
 hipError_t launch_row_fm_bag_rows(int dtype, const FmPoolArgs& a, const DenseView& d, const Ovf& o,
                                   const RowShape& rs, hipStream_t st) {
   return launch_row_fm_bags<false>(dtype, a, d, o, rs, st);
+}
+
+hipError_t launch_row_scores(int dtype, bool nt, const ScoreArgs& a, const DenseView& d, const Ovf& o,
+                             const RowShape& rs, hipStream_t st) {
+  if (a.n == 0 || a.nbags == 0) return hipSuccess;
+  if (!a.keys || !a.offsets || !a.queries || !a.out || (uint64_t)rs.units * rs.unit_bytes > kScoreStageBytes)
+    return hipErrorInvalidValue;
+  const uint64_t nwin = (a.n + kScoreWindow - 1) / kScoreWindow;
+  const uint32_t grid = row_grid((uint32_t)std::min<uint64_t>(nwin, 4096));
+  uint32_t* err = &o.c->stat[1];
+  return with_float_type(dtype, [&](auto z) {
+    using T = decltype(z);
+    with_opt_unit<T>(rs, [&](auto v) {
+      constexpr int V = decltype(v)::value;
+      if (nt)
+        k_row_scores<T, V, true><<<grid, kBlock, 0, st>>>(a, d, err, rs);
+      else
+        k_row_scores<T, V, false><<<grid, kBlock, 0, st>>>(a, d, err, rs);
+    });
+  });
 }
 
 hipError_t launch_row_step_losers(int dtype, const FmPushArgs& a, uint32_t nwg, const DenseView& d, void* gsum,

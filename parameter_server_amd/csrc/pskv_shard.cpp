@@ -2434,6 +2434,46 @@ int pooled_fm_impl(pskv_shard* s, const pskv_pool_batch& call, void* out_pair, i
   return rows_to_host(s, hold, at, pair_at + pair_bytes - at, "shard stream (FM pooled pull to host)", back);
 }
 
+// ------------------------------------------------------------ score pulls
+// pskv_get_scores (pskv.h "Score pulls"): one dot product per
+// key, queries[bag(i)] . row(keys[i]).  Through pool_front as a pull that
+// stages rows: the queries ride in bag_grads.  One launch at every n, timed
+// as one operation (kTimePooled).  A host call's n scores get room behind the
+// pooled layout (fm_reserve_stage).
+// `c`: the call as the kernel reads it, bag_grads its query rows.
+int scores_device(pskv_shard* s, const pskv_pool_batch& c, void* out) {
+  const ScoreArgs a{c.keys, c.offsets, c.bag_grads, out, c.n, c.nbags};
+  const RowShape rs = fm_row_shape(s, {s->dense});
+  LaunchTimer t(s, kTimePooled, c.n);
+  PSKV_HIP(launch_row_scores(s->dtype, s->tune_nt, a, s->read_view(s->dense), s->ovf, rs, s->stream));
+  t.done();
+  return PSKV_OK;
+}
+
+// The arguments hold (pskv_get_scores checked them).  call.bag_grads: the queries.
+int scores_impl(pskv_shard* s, const pskv_pool_batch& call, void* out, int flags) {
+  if (const char* why = fm_refusal(s)) return fail(PSKV_EINVAL, std::string("pskv_get_scores") + why);
+  ++s->n_get;
+  if (call.nbags == 0 || call.n == 0) return PSKV_OK;  // no bag, or no key: no score
+  const bool host = !(flags & PSKV_DEVICE);
+  const size_t out_bytes = call.n * (size_t)s->vb;
+  HstageHold hold(s);
+  size_t out_at = 0;
+  int rc = host ? fm_reserve_stage(s, call, out_bytes, &out_at) : PSKV_OK;
+  if (rc) return rc;
+  std::vector<pskv_pool_batch> v;
+  rc = pool_front(s, {call}, nullptr, flags,
+                  PoolFront{"pskv_get_scores", /*writing=*/false, /*with_rows=*/true,
+                            "a score pull reads the dense array only; out is untouched"},
+                  hold, &v);
+  if (rc) return rc;
+  if (!host) return scores_device(s, v[0], out);
+  if ((rc = scores_device(s, v[0], static_cast<char*>(s->dstage) + out_at))) return rc;
+  std::vector<Piece> back;
+  add_pieces(back, static_cast<char*>(s->hstage) + out_at, static_cast<char*>(out), out_bytes, -1);
+  return rows_to_host(s, hold, out_at, out_bytes, "shard stream (score pull to host)", back);
+}
+
 // The push: step_device over an FmPushArgs whose rows are the bag rows t_b,
 // computed from the pre-step parameters in front of the stamps (a long bag's
 // partial sums by the pooled pull's own chunk pass).  Stream order is what
@@ -3561,6 +3601,24 @@ int pskv_get_pooled_fm(pskv_shard* s, const uint32_t* keys, uint64_t n, const vo
   }
   if (!s) return fail(PSKV_EINVAL, "pskv_get_pooled_fm: null shard");
   return pooled_fm_impl(s, pskv_pool_batch{keys, weights, offsets, out_sum, n, nbags}, out_pair, flags);
+}
+
+// pskv_get_pooled_fm's checks in its order, with queries and out as the arrays that must not be null.
+int pskv_get_scores(pskv_shard* s, const uint32_t* keys, uint64_t n, const void* queries, const uint64_t* offsets,
+                    uint64_t nbags, void* out, int flags) {
+  if (bad_flags(flags)) return fail(PSKV_EINVAL, "pskv_get_scores: unknown flags");
+  if (n && !keys) return fail(PSKV_EINVAL, "pskv_get_scores: null keys with n > 0");
+  if (nbags && !offsets) return fail(PSKV_EINVAL, "pskv_get_scores: null offsets with nbags > 0");
+  if (nbags && !queries) return fail(PSKV_EINVAL, "pskv_get_scores: null queries with nbags > 0");
+  if (nbags && n && !out) return fail(PSKV_EINVAL, "pskv_get_scores: null out with n > 0");
+  if (!(flags & PSKV_DEVICE)) {
+    uint64_t bad = 0;
+    if (const char* why = pool_offsets_error(offsets, nbags, n, &bad))
+      return fail(PSKV_EINVAL, "pskv_get_scores: offsets: bag " + std::to_string(bad) + ": " + why + " (n = " +
+                                   std::to_string(n) + ", nbags = " + std::to_string(nbags) + ")");
+  }
+  if (!s) return fail(PSKV_EINVAL, "pskv_get_scores: null shard");
+  return scores_impl(s, pskv_pool_batch{keys, nullptr, offsets, queries, n, nbags}, out, flags);
 }
 
 // pskv_apply_pooled's checks (pool_batch_error) with bag_scale in the place of

@@ -475,6 +475,47 @@ class Shard:
         del w
         return out, pair
 
+    def get_scores(self, keys, offsets, queries, out=None):
+        """One dot product per key (pskv_get_scores): out[i] = queries[b] .
+        row(keys[i]), b the bag that holds position i; queries holds nbags *
+        width values of the shard's dtype.  numpy inputs -> host path, returns
+        a numpy array; torch tensors -> device path (offsets an int64 tensor),
+        stream-ordered.  Returns n values."""
+        dev = _is_torch(keys)
+        if dev:
+            import torch
+
+            if offsets.dtype != torch.int64 or offsets.numel() < 1:
+                raise ValueError("get_scores: device offsets must be an int64 tensor of nbags + 1 values")
+            self._check_dev(keys, offsets)
+            pk, n, po, nbags, flags = keys.data_ptr(), keys.numel(), offsets.data_ptr(), offsets.numel() - 1, \
+                _lib.PSKV_DEVICE
+            if out is None:
+                out = torch.empty(n, dtype=_torch_dtype(self.dtype), device=keys.device)
+            elif out.dtype != _torch_dtype(self.dtype) or out.numel() != n or not out.is_contiguous():
+                raise ValueError("get_scores: out must be a contiguous tensor of n values of the shard's dtype")
+            else:
+                self._check_dev(out)
+            pout = out.data_ptr()
+        else:
+            k = self._host_keys(keys)
+            off = np.ascontiguousarray(offsets, dtype=np.uint64)
+            if off.size < 1:
+                raise ValueError("get_scores: offsets must hold nbags + 1 values")
+            pk, n, po, nbags, flags = k.ctypes.data, k.size, off.ctypes.data, off.size - 1, _lib.PSKV_HOST
+            if out is None:
+                out = np.empty(n, dtype=self.dtype)
+            elif not (isinstance(out, np.ndarray) and out.dtype == self.dtype and out.flags.c_contiguous
+                      and out.size == n):
+                raise ValueError("get_scores: out must be a C-contiguous array of n values")
+            pout = out.ctypes.data
+        pq, q = self._bag_values("get_scores", "queries", queries, nbags * self.width, dev)
+        if dev and q is not None and not q.is_contiguous():
+            raise ValueError("get_scores: queries must be contiguous")
+        check(lib.pskv_get_scores(self._h, pk, n, pq, po, nbags, pout, flags))
+        del q
+        return out
+
     def apply_pooled_fm(self, keys, offsets, bag_scale, weights=None, bag_grads=None):
         """One optimizer step that is the backward pass of get_pooled_fm
         (pskv_apply_pooled_fm): bag_scale[b] = dL/dpair_b (nbags values),
