@@ -281,6 +281,22 @@ class HipStorage : public AbstractStorage {
     return third_party::SArray<char>(reply_vals);
   }
 
+  // Every query row against every key (pskv_get_score_matrix): the reply holds
+  // nq rows of keys.size() scores, row b the scores of queries[b * width ..).
+  third_party::SArray<char> SubGetScoreMatrix(const third_party::SArray<Key>& typed_keys,
+                                              const third_party::SArray<Val>& queries) {
+    if (queries.size() % width_ != 0) {
+      std::fprintf(stderr, "Check failed: queries.size() is a multiple of the width\n");
+      std::abort();
+    }
+    const uint64_t n = typed_keys.size(), nq = queries.size() / width_;
+    auto reply_vals = FrameArray<Val>(nq * n);
+    pskv_check(pskv_get_score_matrix(shard_, typed_keys.data(), n, queries.data(), nq, reply_vals.data(), n,
+                                     PSKV_HOST | PSKV_HOST_FRAME),
+               "pskv_get_score_matrix");
+    return third_party::SArray<char>(reply_vals);
+  }
+
   // One optimizer step that is the backward pass of SubGetPooledFm
   // (pskv_apply_pooled_fm): bag_scale holds dL/dpair per bag, bag_grads
   // dL/dsum ((offsets.size() - 1) * width values) or null.  Every row on the

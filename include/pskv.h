@@ -410,6 +410,43 @@
  *     is synchronous, a device call stream-ordered;
  *   - not provided: weights (scale the query), int32, a grouped form.
  *
+ * Score matrix pulls (pskv_get_score_matrix): every one of nq
+ * query rows against every one of n keys, the logit matrix of in-batch or
+ * shared sampled negatives,
+ *     out[b * out_stride + i] = sum_j queries[b * W + j] * row(keys[i])[j],
+ * b < nq, i < n, on the matrix units (v_mfma_f32_16x16x4_f32,
+ * v_mfma_f64_16x16x4_f64: no conversion, T is the shard's value type).
+ * out_stride counts elements and is >= n; the elements of a row of out past n
+ * are never written, so each shard of a range-partitioned candidate list fills
+ * its column block of the worker's one nq x S matrix in place.  The backward
+ * half needs no call of its own: the rows' gradients are dOut^T @ Q, a dense
+ * product the worker forms and pushes with pskv_apply; the queries' gradients
+ * are dOut @ rows, pskv_get_pooled with weights = a row of dOut per query.
+ *   The sum of one score is a function of the row's bits, the query's bits and
+ *   W alone: k ascending in steps of 4 from an accumulator of +0, one matrix
+ *   instruction per step (the four products and the accumulator summed inside
+ *   it), a last step of fewer than 4 elements filled with zeros.  Never a
+ *   function of the position of the key or the query, n, nq, out_stride, host
+ *   or device buffers, row or sparse shard, the alignment of queries or out,
+ *   an option or timing; no atomics on values.  Subnormal inputs: what the
+ *   matrix instructions do with them is not specified here (no ISA guide was
+ *   at hand); do not rely on either flushing or gradual underflow.
+ *   Rules: pskv_get_scores' where they apply --
+ *   - float shards only, any width, row and sparse shards; a Get that only reads;
+ *   - checked before the handle is looked at: flags; null keys with n > 0, null
+ *     queries with nq > 0, null out with both; out_stride < n;
+ *   - n == 0 or nq == 0: PSKV_OK, nothing is written or launched;
+ *   - a key that reads zeros gives a column of +0 against finite queries; on
+ *     the device path a key outside a row shard's range does and sets the
+ *     out-of-range status; a host call with such a key is refused before
+ *     anything is queued, out untouched; repeated keys are allowed;
+ *   - no access outside keys[0, n), queries[0, nq * W) and the first n elements
+ *     of each of out's nq rows; queries and out need element alignment only;
+ *   - one launch per call at every n and nq; timing: PSKV_TIME_POOLED's slot,
+ *     one operation per call, elements = n * nq; a host call is synchronous
+ *     (and stages nq * n scores: it is meant for small matrices), a device
+ *     call stream-ordered.
+ *
  * Sparse shards (pskv_shard_create_sparse): a shard whose memory
  * follows the number of keys it holds, not the span of the key space -- the
  * storage of a server under consistent hashing (a scattered 1/N of the keys),
@@ -806,6 +843,14 @@ int pskv_apply_pooled_fm(pskv_shard* s, const uint32_t* keys, uint64_t n, const 
  * Synchronous for host buffers, stream-ordered for PSKV_DEVICE ones. */
 int pskv_get_scores(pskv_shard* s, const uint32_t* keys, uint64_t n, const void* queries,
                     const uint64_t* offsets, uint64_t nbags, void* out, int flags);
+
+/* Score matrix pull (semantics: the header comment, "Score matrix pulls"):
+ * out[b * out_stride + i] = sum_j queries[b * W + j] * row(keys[i])[j], b < nq, i < n.
+ * keys: n keys; queries: nq * W values of the shard's type; out: nq rows of out_stride
+ * elements (out_stride >= n), the first n of each written.
+ * Synchronous for host buffers, stream-ordered for PSKV_DEVICE ones. */
+int pskv_get_score_matrix(pskv_shard* s, const uint32_t* keys, uint64_t n, const void* queries, uint64_t nq,
+                          void* out, uint64_t out_stride, int flags);
 
 /* Grouped pooled push (semantics: "Grouped pooled pushes"): ONE optimizer step
  * from the pooled pushes of nb workers, the step pskv_apply_pooled would make

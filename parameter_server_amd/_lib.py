@@ -84,7 +84,7 @@ EXPORTED = [
     "pskv_shard_set_optimizer_cfg", "pskv_shard_get_optimizer_cfg",
     "pskv_shard_create_sparse", "pskv_sparse_info_get", "pskv_sparse_keys", "pskv_index_time",
     "pskv_sparse_reserve", "pskv_sparse_set_growth", "pskv_sparse_get_growth", "pskv_sparse_erase",
-    "pskv_get_pooled_fm", "pskv_apply_pooled_fm", "pskv_get_scores",
+    "pskv_get_pooled_fm", "pskv_apply_pooled_fm", "pskv_get_scores", "pskv_get_score_matrix",
     "pskv_shard_set_initializer", "pskv_shard_get_initializer", "pskv_get_init",
 ]
 
@@ -200,6 +200,7 @@ def _load():
         "pskv_get_pooled_fm": ([vp, vp, u64, vp, vp, u64, vp, vp, i32], i32),
         "pskv_apply_pooled_fm": ([vp, vp, u64, vp, vp, u64, vp, vp, i32], i32),
         "pskv_get_scores": ([vp, vp, u64, vp, vp, u64, vp, i32], i32),
+        "pskv_get_score_matrix": ([vp, vp, u64, vp, u64, vp, u64, i32], i32),
         "pskv_apply_pooled_grouped": ([vp, ctypes.POINTER(PskvPoolBatch), u64, i32], i32),
         "pskv_shard_set_optimizer_cfg": ([vp, ctypes.POINTER(PskvOptimizerCfg)], i32),
         "pskv_shard_get_optimizer_cfg": ([vp, ctypes.POINTER(PskvOptimizerCfg), ctypes.POINTER(u64)], i32),

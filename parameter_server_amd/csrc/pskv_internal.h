@@ -436,6 +436,21 @@ struct ScoreArgs {
 hipError_t launch_row_scores(int dtype, bool nt, const ScoreArgs& a, const DenseView& d, const Ovf& o,
                              const RowShape& rs, hipStream_t st);
 
+// Score matrix pull (pskv_get_score_matrix; pskv.h "Score matrix pulls",
+// DESIGN.md §8s; pskv_matrix.hip), float shards: out[b * out_stride + i] =
+// sum_j queries[b * W + j] * row(keys[i])[j] on the matrix units.  One launch
+// at every n and nq; windows, query groups and the LDS layout: pskv_plan.h.
+struct ScoreMatArgs {
+  const uint32_t* keys;  // n
+  const void* queries;   // nq rows, element-aligned
+  void* out;             // nq rows of out_stride elements, the first n of each written; element-aligned
+  uint64_t n, nq, out_stride;
+};
+// rs as launch_row_scores'.  A key outside the range gives a column of +0 and
+// sets kErrRowOutOfRange.  nt: the scores leave in non-temporal stores.
+hipError_t launch_row_score_matrix(int dtype, bool nt, const ScoreMatArgs& a, const DenseView& d, const Ovf& o,
+                                   const RowShape& rs, hipStream_t st);
+
 // Sparse shards (pskv_index.hip): the hash index that maps a
 // uint32 key to a slot of the row arrays.  table: mask + 1 entries (a power of
 // two, >= 2 * capacity), linear probing from fmix32(key).  An entry is 0 when

@@ -463,6 +463,58 @@ PSKV_HD static inline uint64_t score_bag_walk(const uint64_t* off, uint64_t cb, 
   return cb;
 }
 
+// Score matrix pulls (pskv_get_score_matrix): every query
+// against every key.  A virtual workgroup owns one WINDOW of kMatKeys key
+// positions and one GROUP of consecutive query blocks (kMatQueries queries
+// each); it gathers the window's rows once and walks its blocks.  The number
+// of groups is a function of n and nq alone: one per window once the windows
+// alone make kMatFillWgs workgroups (each row then leaves HBM once), else as
+// many as it takes to reach that number, one block per group at the most.
+constexpr uint32_t kMatKeys = 64;
+constexpr uint32_t kMatQueries = 64;
+constexpr uint32_t kMatChunk = 32;       // elements of a k-chunk (a multiple of 4)
+constexpr uint32_t kMatFillWgs = 1024;   // workgroups wanted: four per CU of a 256-CU part
+constexpr uint32_t kMatRowsLds = 69632;  // bytes of LDS a window's rows may take and stay resident
+struct MatSplit {
+  uint64_t nwin, nqb;  // key windows, query blocks
+  uint64_t per;        // query blocks of a group
+  uint64_t groups;     // ceil(nqb / per)
+};
+PSKV_HD static inline MatSplit mat_split(uint64_t n, uint64_t nq) {
+  MatSplit m;
+  m.nwin = (n + kMatKeys - 1) / kMatKeys;
+  m.nqb = (nq + kMatQueries - 1) / kMatQueries;
+  m.per = m.groups = 0;
+  if (m.nwin == 0 || m.nqb == 0) return m;
+  uint64_t want = m.nwin >= kMatFillWgs ? 1 : (kMatFillWgs + m.nwin - 1) / m.nwin;
+  if (want > m.nqb) want = m.nqb;
+  m.per = (m.nqb + want - 1) / want;
+  m.groups = (m.nqb + m.per - 1) / m.per;
+  return m;
+}
+// The LDS of a workgroup: kMatKeys rows of `rstride` elements, kMatQueries
+// query rows of `qstride`, then the window's row offsets and their flags.  A
+// row of k elements (k a multiple of 4) lies at a stride that makes the MFMA
+// operand read -- lane l takes element l / 16 of row l % 16 -- free of bank
+// conflicts: 4-byte values, stride = 4 (mod 8) words, so that 16 rows times 4
+// elements fall on 64 distinct banks; 8-byte values, stride = 2 (mod 4), so
+// that the 32 lanes of a half-wave do.  resident: the whole row (width rounded
+// up to 4) fits kMatRowsLds and stays across the query blocks; else the rows
+// are gathered a k-chunk at a time.
+PSKV_HD static inline uint32_t mat_stride(uint32_t k4, int vb) { return vb == 4 ? (k4 | 4u) : k4 + 2u; }
+struct MatLds {
+  uint32_t resident, rstride, qstride, bytes;
+};
+PSKV_HD static inline MatLds mat_lds(uint32_t width, int vb) {
+  MatLds l;
+  const uint32_t w4 = (width + 3u) & ~3u;
+  l.resident = (uint64_t)kMatKeys * mat_stride(w4, vb) * (uint32_t)vb <= kMatRowsLds;
+  l.rstride = mat_stride(l.resident ? w4 : kMatChunk, vb);
+  l.qstride = mat_stride(kMatChunk, vb);
+  l.bytes = (kMatKeys * l.rstride + kMatQueries * l.qstride) * (uint32_t)vb + 2u * kMatKeys * 4u;
+  return l;
+}
+
 }  // namespace
 
 // ---------------------------------------------------- grouped pooled pushes

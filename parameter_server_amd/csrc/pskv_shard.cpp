@@ -2474,6 +2474,58 @@ int scores_impl(pskv_shard* s, const pskv_pool_batch& call, void* out, int flags
   return rows_to_host(s, hold, out_at, out_bytes, "shard stream (score pull to host)", back);
 }
 
+// ----------------------------------------------------- score matrix pulls
+// pskv_get_score_matrix (pskv.h "Score matrix pulls"): every
+// query against every key.  Through pool_front as a score pull: the queries
+// ride in bag_grads with nbags = nq.  The kernel reads no offsets: a device
+// call passes none, a host call stages nq + 1 internal ones so that the
+// staging layout is the pooled one.  One launch at every n and nq, timed as
+// one operation (kTimePooled, n * nq elements).  A host call's nq * n scores
+// get room behind the pooled layout and come back with stride n.
+// `c`: the call as the kernel reads it, bag_grads its query rows.
+int score_matrix_device(pskv_shard* s, const pskv_pool_batch& c, void* out, uint64_t out_stride) {
+  const ScoreMatArgs a{c.keys, c.bag_grads, out, c.n, c.nbags, out_stride};
+  const RowShape rs = fm_row_shape(s, {s->dense});
+  LaunchTimer t(s, kTimePooled, c.n * c.nbags);
+  PSKV_HIP(launch_row_score_matrix(s->dtype, s->tune_nt, a, s->read_view(s->dense), s->ovf, rs, s->stream));
+  t.done();
+  return PSKV_OK;
+}
+
+// The arguments hold (pskv_get_score_matrix checked them).
+int score_matrix_impl(pskv_shard* s, const uint32_t* keys, uint64_t n, const void* queries, uint64_t nq, void* out,
+                      uint64_t out_stride, int flags) {
+  if (const char* why = fm_refusal(s)) return fail(PSKV_EINVAL, std::string("pskv_get_score_matrix") + why);
+  ++s->n_get;
+  if (nq == 0 || n == 0) return PSKV_OK;  // no query, or no key: no score
+  const bool host = !(flags & PSKV_DEVICE);
+  std::vector<uint64_t> offsets;  // a host call's: staged, never read
+  if (host) {
+    offsets.assign(nq + 1, n);
+    offsets[0] = 0;
+  }
+  const pskv_pool_batch call{keys, nullptr, host ? offsets.data() : nullptr, queries, n, nq};
+  const size_t row = n * (size_t)s->vb, out_bytes = nq * row;
+  HstageHold hold(s);
+  size_t out_at = 0;
+  int rc = host ? fm_reserve_stage(s, call, out_bytes, &out_at) : PSKV_OK;
+  if (rc) return rc;
+  std::vector<pskv_pool_batch> v;
+  rc = pool_front(s, {call}, nullptr, flags,
+                  PoolFront{"pskv_get_score_matrix", /*writing=*/false, /*with_rows=*/true,
+                            "a score matrix pull reads the dense array only; out is untouched"},
+                  hold, &v);
+  if (rc) return rc;
+  if (!host) return score_matrix_device(s, v[0], out, out_stride);
+  if ((rc = score_matrix_device(s, v[0], static_cast<char*>(s->dstage) + out_at, n))) return rc;
+  std::vector<Piece> back;
+  char* h = static_cast<char*>(s->hstage) + out_at;
+  if (out_stride == n) add_pieces(back, h, static_cast<char*>(out), out_bytes, -1);
+  for (uint64_t b = 0; b < nq && out_stride != n; ++b)
+    add_pieces(back, h + b * row, static_cast<char*>(out) + b * out_stride * (size_t)s->vb, row, -1);
+  return rows_to_host(s, hold, out_at, out_bytes, "shard stream (score matrix pull to host)", back);
+}
+
 // The push: step_device over an FmPushArgs whose rows are the bag rows t_b,
 // computed from the pre-step parameters in front of the stamps (a long bag's
 // partial sums by the pooled pull's own chunk pass).  Stream order is what
@@ -3619,6 +3671,20 @@ int pskv_get_scores(pskv_shard* s, const uint32_t* keys, uint64_t n, const void*
   }
   if (!s) return fail(PSKV_EINVAL, "pskv_get_scores: null shard");
   return scores_impl(s, pskv_pool_batch{keys, nullptr, offsets, queries, n, nbags}, out, flags);
+}
+
+// pskv_get_scores' checks without the offsets, and the stride of out's rows.
+int pskv_get_score_matrix(pskv_shard* s, const uint32_t* keys, uint64_t n, const void* queries, uint64_t nq, void* out,
+                          uint64_t out_stride, int flags) {
+  if (bad_flags(flags)) return fail(PSKV_EINVAL, "pskv_get_score_matrix: unknown flags");
+  if (n && !keys) return fail(PSKV_EINVAL, "pskv_get_score_matrix: null keys with n > 0");
+  if (nq && !queries) return fail(PSKV_EINVAL, "pskv_get_score_matrix: null queries with nq > 0");
+  if (nq && n && !out) return fail(PSKV_EINVAL, "pskv_get_score_matrix: null out with n > 0 and nq > 0");
+  if (out_stride < n)
+    return fail(PSKV_EINVAL, "pskv_get_score_matrix: out_stride " + std::to_string(out_stride) + " < n = " +
+                                 std::to_string(n));
+  if (!s) return fail(PSKV_EINVAL, "pskv_get_score_matrix: null shard");
+  return score_matrix_impl(s, keys, n, queries, nq, out, out_stride, flags);
 }
 
 // pskv_apply_pooled's checks (pool_batch_error) with bag_scale in the place of

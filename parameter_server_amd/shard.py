@@ -516,6 +516,52 @@ class Shard:
         del q
         return out
 
+    def get_score_matrix(self, keys, queries, out=None):
+        """Every query against every key (pskv_get_score_matrix): out[b, i] =
+        queries[b] . row(keys[i]).  queries: (nq, width) or flat, contiguous,
+        of the shard's dtype.  numpy inputs -> host path, returns a numpy
+        (nq, n) array; torch tensors -> device path, stream-ordered.  out may
+        be a 2-D (nq, n) view whose last stride is 1 and whose first stride is
+        >= n, such as a column slice of a larger matrix."""
+        dev = _is_torch(keys)
+        if dev:
+            self._check_dev(keys)
+            n, count = keys.numel(), queries.numel()
+        else:
+            k = self._host_keys(keys)
+            n, count = k.size, np.size(queries)
+        if count % self.width:
+            raise ValueError(f"get_score_matrix: {count} query values are no multiple of the width {self.width}")
+        nq = count // self.width
+        pq, q = self._bag_values("get_score_matrix", "queries", queries, count, dev)
+        bad = ValueError("get_score_matrix: out must be an (nq, n) array of the shard's dtype, last stride 1, "
+                         "first stride >= n")
+        if dev:
+            import torch
+
+            if not q.is_contiguous():
+                raise ValueError("get_score_matrix: queries must be contiguous")
+            if out is None:
+                out = torch.empty((nq, n), dtype=_torch_dtype(self.dtype), device=keys.device)
+            elif (out.dtype != _torch_dtype(self.dtype) or tuple(out.shape) != (nq, n) or not out.is_cuda
+                  or out.device.index != self.device):
+                raise bad
+            stride = (out.stride(0) if nq > 1 else n, out.stride(1) if n > 1 else 1)
+            pk, pout, flags = keys.data_ptr(), out.data_ptr(), _lib.PSKV_DEVICE
+        else:
+            if out is None:
+                out = np.empty((nq, n), dtype=self.dtype)
+            elif not (isinstance(out, np.ndarray) and out.dtype == self.dtype and out.shape == (nq, n)):
+                raise bad
+            item = out.itemsize
+            stride = (out.strides[0] // item if nq > 1 else n, out.strides[1] // item if n > 1 else 1)
+            pk, pout, flags = k.ctypes.data, out.ctypes.data, _lib.PSKV_HOST
+        if nq and n and (stride[1] != 1 or stride[0] < n):
+            raise bad
+        check(lib.pskv_get_score_matrix(self._h, pk, n, pq, nq, pout, max(stride[0], n), flags))
+        del q
+        return out
+
     def apply_pooled_fm(self, keys, offsets, bag_scale, weights=None, bag_grads=None):
         """One optimizer step that is the backward pass of get_pooled_fm
         (pskv_apply_pooled_fm): bag_scale[b] = dL/dpair_b (nbags values),
